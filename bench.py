@@ -1,7 +1,13 @@
 #!/usr/bin/env python
 """bench.py — rays/sec of the R2L W256D88 hot path on MI355X (BASELINE.json metric).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
+
+A plain run times the graded leg only (the top-level record below: set-up, W warm-up steps, K timed steps, the line).
+--full adds every other leg (fast mode, bf16x3, trained-like weights, training, teacher, raw2outputs, CPU baseline and its
+parity check); --no-train / --no-teacher / --no-cpu-baseline trim that full run, --one-frame-leg / --segmented-leg add to it
+(and imply --full).
+--dump-outputs DIR: rank 0 writes what the timed graded leg computed in its last step, DIR/rgb.npy (float32 [9, 160000, 3]).
 
 N > 1: one rank per GPU over RCCL.  Started under torch.distributed.run (the driver's form) this process is a rank;
 started bare it launches the N ranks itself (plan_launch) — and exits non-zero rather than run on fewer GPUs than
@@ -21,7 +27,7 @@ and parity figure: "fast_mode.train" (default trio; at N > 1 the bucketed RCCL a
 the weight-gradient stages), "fast_mode.train_strong" (N > 1), "fast_mode.train_4096" / "train_12288", "fast_mode.teacher".
 "fp32_grade_products" = the bf16x3 family (six bf16 products per fp32 product).  "raw2outputs" = the alpha-composite kernel
 against the HBM roofline.  Every leg is timed by the same barrier-bracketed recipe with the full K / W.
-Prints ONE JSON line on rank 0; its last key "summary" is a digest of every leg.
+Prints ONE JSON line on rank 0; its last key "summary" is a digest of every leg that ran.
 """
 import argparse
 import json
@@ -433,7 +439,14 @@ def main():
     ap.add_argument("--one-frame-leg", action="store_true",
                     help="also time the render kernel ONE frame per launch (the step of rounds 1 / 2), for comparison; off by "
                          "default so that the kernel-trace of this command holds one population of render launches")
+    ap.add_argument("--full", action="store_true",
+                    help="run every leg, not only the graded one: fast mode, bf16x3, trained-like weights, training, teacher, "
+                         "raw2outputs, CPU baseline and parity (--one-frame-leg / --segmented-leg imply it)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the graded leg's output of its last timed step to DIR/rgb.npy (float32, rank 0's frames)")
     a = ap.parse_args()
+    if a.one_frame_leg or a.segmented_leg:
+        a.full = True
 
     plan = plan_launch(a.gpus, os.environ, torch.cuda.device_count())
     if plan[0] == "spawn":  # `python bench.py --gpus N` run bare: become the launcher of N ranks (one per GPU)
@@ -444,6 +457,7 @@ def main():
     torch.cuda.set_device(local_rank)
     device = torch.device("cuda", local_rank)
     rccl_ranks = 1
+    shared_gpu_test = False
     if distributed:
         os.environ.setdefault("MASTER_ADDR", "127.0.0.1")
         shared_gpu_test = os.environ.get("R2L_BENCH_SHARED_GPU_TEST") == "1"
@@ -545,6 +559,10 @@ def main():
                          peak_note="achieved counts ALGORITHMIC fp32 FLOPs (11 789 824 per ray) on the exact-fp32 MFMA "
                                    "(v_mfma_f32_32x32x2_f32, 157.3 TF dense: /opt/skills/guides/MI355X_MICROARCH.md)"),
     }
+    if a.dump_outputs and rank == 0:  # before any other leg launches: frames["rgb"] is the last timed step's output
+        dump_outputs(a.dump_outputs, frames["rgb"])
+    if not a.full:  # a plain run: the graded leg is the whole measurement
+        return finish(out, rank, distributed, shared_gpu_test)
 
     def fast_roofline_extras(r):
         r.update({"frac_of_measured_mfma_only_rate": r["achieved"] * 3. / SUSTAINED_FP16_MFMA_ONLY,
@@ -673,6 +691,18 @@ def main():
         out["parity_max_abs_err_vs_cpu"] = (rgb_gpu_check["fp32_mfma"][rows] - rgb_cpu).abs().max().item()
         fast["parity_max_abs_err_vs_cpu"] = (rgb_gpu_check["fp16x2"][rows] - rgb_cpu).abs().max().item()
         out["fp32_grade_products"]["parity_max_abs_err_vs_cpu"] = (rgb_gpu_check["bf16x3"][rows] - rgb_cpu).abs().max().item()
+    finish(out, rank, distributed, shared_gpu_test)
+
+
+def dump_outputs(path, rgb):
+    """--dump-outputs: what the graded leg's caller received from its last timed step, rgb [FRAMES_PER_STEP, H*W, 3] (17 MB)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    np.save(os.path.join(path, "rgb.npy"), rgb.detach().float().cpu().numpy())
+
+
+def finish(out, rank, distributed, shared_gpu_test):
+    """The line's closing keys, the line itself (rank 0) and the end of the process group."""
     if distributed and shared_gpu_test:
         out["shared_gpu_test"] = "ranks share ONE GPU over gloo (R2L_BENCH_SHARED_GPU_TEST=1): a walk through the N > 1 code, not a measurement"
     out["leg_wall_s"] = {k: round(v, 3) for k, v in LEG_WALL.items()}  # rank 0's host wall per leg, warm-up and set-up included

@@ -547,3 +547,36 @@ def test_pool_kernels_vs_torch_ops():
         pa.update(r2, *xa, B)
         pb.update(r2, *xb, B)
     assert pa.full and torch.equal(pa.pool, pb.pool)
+
+
+def test_bench_plain_run_and_dumped_outputs(tmp_path):
+    """`bench.py --steps K --warmup W --dump-outputs DIR` without --full: ONE line with the graded leg only (no other leg runs),
+    and DIR/rgb.npy = the frames of its last timed step, which the oracle reproduces on a sample of rays."""
+    import json
+    import subprocess
+    import sys
+    import bench
+    dump = tmp_path / "dump"
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "1", "--steps", "2", "--warmup", "1",
+                        "--dump-outputs", str(dump)], env={k: v for k, v in os.environ.items() if not k.startswith("R2L_")},
+                       cwd=str(tmp_path), capture_output=True, text=True, timeout=600)
+    assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
+    lines = [l for l in r.stdout.splitlines() if l.startswith("{")]
+    assert len(lines) == 1, r.stdout[-2000:]
+    out = json.loads(lines[0])
+    assert out["unit"] == "rays/s" and out["higher_is_better"] is True and out["value"] > 0
+    assert out["steps"] == 2 and out["warmup"] == 1 and out["ms_per_step"] > 0
+    assert abs(out["value"] - bench.FRAMES_PER_STEP * bench.H * bench.W / (out["ms_per_step"] * 1e-3)) < 1e-6 * out["value"]
+    assert out["dtype"].startswith("f32 (v_mfma_f32_32x32x2_f32") and out["roofline"]["peak"] == 157.3
+    assert set(out["leg_wall_s"]) == {"render"} and list(out)[-1] == "summary"
+    assert not set(out) & {"fast_mode", "fp32_grade_products", "train", "teacher", "raw2outputs", "cpu_baseline"}
+    rgb = np.load(str(dump / "rgb.npy"))
+    assert rgb.dtype == np.float32 and rgb.shape == (bench.FRAMES_PER_STEP, bench.H * bench.W, 3) and np.isfinite(rgb).all()
+    # the last timed step is step W + K - 1 = 2: test poses 18 .. 26 of bench's 40, theta = -180 + 9 k
+    _, _, sd = bench.make_model("cpu")
+    dirs, z = O.pixel_dirs(bench.H, bench.W, bench.FOCAL), O.z_vals(16, 2., 6.)
+    rows = torch.randperm(bench.H * bench.W, generator=torch.Generator().manual_seed(3))[:512]
+    for j in (0, bench.FRAMES_PER_STEP - 1):
+        c2w = torch.from_numpy(O.pose_spherical(-180. + 9. * (2 * bench.FRAMES_PER_STEP + j), -30., 4.)[:3, :4])
+        ref = O.r2l_forward(sd, O.positional_embed(O.sample_test(dirs, z, c2w)[rows], 10))
+        assert np.abs(rgb[j][rows.numpy()] - ref.numpy()).max() < 1e-4, j

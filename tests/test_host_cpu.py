@@ -598,14 +598,74 @@ def test_c99_host_compiles_links_and_runs(tmp_path):
     assert r.returncode == 0 and "C99 host ok" in r.stdout, r.stdout + r.stderr
 
 
-@pytest.mark.skipif(not os.path.isdir("/root/reference"), reason="needs the reference tree (dev container only)")
-def test_checkpoint_written_here_loads_in_the_reference(tmp_path):
-    """"checkpoints written here load in the reference".  save_ckpt's .tar (pickled network_fn + state dict +
-    Adam-format optimizer state) is opened in a SEPARATE process whose sys.path holds only the reference: the pickle resolves to
-    the reference's own model.nerf_raybased.NeRF_v3_2, the forward matches bit for bit, torch.optim.Adam takes the state."""
+def _unpickle_symbolically(path):
+    """A torch .tar unpickled WITHOUT importing what it names: every global (module, qualname) becomes a recording stand-in
+    class (its instances keep their constructor arguments and BUILD state), tensor storages a placeholder.  Returns the
+    object and the set of globals the file names."""
+    import io
+    import pickle
+    import zipfile
+    classes = {}
+
+    class Stub:
+        def __new__(cls, *a, **k):
+            return object.__new__(cls)
+
+        def __init__(self, *a, **k):
+            self.args = a
+
+        def __setstate__(self, state):
+            self.state = state
+
+    class Unpickler(pickle.Unpickler):
+        def find_class(self, module, name):
+            if module == "collections" and name == "OrderedDict":
+                return super().find_class(module, name)
+            if (module, name) not in classes:
+                classes[(module, name)] = type(name, (Stub,), {"key": (module, name)})
+            return classes[(module, name)]
+
+        def persistent_load(self, pid):
+            return "storage"
+
+    with zipfile.ZipFile(path) as z:
+        data = [n for n in z.namelist() if n.endswith("/data.pkl")]
+        assert len(data) == 1, z.namelist()
+        obj = Unpickler(io.BytesIO(z.read(data[0]))).load()
+    return obj, set(classes), Stub
+
+
+def _module_objects(obj, stub):
+    """(module, qualname) -> [BUILD state dict] of every pickled nn.Module-like object (state holds `_modules`) below obj."""
+    found, seen, todo = {}, set(), [obj]
+    while todo:
+        o = todo.pop()
+        if id(o) in seen:
+            continue
+        seen.add(id(o))
+        if isinstance(o, dict):
+            todo += list(o.values())
+        elif isinstance(o, (list, tuple)):
+            todo += list(o)
+        elif isinstance(o, stub):
+            st = getattr(o, "state", None)
+            if isinstance(st, dict) and "_modules" in st:
+                found.setdefault(o.key, []).append(st)
+            todo += [st, getattr(o, "args", ())]
+    return found
+
+
+def test_checkpoint_written_here_loads_in_the_reference(tmp_path, golden_dir):
+    """"checkpoints written here load in the reference".  The reference's loader unpickles save_ckpt's .tar
+    (pickled network_fn + state dict + Adam-format optimizer state) into its OWN classes; what that takes is on record in
+    ckpt_w32d6.tar, which the reference's save_ckpt wrote.  Both files are unpickled without importing anything they name: ours
+    names no global the reference's file does not (model.nerf_raybased.NeRF_v3_2 / ResMLP, torch), and every module object
+    carries at least the attributes, and exactly the child modules, of the reference's objects of its class.  Ours then loads
+    back to the same forward bit for bit, and torch.optim.Adam takes its optimizer state (the reference's rgb from the
+    reference's own checkpoint: test_unpickle_reference_checkpoint)."""
     import argparse
     from model.nerf_raybased import NeRF_v3_2
-    from r2l_amd.checkpoint import save_ckpt
+    from r2l_amd.checkpoint import load_ckpt, save_ckpt
     trial = argparse.Namespace(ON=True, body_arch="resmlp", inact="relu", outact="none", res_scale=1., n_learnable=2,
                                n_block=-1, near=-1, far=-1)
     args = argparse.Namespace(netdepth=8, netwidth=256, layerwise_netwidths="", act="relu", linear_tail=False,
@@ -617,24 +677,30 @@ def test_checkpoint_written_here_loads_in_the_reference(tmp_path):
     m(x).sum().backward()
     opt.step()
     # (with the arithmetic record the drivers store, driver.apply_arithmetic: a key the reference's loaders never read)
-    save_ckpt(str(tmp_path / "ckpt.tar"), 7, m, opt.state_dict(), 1.0, 3,
-              r2l_config={"precision": "fp32_mfma", "dw_mode": "exact", "requested": {"precision": "fp32_mfma", "dw_mode": "auto"}})
-    torch.save({"x": x, "y": m(x).detach()}, str(tmp_path / "io.pt"))
-    code = ("import sys; sys.path.insert(0, '/root/reference')\n"
-            "import torch, model.nerf_raybased as rm\n"
-            "assert rm.__file__.startswith('/root/reference')\n"
-            "ck = torch.load(%r, weights_only=False, map_location='cpu')\n"
-            "m = ck['network_fn']\n"
-            "assert type(m) is rm.NeRF_v3_2 and ck['global_step'] == 7 and ck['r2l_config']['precision'] == 'fp32_mfma'\n"
-            "m.load_state_dict(ck['network_fn_state_dict'])\n"
-            "io = torch.load(%r)\n"
-            "assert torch.equal(m(io['x']), io['y'])\n"
-            "opt = torch.optim.Adam(m.parameters(), lr=5e-4)\n"
-            "opt.load_state_dict(ck['optimizer_state_dict'])\n"
-            "assert len(opt.state_dict()['state']) == 16\n"
-            "print('REFERENCE LOADED IT')\n" % (str(tmp_path / "ckpt.tar"), str(tmp_path / "io.pt")))
-    r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=600, cwd=str(tmp_path))
-    assert "REFERENCE LOADED IT" in r.stdout, r.stdout + r.stderr
+    path = save_ckpt(str(tmp_path / "ckpt.tar"), 7, m, opt.state_dict(), 1.0, 3,
+                     r2l_config={"precision": "fp32_mfma", "dw_mode": "exact", "requested": {"precision": "fp32_mfma", "dw_mode": "auto"}})
+    ref, ref_globals, ref_stub = _unpickle_symbolically(os.path.join(golden_dir, "ckpt_w32d6.tar"))
+    ours, our_globals, our_stub = _unpickle_symbolically(path)
+    assert ("model.nerf_raybased", "NeRF_v3_2") in ref_globals and ("model.nerf_raybased", "ResMLP") in ref_globals
+    assert our_globals <= ref_globals, sorted(our_globals - ref_globals)
+    assert set(ours) >= set(ref) and ours["global_step"] == 7 and ours["r2l_config"]["precision"] == "fp32_mfma"
+    assert ours["network_fn"].key == ref["network_fn"].key == ("model.nerf_raybased", "NeRF_v3_2")
+    ref_mods, our_mods = _module_objects(ref, ref_stub), _module_objects(ours, our_stub)
+    assert set(our_mods) <= set(ref_mods) and ("model.nerf_raybased", "ResMLP") in our_mods
+    for cls, states in our_mods.items():
+        need = set().union(*(set(st) for st in ref_mods[cls]))
+        children = {tuple(st["_modules"]) for st in ref_mods[cls]}
+        for st in states:
+            assert need <= set(st), (cls, sorted(need - set(st)))
+            assert tuple(st["_modules"]) in children or cls[0].startswith("torch."), (cls, list(st["_modules"]))
+    ck = load_ckpt(path, map_location="cpu")
+    back = ck["network_fn"]
+    back.load_state_dict(ck["network_fn_state_dict"])
+    with torch.no_grad():
+        assert torch.equal(back(x), m(x))
+    opt2 = torch.optim.Adam(back.parameters(), lr=5e-4)
+    opt2.load_state_dict(ck["optimizer_state_dict"])
+    assert len(opt2.state_dict()["state"]) == 16
 
 
 def test_checkpoint_helpers_error_behaviour():

@@ -93,7 +93,7 @@ def test_native_allreduce_two_ranks(tmp_path):
 
 @two_gpus
 def test_bench_two_gpus_on_rccl():
-    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1"],
+    r = subprocess.run([sys.executable, os.path.join(ROOT, "bench.py"), "--gpus", "2", "--steps", "3", "--warmup", "1", "--full"],
                        env={k: v for k, v in os.environ.items() if not k.startswith("R2L_")}, capture_output=True, text=True,
                        timeout=1500)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]

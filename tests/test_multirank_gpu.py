@@ -121,7 +121,7 @@ def test_bench_two_ranks_walk(tmp_path):
     env.update(MASTER_ADDR="127.0.0.1", R2L_BENCH_SHARED_GPU_TEST="1")
     r = subprocess.run([sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", "2",
                         "--master-addr", "127.0.0.1", "--master-port", "29617", os.path.join(ROOT, "bench.py"),
-                        "--gpus", "2", "--steps", "2", "--warmup", "1"], env=env, capture_output=True, text=True,
+                        "--gpus", "2", "--steps", "2", "--warmup", "1", "--full"], env=env, capture_output=True, text=True,
                        timeout=900)
     assert r.returncode == 0, r.stdout[-3000:] + r.stderr[-3000:]
     lines = [l for l in r.stdout.splitlines() if l.startswith("{")]

@@ -164,7 +164,7 @@ def test_bench_eight_ranks_walk(tmp_path):
     env.pop("R2L_DIST_BACKEND", None)
     env["R2L_BENCH_SHARED_GPU_TEST"] = "1"
     cmd = [sys.executable, "-m", "torch.distributed.run", "--nnodes=1", "--nproc-per-node", str(WORLD), "--master-addr", "127.0.0.1",
-           "--master-port", "29663", os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--steps", "2", "--warmup", "1",
+           "--master-port", "29663", os.path.join(ROOT, "bench.py"), "--gpus", str(WORLD), "--steps", "2", "--warmup", "1", "--full",
            # (eight ranks share ONE GPU's memory here: the default 98 304-ray legs hold 36 GB of stash per rank — 288 GB, the whole
            # HBM, and the walk then spends minutes in allocator retries; a third of the rays walks the same code)
            "--train-rays", "32768"]

@@ -6,7 +6,7 @@ OUT=$REPO/gpurun_out/abkt
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
 for L in "$@"; do
-  R2L_LIB_PATH=$REPO/r2l_amd/lib/$L rocprofv3 --kernel-trace --stats -d $OUT/$L -o kt --output-format csv -- python $REPO/bench.py --steps 8 --warmup 2 --no-cpu-baseline --no-teacher > $OUT/$L.log 2>&1
+  R2L_LIB_PATH=$REPO/r2l_amd/lib/$L rocprofv3 --kernel-trace --stats -d $OUT/$L -o kt --output-format csv -- python $REPO/bench.py --full --steps 8 --warmup 2 --no-cpu-baseline --no-teacher > $OUT/$L.log 2>&1
   f=$(find $OUT/$L -name "*kernel_stats.csv" | head -1)
   python - "$f" > $OUT/$L.txt <<'PY'
 import csv, sys

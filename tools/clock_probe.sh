@@ -2,7 +2,7 @@
 # effective shader clock per kernel: GRBM_GUI_ACTIVE / kernel wall time of the same (profiled) pass
 export TMPDIR=/tmp
 REPO=$(pwd); OUT=$REPO/gpurun_out/clk; rm -rf $OUT; mkdir -p $OUT; cd /tmp
-rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES -d $OUT/a -o a --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
+rocprofv3 --kernel-trace --pmc GRBM_GUI_ACTIVE SQ_WAVE_CYCLES SQ_VALU_MFMA_BUSY_CYCLES -d $OUT/a -o a --output-format csv -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline > /dev/null 2>&1
 cd $REPO
 python - <<'PY'
 import csv, glob, collections

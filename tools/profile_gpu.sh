@@ -4,13 +4,13 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/prof
 rm -rf $OUT; mkdir -p $OUT
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 cat $OUT/bench.json
 cd /tmp
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py --steps 20 --warmup 3 --no-cpu-baseline > $OUT/kt.log 2>&1
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc1.log 2>&1
-rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc2.log 2>&1
-rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc3.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py --full --steps 20 --warmup 3 --no-cpu-baseline > $OUT/kt.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc1.log 2>&1
+rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc2.log 2>&1
+rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py --full --steps 3 --warmup 1 --no-cpu-baseline --no-teacher > $OUT/pmc3.log 2>&1
 cd $REPO
 python - <<'PY'
 import csv, glob, collections, json

@@ -6,11 +6,11 @@ OUT=$REPO/gpurun_out/${1:-r02_train}
 rm -rf $OUT; mkdir -p $OUT
 cd /tmp
 ARGS="--steps 6 --warmup 2 --no-cpu-baseline --no-teacher"
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py $ARGS > $OUT/kt.log 2>&1
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc1.log 2>&1
-rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc2.log 2>&1
-rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc3.log 2>&1
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA -d $OUT/pmc4 -o pmc4 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc4.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/kt.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc1.log 2>&1
+rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc2.log 2>&1
+rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc3.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA -d $OUT/pmc4 -o pmc4 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc4.log 2>&1
 cd $REPO
 python - "$OUT" <<'PY'
 import csv, glob, collections, json, sys

@@ -5,15 +5,15 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 OUT=$REPO/gpurun_out/r05
 rm -rf $OUT; mkdir -p $OUT
-python bench.py --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
+python bench.py --full --steps 20 --warmup 3 > $OUT/bench.json 2> $OUT/bench.err
 cd /tmp
 ARGS="--steps 20 --warmup 3 --no-cpu-baseline"
-rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py $ARGS > $OUT/kt.log 2>&1
+rocprofv3 --kernel-trace --stats -d $OUT/kt -o kt --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/kt.log 2>&1
 ARGS="--steps 3 --warmup 1 --no-cpu-baseline --no-teacher"
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc1.log 2>&1
-rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc2.log 2>&1
-rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc3.log 2>&1
-rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA -d $OUT/pmc4 -o pmc4 --output-format csv -- python $REPO/bench.py $ARGS > $OUT/pmc4.log 2>&1
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d $OUT/pmc1 -o pmc1 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc1.log 2>&1
+rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc2 -o pmc2 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc2.log 2>&1
+rocprofv3 --pmc WRITE_SIZE -d $OUT/pmc3 -o pmc3 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc3.log 2>&1
+rocprofv3 --pmc SQ_LDS_BANK_CONFLICT SQ_LDS_IDX_ACTIVE SQ_INSTS_VALU SQ_INSTS_MFMA -d $OUT/pmc4 -o pmc4 --output-format csv -- python $REPO/bench.py --full $ARGS > $OUT/pmc4.log 2>&1
 rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_INSTS_VALU SQ_INSTS_MFMA -d $OUT/pmc5 -o pmc5 --output-format csv -- python $REPO/tools/teacher_time.py > $OUT/pmc5.log 2>&1
 # the alpha-composite kernel alone (eager launches on HBM-resident inputs): traffic counters, then busy / instruction counters
 rocprofv3 --pmc FETCH_SIZE -d $OUT/pmc6 -o pmc6 --output-format csv -- python $REPO/tools/r2o_time.py > $OUT/pmc6.log 2>&1

@@ -4,9 +4,9 @@ export TMPDIR=/tmp
 REPO=$(pwd)
 cd /tmp
 rm -rf /tmp/rpm
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU -d /tmp/rpm -o rpm --output-format csv -- python $REPO/bench.py --no-cpu-baseline --no-train --no-teacher --steps 3 --warmup 1 > /tmp/rpm.log 2>&1 || tail -20 /tmp/rpm.log
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY SQ_INSTS_VALU -d /tmp/rpm -o rpm --output-format csv -- python $REPO/bench.py --full --no-cpu-baseline --no-train --no-teacher --steps 3 --warmup 1 > /tmp/rpm.log 2>&1 || tail -20 /tmp/rpm.log
 rm -rf /tmp/rpm2
-rocprofv3 --pmc SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES -d /tmp/rpm2 -o rpm2 --output-format csv -- python $REPO/bench.py --no-cpu-baseline --no-train --no-teacher --steps 3 --warmup 1 > /tmp/rpm2.log 2>&1 || tail -20 /tmp/rpm2.log
+rocprofv3 --pmc SQ_WAIT_INST_LDS SQ_INSTS_LDS SQ_LDS_BANK_CONFLICT SQ_ACTIVE_INST_LDS SQ_WAVE_CYCLES -d /tmp/rpm2 -o rpm2 --output-format csv -- python $REPO/bench.py --full --no-cpu-baseline --no-train --no-teacher --steps 3 --warmup 1 > /tmp/rpm2.log 2>&1 || tail -20 /tmp/rpm2.log
 python - <<'PY'
 import csv, glob, collections
 for d in ("/tmp/rpm", "/tmp/rpm2"):

@@ -3,7 +3,7 @@
 export TMPDIR=/tmp
 REPO=$(pwd)
 cd /tmp
-rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d /tmp/tpm -o tpm --output-format csv -- python $REPO/bench.py --no-cpu-baseline --no-train --steps 2 --warmup 1 > /tmp/tpm.log 2>&1 || tail -20 /tmp/tpm.log
+rocprofv3 --pmc SQ_VALU_MFMA_BUSY_CYCLES SQ_BUSY_CYCLES GRBM_GUI_ACTIVE SQ_WAVES SQ_WAVE_CYCLES SQ_WAIT_ANY SQ_WAIT_INST_ANY -d /tmp/tpm -o tpm --output-format csv -- python $REPO/bench.py --full --no-cpu-baseline --no-train --steps 2 --warmup 1 > /tmp/tpm.log 2>&1 || tail -20 /tmp/tpm.log
 python - <<'PY'
 import csv, glob, collections
 f = glob.glob("/tmp/tpm/**/*counter_collection.csv", recursive=True)[0]
