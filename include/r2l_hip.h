@@ -277,6 +277,28 @@ int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, const float* v
                         const float* wstream, const float* tparams, float* raw, int64_t R, int S, void* stream,
                         const r2l_config* cfg);
 
+/* ---- NeRF teacher training (exact fp32; utils/train_nerf.py) ---------------------------------------------------------
+ * One step of main.py:1319-1406 for the teacher: loss = img2mse(rgb) + img2mse(rgb0) (helpers:19), gradients by hand.
+ * Stash: floats of the layer outputs kept for the backward pass of P = R*S points (relu(h0..h7), the feature, relu(views)). */
+int64_t r2l_teacher_stash_floats(int64_t P);
+/* The fp32-MFMA chain of r2l_teacher_mlp_cfg(precision = fp32_mfma) (raw bit-identical), also writing the stash. */
+int r2l_teacher_mlp_train(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                          const float* wstream, const float* tparams, float* raw, float* stash, int64_t R, int S, void* stream);
+/* draw[R,S,4] = d loss / d raw for loss = img2mse(rgb_map, target) (helpers:19; main.py:1353-1363), through raw2outputs
+ * (main.py:556-621: relu(sigma + noise), the 1e10 last dists times |d|, cumprod(1 - alpha + 1e-10), white_bkgd rgb + 1 - acc);
+ * alpha = 1 is handled by suffix sums, no division by 1 - alpha.  sqerr[R] = sum_c (rgb_map - target)^2 for r2l_loss_finish
+ * with inv_denom = 1/(3R).  noise[R,S] optional (already scaled by raw_noise_std).  1 <= S <= 256. */
+int r2l_raw2outputs_backward(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
+                             const float* target, float* draw, float* sqerr, int64_t R, int S, void* stream);
+/* Scratch floats of r2l_teacher_backward for P points. */
+int64_t r2l_teacher_train_work_floats(int64_t P);
+/* grads[595 844] (tparams order) = d loss / d tparams from draw and the stash of r2l_teacher_mlp_train on the same points
+ * (NeRF.forward, model/nerf_raybased.py:377-401, backwards; embedder helpers:24-74 recomputed).  Overwrites grads; fixed
+ * reduction order, no atomics: bit-reproducible. */
+int r2l_teacher_backward(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                         const float* tparams, const float* stash, const float* draw, float* grads, float* work, int64_t R,
+                         int S, void* stream);
+
 /* z_out[R,S] = near*(1-t)+far*t, with stratified jitter when t_rand[R,S] != NULL (create_data.py:457-482).
  * near/far: per-ray values read at near[r*nf_stride], far[r*nf_stride]; ttab[2S] = t_vals ++ (1 - t_vals). */
 int r2l_stratified_z(const float* near, const float* far, int nf_stride, const float* ttab, const float* t_rand,

@@ -85,6 +85,11 @@ SIGNATURES = {
     "r2l_pack_teacher": (_i, [_p, _p, _p]),
     "r2l_teacher_mlp": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_teacher_mlp_cfg": (_i, [_p, _p, _p, _p, _p, _p, _p, _l, _i, _p, _cfgp]),
+    "r2l_teacher_stash_floats": (_l, [_l]),
+    "r2l_teacher_mlp_train": (_i, [_p, _p, _p, _p, _p, _p, _p, _p, _l, _i, _p]),
+    "r2l_raw2outputs_backward": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _l, _i, _p]),
+    "r2l_teacher_train_work_floats": (_l, [_l]),
+    "r2l_teacher_backward": (_i, [_p] * 9 + [_l, _i, _p]),
     "r2l_stratified_z": (_i, [_p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "r2l_raw2outputs": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_sample_pdf_sort": (_i, [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _p]),

@@ -140,7 +140,28 @@ struct TeacherArgs {
     float* raw;             // [R,S,4]
     int64_t n_pts;          // R*S
     int S;
+    float* stash;           // training only (r2l_teacher_mlp_train): the layer outputs of every point, T_STASH_* below
 };
+
+// Stash of the forward with stash (teacher training, r2l_teacher_train.hip reads it): slot l of [P,256] floats for l = 0..7
+// holds relu(layer l), slot 8 the feature (no ReLU), slot 9 relu(views layer) as [P,128].  ReLU masks follow from the values.
+#define T_STASH_FEAT 8
+#define T_STASH_VIEWS 9
+#define T_STASH_PER_POINT (9 * T_W + 128)
+
+// one wave's NT 32-feature tiles of a layer output (accumulator layout: point = lane & 31, feature 32T + 8q + 4h + j)
+template <int NT>
+__device__ __forceinline__ void t_stash_store(float* dst, const f32x16 (&a)[NT], int h, bool relu) {
+#pragma unroll
+    for (int T = 0; T < NT; ++T)
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            f32x4 o;
+#pragma unroll
+            for (int j = 0; j < 4; ++j) o[j] = relu ? fmaxf(a[T][4 * q + j], 0.f) : a[T][4 * q + j];
+            *reinterpret_cast<f32x4*>(dst + 32 * T + 8 * q + 4 * h) = o;
+        }
+}
 
 #ifndef T_RING
 #define T_RING 1  // depth of the weight ring (1 or 2; same-box A/B: 2 is 0.6 % slower here); slot of group i = i & (T_RING - 1)
@@ -187,6 +208,8 @@ __device__ __forceinline__ void t_pe_gemm(f32x16 (&acc)[R2L_NT], const float (&p
     t_pe_steps<BASE, 0, NG>(acc, p, h, ws, t_xyz_group<0>(p, h));
 }
 
+// STASH: the same chain (bit-identical raw), plus every layer output written to a.stash for the backward pass
+template <bool STASH>
 __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherArgs a) {
     const TOff off = t_offsets();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
@@ -217,6 +240,9 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         mfma_bias_group<true, 0>(x, ws, one_h0);
         t_pe_gemm<1, T_PE_GROUPS>(x, p, h, ws);  // 1 + 9 groups: the loop below starts at an even group index
     }
+    float* const st = STASH ? a.stash + pc * T_W : nullptr;  // slot l of this point: st + l * n_pts * T_W
+    if constexpr (STASH)
+        if (valid) t_stash_store(st, x, h, true);
     // (L1,L2) (L3,L4) (L5,L6) (L7,feature): t = W_odd relu(x) [+ W5pe pe] + b ; x = W_even relu(t) + b
     float alpha = 0.f;
     NoHook nh;
@@ -232,6 +258,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
             t_pe_gemm<1, T_PE5_GROUPS>(t, pp, hh, ws);
         }
         gemm256x<true, T_SLOT(1)>(t, x, ws, nh);
+        if constexpr (STASH)
+            if (valid) t_stash_store(st + (2 * k + 1) * a.n_pts * T_W, t, h, true);
         if (k == 3) {  // alpha_linear on relu(layer 7)
             float acc = 0.f;
 #pragma unroll
@@ -247,6 +275,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         }
         mfma_bias_group<true, T_SLOT(1)>(x, ws, one_h0);
         gemm256x<true, 0>(x, t, ws, nh);  // k == 3: x = feature_linear(relu(layer 7)), consumed WITHOUT a ReLU below
+        if constexpr (STASH)
+            if (valid) t_stash_store(st + (2 * k + 2) * a.n_pts * T_W, x, h, k < 3);
     }
     // views layer: v[128] = Wv [feature, dir-embedding] + bv   (4 output tiles; ReLU applied by the rgb head)
     f32x16 v[4];
@@ -290,6 +320,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
             else mfma_group4x2<T_SLOT(1)>(v, ws, ba, bb);
         }
     }
+    if constexpr (STASH)
+        if (valid) t_stash_store(a.stash + T_STASH_VIEWS * a.n_pts * T_W + pc * 128, v, h, true);
     // rgb = Wrgb relu(v) + b
     float acc3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -378,7 +410,26 @@ extern "C" int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, con
         return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, wstream + t_stream32_floats(), params, raw, a.n_pts, S,
                                 (hipStream_t)stream, nullptr);
     const int64_t tiles = (a.n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-    hipLaunchKernelGGL(r2l_teacher_mlp_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ---- teacher training: the fp32 chain with stash (the backward pass is in r2l_teacher_train.hip) ----------------------
+extern "C" int64_t r2l_teacher_stash_floats(int64_t P) { return P < 0 ? -1 : P * (int64_t)T_STASH_PER_POINT; }
+
+extern "C" int r2l_teacher_mlp_train(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                     const float* wstream, const float* params, float* raw, float* stash, int64_t R, int S,
+                                     void* stream) {
+    R2L_REQUIRE(R >= 0 && S >= 0, "r2l_teacher_mlp_train: negative R / S");
+    if (R == 0 || S == 0) return 0;
+    R2L_REQUIRE(rays_o && rays_d && viewdirs && z && wstream && params && raw && stash,
+                "r2l_teacher_mlp_train: a required pointer is NULL");
+    TeacherArgs a{};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
+    a.raw = raw; a.n_pts = R * (int64_t)S; a.S = S; a.stash = stash;
+    const int64_t tiles = (a.n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
+    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

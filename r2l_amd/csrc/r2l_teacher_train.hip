@@ -1,0 +1,398 @@
+// r2l_teacher_train.hip — backward pass of the NeRF teacher for training it (step 1 of the pipeline, /root/reference/main.py
+// --model_name nerf: render_rays + img2mse(rgb) + img2mse(rgb0) + loss.backward(), main.py:1319-1406), exact fp32 throughout:
+//   r2l_raw2outputs_backward : loss seed 2 (rgb_map - target) / (3R) and autograd of raw2outputs (main.py:556-621) -> draw
+//   r2l_teacher_backward     : dX chain and weight / bias gradients of NeRF(D=8, W=256, 63+27, skips=[4], use_viewdirs)
+//                              (model/nerf_raybased.py:357-401) from draw and the stash of r2l_teacher_mlp_train
+// The products are fp32-input MFMA (v_mfma_f32_32x32x2_f32) in one LDS-tiled GEMM kernel with loader / epilogue functors:
+// the dX products G_{l-1} = (G_l W_l) * relu'(h_{l-1}) (weights read row-major, no transposed stream needed) and the weight
+// products dW_l = G_l^T A_l reduced over the points in fixed-size chunks into partial slabs, summed in a fixed order by a second
+// kernel (no atomics: a step is bit-reproducible).  The positional encodings (A of layer 0, of layer 5's first 63 columns and
+// of the views layer's last 27) are not stored: the GEMM's loader recomputes them from (o, d, z) / viewdirs.
+#include "r2l_common.h"
+
+#define TT_W 256
+#define TT_XYZ 63
+#define TT_DIR 27
+#define TT_BM 128
+#define TT_BN 128
+#define TT_BK 16
+#define TT_KCHUNK 2048  // points per partial slab of a weight gradient: fixed, so the reduction order never changes
+
+// ---- flat parameter offsets (state_dict order; same census as t_offsets of r2l_teacher_mlp.hip) ------------------------
+struct TTOff {
+    int64_t w[8], b[8], views_w, views_b, feat_w, feat_b, alpha_w, alpha_b, rgb_w, rgb_b, total;
+};
+static TTOff tt_offsets() {
+    TTOff o;
+    int64_t p = 0;
+    for (int i = 0; i < 8; ++i) {
+        const int fin = i == 0 ? TT_XYZ : (i == 5 ? TT_W + TT_XYZ : TT_W);
+        o.w[i] = p; p += (int64_t)TT_W * fin;
+        o.b[i] = p; p += TT_W;
+    }
+    o.views_w = p; p += (int64_t)128 * (TT_W + TT_DIR);
+    o.views_b = p; p += 128;
+    o.feat_w = p; p += (int64_t)TT_W * TT_W;
+    o.feat_b = p; p += TT_W;
+    o.alpha_w = p; p += TT_W;
+    o.alpha_b = p; p += 1;
+    o.rgb_w = p; p += 3 * 128;
+    o.rgb_b = p; p += 3;
+    o.total = p;
+    return o;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// raw2outputs backward (one wave per ray, S <= 256 samples staged in LDS)
+// ------------------------------------------------------------------------------------------------------------------
+// Forward (main.py:556-621): dists = [z_{i+1} - z_i, 1e10] * |d| ; a_i = 1 - exp(-relu(raw3_i + noise_i) dists_i) ;
+// T_i = prod_{j<i} t_j with t_j = 1 - a_j + 1e-10 ; w_i = a_i T_i ; rgb_map = sum w_i sigmoid(raw_i[:3]) (+ 1 - sum w_i when
+// white_bkgd).  With e_i = dL/dw_i = g . rgb_i (- sum g when white_bkgd) and g = dL/drgb_map:
+//   dL/da_k = T_k (e_k - U_k),  U_k = sum_{i>k} e_i a_i prod_{k<j<i} t_j   (suffix recurrence U_k = e_{k+1} a_{k+1} + t_{k+1} U_{k+1})
+// which is cumprod's backward without a division by t_k (a_k = 1 leaves t_k = 1e-10, where dividing loses the gradient).
+#define TT_RB_MAXS 256
+__global__ __launch_bounds__(256) void r2l_raw2outputs_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                  const float* __restrict__ rays_d,
+                                                                  const float* __restrict__ noise, int white,
+                                                                  const float* __restrict__ target, float* __restrict__ draw,
+                                                                  float* __restrict__ sqerr, int64_t R, int S, float gscale) {
+    __shared__ float s_a[4][TT_RB_MAXS], s_t[4][TT_RB_MAXS], s_da[4][TT_RB_MAXS], s_e[4][TT_RB_MAXS], s_T[4][TT_RB_MAXS];
+    __shared__ float s_rgb[4][TT_RB_MAXS][3];
+    __shared__ float s_g[4][3];
+    const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + wave;
+    const bool live = r < R;  // (no early return: the barriers below are block-wide)
+    const int64_t rc = live ? r : R - 1;
+    const float d0 = rays_d[rc * 3], d1 = rays_d[rc * 3 + 1], d2 = rays_d[rc * 3 + 2];
+    const float dn = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);
+    const float* rr = raw + rc * S * 4;
+    const float* zr = z + rc * S;
+    for (int i = lane; i < S && live; i += 64) {
+        const float dist = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
+        const float sig = noise ? rr[4 * i + 3] + noise[rc * S + i] : rr[4 * i + 3];
+        const float ex = expf(-fmaxf(sig, 0.f) * dist);
+        const float a = 1.0f - ex;
+        s_a[wave][i] = a;
+        s_t[wave][i] = (1.0f - a) + 1e-10f;
+        s_da[wave][i] = sig > 0.f ? dist * ex : 0.f;  // d a / d raw3 (relu'(0) = 0, as torch)
+#pragma unroll
+        for (int c = 0; c < 3; ++c) s_rgb[wave][i][c] = 1.0f / (1.0f + expf(-rr[4 * i + c]));
+    }
+    __syncthreads();
+    if (lane == 0 && live) {
+        float T = 1.0f, acc = 0.f, m[3] = {0.f, 0.f, 0.f};
+        for (int i = 0; i < S; ++i) {  // cumprod order of the reference
+            const float w = s_a[wave][i] * T;
+            s_T[wave][i] = T;
+            acc += w;
+#pragma unroll
+            for (int c = 0; c < 3; ++c) m[c] += w * s_rgb[wave][i][c];
+            T *= s_t[wave][i];
+        }
+        float g[3], se = 0.f, gsum = 0.f;
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float rgb = white ? m[c] + (1.0f - acc) : m[c];
+            const float diff = rgb - target[r * 3 + c];
+            se += diff * diff;
+            g[c] = gscale * diff;  // d img2mse / d rgb_map = 2 (rgb - target) / (3 R)
+            gsum += g[c];
+            s_g[wave][c] = g[c];
+        }
+        sqerr[r] = se;
+        float U = 0.f;
+        for (int k = S - 1; k >= 0; --k) {
+            const float e = g[0] * s_rgb[wave][k][0] + g[1] * s_rgb[wave][k][1] + g[2] * s_rgb[wave][k][2] -
+                            (white ? gsum : 0.f);
+            s_e[wave][k] = s_T[wave][k] * (e - U);  // dL/da_k
+            U = e * s_a[wave][k] + s_t[wave][k] * U;
+        }
+    }
+    __syncthreads();
+    if (!live) return;
+    const float g0 = s_g[wave][0], g1 = s_g[wave][1], g2 = s_g[wave][2];
+    for (int i = lane; i < S; i += 64) {
+        const float w = s_a[wave][i] * s_T[wave][i];
+        f32x4 o;
+        const float gg[3] = {g0, g1, g2};
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            const float sg = s_rgb[wave][i][c];
+            o[c] = w * gg[c] * (sg * (1.0f - sg));
+        }
+        o[3] = s_e[wave][i] * s_da[wave][i];
+        *reinterpret_cast<f32x4*>(draw + (r * S + i) * 4) = o;
+    }
+}
+
+extern "C" int r2l_raw2outputs_backward(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
+                                        const float* target, float* draw, float* sqerr, int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0 && S >= 1 && S <= TT_RB_MAXS, "r2l_raw2outputs_backward: need R >= 0 and 1 <= S <= 256");
+    if (R == 0) return 0;
+    R2L_REQUIRE(raw && z && rays_d && target && draw && sqerr, "r2l_raw2outputs_backward: a required pointer is NULL");
+    hipLaunchKernelGGL(r2l_raw2outputs_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw, z,
+                       rays_d, noise, white_bkgd, target, draw, sqerr, R, S, (float)(2.0 / (3.0 * (double)R)));
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// GEMM: C[M,N] = sum_k A[m,k] B[k,n] on v_mfma_f32_32x32x2_f32.  128 x 128 block tile, 4 waves of 64 x 64 (2 x 2 MFMA
+// tiles), K staged through LDS 16 at a time.  blockIdx.z = one K chunk of `kchunk` (the weight products); the epilogue gets
+// (row, col, value, chunk).  Loaders return the operand element (the caller keeps indices in range).
+// ------------------------------------------------------------------------------------------------------------------
+struct LdRowA {  // A[m,k] = p[m*ld + k]   (dX: the layer's output gradient, k along a row)
+    const float* p;
+    int ld;
+    static constexpr bool KFAST = true;
+    __device__ float operator()(int64_t m, int64_t k) const { return p[m * ld + k]; }
+};
+struct LdTransA {  // A[m,k] = p[k*ld + m]   (dW: G^T, the points are k)
+    const float* p;
+    int ld;
+    static constexpr bool KFAST = false;
+    __device__ float operator()(int64_t m, int64_t k) const { return p[k * ld + m]; }
+};
+struct LdWeightB {  // B[k,n] = W[k*ld + col0 + n]   (dX: row k = output feature of the layer, n = input feature)
+    const float* w;
+    int ld, col0;
+    __device__ float operator()(int64_t k, int64_t n) const { return w[k * ld + col0 + n]; }
+};
+// B[k = point, n] = the input row of a layer: [PE(xyz) (nx cols)] [stashed activation (w1 cols, row stride w1)] [PE(dir) (nd)]
+struct LdActB {
+    const float* act;
+    const float *rays_o, *rays_d, *viewdirs, *z;
+    int S, nx, w1, nd;
+    __device__ float operator()(int64_t p, int64_t n) const {
+        if (n < nx) {  // embed xyz, helpers:24-56: [x, sin(2^0 x), cos(2^0 x), ...]
+            const int64_t ray = p / S;
+            const int c = (int)n;
+            const int ax = c < 3 ? c : (c - 3) % 3;
+            const float x = rays_o[ray * 3 + ax] + rays_d[ray * 3 + ax] * z[p];  // as the forward: mul / add rounded separately
+            return tt_pe(x, c);
+        }
+        n -= nx;
+        if (n < w1) return act[p * w1 + n];
+        n -= w1;
+        const int64_t ray = p / S;
+        const int c = (int)n;
+        return tt_pe(viewdirs[ray * 3 + (c < 3 ? c : (c - 3) % 3)], c);
+    }
+    // column c of the encoding of one coordinate value x (c < 3: x itself; else frequency (c-3)/6, sin for (c-3)%6 < 3)
+    __device__ static float tt_pe(float x, int c) {
+        if (c < 3) return x;
+        const int f = (c - 3) / 6;
+        float sn, cs;
+        r2l_sincos(x * (float)(1 << f), sn, cs);
+        return (c - 3) % 6 < 3 ? sn : cs;
+    }
+};
+// dX epilogue: out[m*ld + n] = (v + r1a[4m] r1b[n]) * (mask[m*ld_mask + n] > 0)  (rank-1 term and mask optional)
+struct EpDX {
+    float* out;
+    int ld;
+    const float* mask;
+    int mask_ld;
+    const float* r1a;
+    const float* r1b;
+    int64_t M;
+    int N;
+    __device__ void operator()(int64_t m, int n, float v, int) const {
+        if (m >= M || n >= N) return;
+        if (r1a) v += r1a[m * 4] * r1b[n];
+        if (mask && !(mask[m * mask_ld + n] > 0.f)) v = 0.f;
+        out[m * ld + n] = v;
+    }
+};
+// dW epilogue: partial slab [chunk][M][N + 1] (column N = the bias partial, written by the kernel's row sums)
+struct EpSlab {
+    float* slab;
+    int64_t M;
+    int N;
+    __device__ void operator()(int64_t m, int n, float v, int z) const {
+        if (m >= M || n >= N) return;
+        slab[((int64_t)z * M + m) * (N + 1) + n] = v;
+    }
+};
+
+template <class LA, class LB, class EP>
+__global__ __launch_bounds__(256) void tt_gemm_kernel(const LA la, const LB lb, const EP ep, int64_t M, int N, int64_t K,
+                                                      int64_t kchunk, float* bias_slab) {
+    __shared__ float As[TT_BK][TT_BM + 1];
+    __shared__ float Bs[TT_BK][TT_BN + 1];
+    __shared__ float rs[2][TT_BM];
+    const int tid = threadIdx.x, lane = tid & 63, wave = tid >> 6, h = lane >> 5, l = lane & 31;
+    const int64_t m0 = (int64_t)blockIdx.y * TT_BM;
+    const int n0 = blockIdx.x * TT_BN;
+    const int64_t kb = (int64_t)blockIdx.z * kchunk, ke = kb + kchunk < K ? kb + kchunk : K;
+    const int wm = (wave >> 1) * 64, wn = (wave & 1) * 64;
+    // row sums of A over this chunk (dW: the bias gradient), only in the first column block, fixed order
+    const bool rowsum = bias_slab != nullptr && blockIdx.x == 0;
+    float rsum = 0.f;
+    f32x16 acc[2][2];
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r) acc[i][j][r] = 0.f;
+    for (int64_t k0 = kb; k0 < ke; k0 += TT_BK) {
+#pragma unroll
+        for (int r = 0; r < TT_BM * TT_BK / 256; ++r) {
+            const int e = tid + 256 * r;
+            const int mm = LA::KFAST ? e / TT_BK : e % TT_BM, kk = LA::KFAST ? e % TT_BK : e / TT_BM;
+            As[kk][mm] = (m0 + mm < M && k0 + kk < ke) ? la(m0 + mm, k0 + kk) : 0.f;
+        }
+#pragma unroll
+        for (int r = 0; r < TT_BN * TT_BK / 256; ++r) {
+            const int e = tid + 256 * r;
+            const int nn = e % TT_BN, kk = e / TT_BN;
+            Bs[kk][nn] = (n0 + nn < N && k0 + kk < ke) ? lb(k0 + kk, n0 + nn) : 0.f;
+        }
+        __syncthreads();
+        if (rowsum) {
+#pragma unroll
+            for (int kk = 0; kk < TT_BK / 2; ++kk) rsum += As[(tid >> 7) * (TT_BK / 2) + kk][tid & 127];
+        }
+#pragma unroll
+        for (int kk = 0; kk < TT_BK; kk += 2) {
+            const float a0 = As[kk + h][wm + l], a1 = As[kk + h][wm + 32 + l];
+            const float b0 = Bs[kk + h][wn + l], b1 = Bs[kk + h][wn + 32 + l];
+            acc[0][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b0, acc[0][0], 0, 0, 0);
+            acc[0][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a0, b1, acc[0][1], 0, 0, 0);
+            acc[1][0] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b0, acc[1][0], 0, 0, 0);
+            acc[1][1] = __builtin_amdgcn_mfma_f32_32x32x2f32(a1, b1, acc[1][1], 0, 0, 0);
+        }
+        __syncthreads();
+    }
+    // D layout of 32x32x2: column = lane & 31, row = 8 (r / 4) + 4 (lane / 32) + r % 4
+#pragma unroll
+    for (int i = 0; i < 2; ++i)
+#pragma unroll
+        for (int j = 0; j < 2; ++j)
+#pragma unroll
+            for (int r = 0; r < 16; ++r)
+                ep(m0 + wm + 32 * i + 8 * (r >> 2) + 4 * h + (r & 3), n0 + wn + 32 * j + l, acc[i][j][r], blockIdx.z);
+    if (rowsum) {
+        rs[tid >> 7][tid & 127] = rsum;
+        __syncthreads();
+        if (tid < TT_BM && m0 + tid < M) bias_slab[((int64_t)blockIdx.z * M + m0 + tid) * (N + 1) + N] = rs[0][tid] + rs[1][tid];
+    }
+}
+
+// grads[w_off + m*N + n] = sum_z slab[z][m][n] (n < N), grads[b_off + m] = sum_z slab[z][m][N]; z in increasing order
+__global__ void tt_slab_reduce_kernel(const float* __restrict__ slab, int Z, int64_t M, int N, float* __restrict__ grads,
+                                      int64_t w_off, int64_t b_off) {
+    const int64_t cols = N + 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * cols; i += (int64_t)gridDim.x * blockDim.x) {
+        float s = 0.f;
+        for (int zz = 0; zz < Z; ++zz) s += slab[(int64_t)zz * M * cols + i];
+        const int64_t m = i / cols;
+        const int n = (int)(i % cols);
+        if (n < N) grads[w_off + m * N + n] = s;
+        else grads[b_off + m] = s;
+    }
+}
+
+// G_views[p, j] = (sum_c drgb[p, c] W_rgb[c, j]) * (relu(v)[p, j] > 0)   (rgb_linear^T and the views layer's ReLU)
+__global__ void tt_rgb_head_dx_kernel(const float* __restrict__ draw, const float* __restrict__ rgb_w,
+                                      const float* __restrict__ vstash, float* __restrict__ gv, int64_t P) {
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < P * 128; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = i >> 7;
+        const int j = (int)(i & 127);
+        const float v = draw[p * 4] * rgb_w[j] + draw[p * 4 + 1] * rgb_w[128 + j] + draw[p * 4 + 2] * rgb_w[256 + j];
+        gv[i] = vstash[i] > 0.f ? v : 0.f;
+    }
+}
+
+template <class LA, class LB, class EP>
+static int tt_gemm(const LA& la, const LB& lb, const EP& ep, int64_t M, int N, int64_t K, int64_t kchunk, float* bias_slab,
+                   hipStream_t st) {
+    const int64_t nz = (K + kchunk - 1) / kchunk;
+    R2L_REQUIRE((M + TT_BM - 1) / TT_BM < 65536 && nz < 65536, "r2l_teacher_backward: too many points for one call");
+    const dim3 grid((unsigned)((N + TT_BN - 1) / TT_BN), (unsigned)((M + TT_BM - 1) / TT_BM), (unsigned)nz);
+    hipLaunchKernelGGL((tt_gemm_kernel<LA, LB, EP>), grid, dim3(256), 0, st, la, lb, ep, M, N, K, kchunk, bias_slab);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// dW (and db) of one layer: grads[w_off + m*N + n] = sum_p G[p, m] B[p, n], grads[b_off + m] = sum_p G[p, m]
+static int tt_weight_grad(const float* G, int ldg, int64_t M, const LdActB& b, int N, int64_t P, float* slab, float* grads,
+                          int64_t w_off, int64_t b_off, hipStream_t st) {
+    const int Z = (int)((P + TT_KCHUNK - 1) / TT_KCHUNK);
+    const EpSlab ep{slab, M, N};
+    if (int rc = tt_gemm(LdTransA{G, ldg}, b, ep, M, N, P, TT_KCHUNK, slab, st)) return rc;
+    const int64_t n = M * (N + 1);
+    hipLaunchKernelGGL(tt_slab_reduce_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slab, Z, M, N, grads, w_off,
+                       b_off);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// dX of one layer: out[P, N] = (G[P, Kout] W[Kout, col0 : col0 + N]) (+ rank-1) * relu'(mask)
+static int tt_dx(const float* G, int ldg, int Kout, const float* w, int ldw, int col0, int N, float* out, const float* mask,
+                 const float* r1a, const float* r1b, int64_t P, hipStream_t st) {
+    const EpDX ep{out, N, mask, N, r1a, r1b, P, N};
+    return tt_gemm(LdRowA{G, ldg}, LdWeightB{w, ldw, col0}, ep, P, N, Kout, Kout, nullptr, st);
+}
+
+static int64_t tt_slab_floats(int64_t P) { return ((P + TT_KCHUNK - 1) / TT_KCHUNK) * (int64_t)TT_W * (TT_W + TT_XYZ + 1); }
+
+extern "C" int64_t r2l_teacher_train_work_floats(int64_t P) {
+    if (P < 0) return -1;
+    return 2 * P * TT_W + P * 128 + tt_slab_floats(P);
+}
+
+extern "C" int r2l_teacher_backward(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                    const float* tparams, const float* stash, const float* draw, float* grads, float* work,
+                                    int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0 && S >= 0, "r2l_teacher_backward: negative R / S");
+    const TTOff off = tt_offsets();
+    const int64_t P = R * (int64_t)S;
+    if (P == 0) {  // no points: every gradient is zero
+        R2L_REQUIRE(grads, "r2l_teacher_backward: grads is NULL");
+        R2L_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * off.total, (hipStream_t)stream));
+        return 0;
+    }
+    R2L_REQUIRE(rays_o && rays_d && viewdirs && z && tparams && stash && draw && grads && work,
+                "r2l_teacher_backward: a required pointer is NULL");
+    const hipStream_t st = (hipStream_t)stream;
+    const float* W = tparams;
+    float* ga = work;
+    float* gb = ga + P * TT_W;
+    float* gv = gb + P * TT_W;
+    float* slab = gv + P * 128;
+    auto slot = [&](int l) { return stash + (int64_t)l * P * TT_W; };
+    const float* vst = slot(9);  // relu(views layer), [P,128]
+    auto act = [&](const float* a, int nx, int w1, int nd) { return LdActB{a, rays_o, rays_d, viewdirs, z, S, nx, w1, nd}; };
+    int rc;
+    // heads: rgb_linear (128 -> 3) and alpha_linear (256 -> 1) weight gradients; G of the views layer
+    if ((rc = tt_weight_grad(draw, 4, 3, act(vst, 0, 128, 0), 128, P, slab, grads, off.rgb_w, off.rgb_b, st))) return rc;
+    if ((rc = tt_weight_grad(draw + 3, 4, 1, act(slot(7), 0, TT_W, 0), TT_W, P, slab, grads, off.alpha_w, off.alpha_b, st)))
+        return rc;
+    hipLaunchKernelGGL(tt_rgb_head_dx_kernel, dim3((unsigned)((P * 128 + 255) / 256 < 65536 ? (P * 128 + 255) / 256 : 65536)),
+                       dim3(256), 0, st, draw, W + off.rgb_w, vst, gv, P);
+    R2L_CHECK(hipGetLastError());
+    // views layer: dW over [feature, PE(dir)]; dX to the feature (the direction encoding is a constant)
+    if ((rc = tt_weight_grad(gv, 128, 128, act(slot(8), 0, TT_W, TT_DIR), TT_W + TT_DIR, P, slab, grads, off.views_w,
+                             off.views_b, st)))
+        return rc;
+    if ((rc = tt_dx(gv, 128, 128, W + off.views_w, TT_W + TT_DIR, 0, TT_W, ga, nullptr, nullptr, nullptr, P, st))) return rc;
+    // feature_linear: dW over h7; dX into h7 plus the alpha head's d sigma (x) w_alpha, then relu'(h7)
+    if ((rc = tt_weight_grad(ga, TT_W, TT_W, act(slot(7), 0, TT_W, 0), TT_W, P, slab, grads, off.feat_w, off.feat_b, st)))
+        return rc;
+    if ((rc = tt_dx(ga, TT_W, TT_W, W + off.feat_w, TT_W, 0, TT_W, gb, slot(7), draw + 3, W + off.alpha_w, P, st))) return rc;
+    // layers 7 .. 1: G (pre-activation gradient of layer l) in `cur`; layer 5's input is [PE(xyz), h4]
+    float* cur = gb;
+    float* nxt = ga;
+    for (int l = 7; l >= 1; --l) {
+        const int nx = l == 5 ? TT_XYZ : 0;
+        const int fin = nx + TT_W;
+        if ((rc = tt_weight_grad(cur, TT_W, TT_W, act(slot(l - 1), nx, TT_W, 0), fin, P, slab, grads, off.w[l], off.b[l], st)))
+            return rc;
+        if ((rc = tt_dx(cur, TT_W, TT_W, W + off.w[l], fin, nx, TT_W, nxt, slot(l - 1), nullptr, nullptr, P, st))) return rc;
+        float* t = cur; cur = nxt; nxt = t;
+    }
+    // layer 0: dW over PE(xyz)
+    return tt_weight_grad(cur, TT_W, TT_W, act(nullptr, TT_XYZ, 0, 0), TT_XYZ, P, slab, grads, off.w[0], off.b[0], st);
+}

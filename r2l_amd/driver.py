@@ -490,7 +490,7 @@ def main(argv=None):
         # (--benchmark times render_func = the R2L student's forward, main.py:401-404,1124-1133)
         raise NotImplementedError("--model_name nerf: the accelerated path renders a pretrained teacher (--render_only, with or "
                                   "without --render_test / --test_pretrained) and uses it in utils/create_data.py; TRAINING "
-                                  "the teacher is out of scope (SURVEY.md §2)")
+                                  "the teacher runs through utils/train_nerf.py")
     rank, world, device = init_distributed()
     np.random.seed(0)
     # every rank must build the same student: torch's default generator is seeded per process otherwise (the reference had

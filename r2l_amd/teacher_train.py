@@ -1,0 +1,199 @@
+"""Training step of the NeRF teacher (step 1 of the pipeline: main.py --model_name nerf, main.py:1199-1406 in images mode).
+
+TeacherTrainer(coarse, fine) owns one flat fp32 buffer [coarse | fine] that both modules' parameters alias (the order of
+torch.optim.Adam(list(coarse.parameters()) + list(fine.parameters())), main.py:425-467), its gradient and the two Adam
+moments.  On ROCm tensors one step is, in libr2l_hip.so (include/r2l_hip.h, "NeRF teacher training"):
+  stratified z -> coarse forward with stash -> raw2outputs (weights) -> sample_pdf + sort (z_samples detached, main.py:728)
+  -> fine forward with stash -> raw2outputs backward with the img2mse seed (fine and coarse) -> both backward passes -> Adam.
+On CPU modules the same step is torch autograd over render.render_rays' CPU branch and torch.optim.Adam (plumbing only:
+it lets the host loop be tested without a GPU).
+"""
+import torch
+
+from . import _lib
+from . import render
+from .engine import _ptr, _stream
+from .metrics import img2mse, mse2psnr
+
+
+class TeacherTrainer:
+    def __init__(self, coarse, fine=None, N_samples=64, N_importance=128, perturb=1., white_bkgd=True, raw_noise_std=0.,
+                 betas=(0.9, 0.999), eps=1e-8):
+        self.nets = [coarse] + ([fine] if fine is not None and N_importance > 0 else [])
+        if N_importance > 0 and fine is None:
+            raise NotImplementedError("N_importance > 0 without a fine network: the reference re-uses network_fn; not supported")
+        self.N_samples, self.N_importance = N_samples, N_importance
+        self.perturb, self.white_bkgd, self.raw_noise_std = float(perturb), bool(white_bkgd), float(raw_noise_std)
+        self.betas, self.eps = tuple(betas), eps
+        self.params = [p for net in self.nets for p in net.parameters()]
+        self.step_count = 0
+        self.on_gpu = self.params[0].is_cuda
+        if not self.on_gpu:
+            self.opt = torch.optim.Adam(self.params, lr=0., betas=self.betas, eps=eps)
+            return
+        self.lib = _lib.load()
+        self.engines = [render.teacher_engine(net) for net in self.nets]
+        self.n_net = self.lib.r2l_teacher_param_count()
+        dev = self.params[0].device
+        n = self.n_net * len(self.nets)
+        self.flat = torch.empty(n, dtype=torch.float32, device=dev)
+        with torch.no_grad():
+            off = 0
+            for p in self.params:
+                v = self.flat[off:off + p.numel()].view(p.shape)
+                v.copy_(p.data)
+                p.data = v
+                off += p.numel()
+        for i, eng in enumerate(self.engines):  # each teacher engine packs from its slice of the one buffer
+            eng.flat = self.flat[i * self.n_net:(i + 1) * self.n_net]
+            eng.wstream = torch.zeros(self.lib.r2l_teacher_stream_floats(), dtype=torch.float32, device=dev)
+            eng._ver = None
+        self.grads = torch.zeros(n, dtype=torch.float32, device=dev)
+        self.exp_avg = torch.zeros_like(self.grads)
+        self.exp_avg_sq = torch.zeros_like(self.grads)
+        self.loss_out = torch.zeros(2, dtype=torch.float32, device=dev)
+        self._bufs = {}
+
+    # ---- device buffers, grown on demand ------------------------------------------------------------------------------
+    def _buf(self, name, n):
+        b = self._bufs.get(name)
+        if b is None or b.numel() < n:
+            b = torch.empty(n, dtype=torch.float32, device=self.flat.device)
+            self._bufs[name] = b
+        return b[:n]
+
+    def _noise(self, R, S):
+        if self.raw_noise_std <= 0.:
+            return None
+        return torch.randn(R, S, device=self.flat.device) * self.raw_noise_std
+
+    def _forward(self, i, rays_o, rays_d, viewdirs, z):
+        eng = self.engines[i]
+        eng.ensure_packed()
+        R, S = z.shape
+        raw = torch.empty(R, S, 4, dtype=torch.float32, device=z.device)
+        stash = self._buf("stash%d" % i, self.lib.r2l_teacher_stash_floats(R * S))
+        _lib.check(self.lib.r2l_teacher_mlp_train(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(eng.wstream),
+                                                  _ptr(eng.flat), _ptr(raw), _ptr(stash), R, S, _stream()),
+                   "r2l_teacher_mlp_train")
+        return raw, stash
+
+    def _backward(self, i, rays_o, rays_d, viewdirs, z, raw, stash, noise, target):
+        R, S = z.shape
+        draw = self._buf("draw", R * S * 4)
+        sqerr = self._buf("sqerr%d" % i, R)
+        _lib.check(self.lib.r2l_raw2outputs_backward(_ptr(raw), _ptr(z), _ptr(rays_d), _ptr(noise), int(self.white_bkgd),
+                                                     _ptr(target), _ptr(draw), _ptr(sqerr), R, S, _stream()),
+                   "r2l_raw2outputs_backward")
+        work = self._buf("work", self.lib.r2l_teacher_train_work_floats(R * S))
+        g = self.grads[i * self.n_net:(i + 1) * self.n_net]
+        _lib.check(self.lib.r2l_teacher_backward(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(self.engines[i].flat),
+                                                 _ptr(stash), _ptr(draw), _ptr(g), _ptr(work), R, S, _stream()),
+                   "r2l_teacher_backward")
+        out = self._buf("mse%d" % i, 2)
+        _lib.check(self.lib.r2l_loss_finish(_ptr(sqerr), R, 1. / (3 * R), _ptr(out), _stream()), "r2l_loss_finish")
+        return out
+
+    def forward_backward(self, rays_o, rays_d, viewdirs, near, far, target, t_rand=None, u=None):
+        """Gradients of img2mse(rgb) + img2mse(rgb0) into self.grads; returns loss_out = [loss, psnr of the last net]."""
+        if not self.on_gpu:
+            raise RuntimeError("forward_backward is the device path; CPU modules train through step()")
+        f32 = dict(dtype=torch.float32, device=self.flat.device)
+        rays_o, rays_d, viewdirs = [t.to(**f32).contiguous() for t in (rays_o, rays_d, viewdirs)]
+        target = target.to(**f32).contiguous()
+        R = rays_o.shape[0]
+        near = torch.as_tensor(near, **f32).expand(R, 1).contiguous()
+        far = torch.as_tensor(far, **f32).expand(R, 1).contiguous()
+        z = render._coarse_z(near, far, self.N_samples, False, self.perturb, False, t_rand)
+        noise_c = self._noise(R, self.N_samples)
+        raw_c, stash_c = self._forward(0, rays_o, rays_d, viewdirs, z)
+        outs = []
+        self.last_z = [z]  # the sample depths of this step (coarse, fine): what a test needs to restate it
+        if self.N_importance > 0:
+            weights = render.raw2outputs(raw_c, z, rays_d, noise=noise_c, white_bkgd=self.white_bkgd)[3]
+            _, z_all, _ = render.sample_pdf_sort(z, weights, self.N_importance, det=(self.perturb == 0.), u=u)
+            self.last_z.append(z_all)
+            noise_f = self._noise(R, z_all.shape[1])
+            raw_f, stash_f = self._forward(1, rays_o, rays_d, viewdirs, z_all)
+            outs.append(self._backward(1, rays_o, rays_d, viewdirs, z_all, raw_f, stash_f, noise_f, target))
+        outs.append(self._backward(0, rays_o, rays_d, viewdirs, z, raw_c, stash_c, noise_c, target))
+        # loss = img2mse(rgb) + img2mse(rgb0); psnr = mse2psnr(img2mse(rgb)) (main.py:1353-1378)
+        self.loss_out[0] = sum(o[0] for o in outs)
+        self.loss_out[1] = outs[0][1]
+        return self.loss_out
+
+    def adam(self, lr):
+        self.step_count += 1
+        _lib.check(self.lib.r2l_adam_step(_ptr(self.flat), _ptr(self.grads), _ptr(self.exp_avg), _ptr(self.exp_avg_sq),
+                                          self.flat.numel(), float(lr), self.betas[0], self.betas[1], self.eps,
+                                          self.step_count, 1.0, _stream()), "r2l_adam_step")
+        for eng in self.engines:
+            eng._ver = None  # the kernel wrote the weights in place: re-pack before the next launch
+
+    def step(self, rays_o, rays_d, viewdirs, near, far, target, lr, t_rand=None, u=None):
+        """One optimisation step; returns (loss, psnr) as floats."""
+        if not self.on_gpu:
+            return self._cpu_step(rays_o, rays_d, viewdirs, near, far, target, lr, t_rand, u)
+        out = self.forward_backward(rays_o, rays_d, viewdirs, near, far, target, t_rand, u)
+        self.adam(lr)
+        loss, psnr = out.tolist()
+        return loss, psnr
+
+    def _cpu_step(self, rays_o, rays_d, viewdirs, near, far, target, lr, t_rand, u):
+        R = rays_o.shape[0]
+        ones = torch.ones(R, 1)
+        batch = torch.cat([rays_o, rays_d, near * ones, far * ones, viewdirs], -1).float()
+        qfn = lambda inputs, vd, fn: render.run_network(inputs, vd, fn, embed_fn=render.get_embedder(10)[0],
+                                                        embeddirs_fn=render.get_embedder(4)[0])
+        fine = self.nets[1] if len(self.nets) > 1 else None
+        ret = render.render_rays(batch, self.nets[0], qfn, self.N_samples, perturb=self.perturb,
+                                 N_importance=self.N_importance, network_fine=fine, white_bkgd=self.white_bkgd,
+                                 raw_noise_std=self.raw_noise_std, t_rand=t_rand, u=u)
+        img_loss = img2mse(ret["rgb_map"], target)
+        loss = img_loss + (img2mse(ret["rgb0"], target) if "rgb0" in ret else 0.)
+        for g in self.opt.param_groups:
+            g["lr"] = lr
+        self.opt.zero_grad()
+        loss.backward()
+        self.opt.step()
+        self.step_count += 1
+        return loss.item(), mse2psnr(img_loss.detach()).item()
+
+    # ---- torch.optim.Adam-compatible state (checkpoint 'optimizer_state_dict', main.py:1528-1529) -------------------------
+    def optimizer_state_dict(self, lr):
+        if not self.on_gpu:
+            sd = self.opt.state_dict()
+            sd["param_groups"][0]["lr"] = lr
+            return sd
+        state, off = {}, 0
+        for i, p in enumerate(self.params):
+            n = p.numel()
+            state[i] = {"step": torch.tensor(float(self.step_count)),
+                        "exp_avg": self.exp_avg[off:off + n].view(p.shape).clone(),
+                        "exp_avg_sq": self.exp_avg_sq[off:off + n].view(p.shape).clone()}
+            off += n
+        group = {"lr": lr, "betas": self.betas, "eps": self.eps, "weight_decay": 0, "amsgrad": False, "maximize": False,
+                 "foreach": None, "capturable": False, "differentiable": False, "fused": None,
+                 "decoupled_weight_decay": False, "params": list(range(len(self.params)))}
+        return {"state": state if self.step_count > 0 else {}, "param_groups": [group]}
+
+    def load_optimizer_state_dict(self, sd):
+        if len(sd["param_groups"][0]["params"]) != len(self.params):
+            raise ValueError("optimizer state has %d parameters, the teacher %d" % (len(sd["param_groups"][0]["params"]),
+                                                                                 len(self.params)))
+        steps = [0]
+        for st in sd["state"].values():
+            steps.append(int(float(st["step"])))
+        if not self.on_gpu:
+            self.opt.load_state_dict(sd)
+            self.step_count = max(steps)
+            return
+        off = 0
+        for i, p in enumerate(self.params):
+            n = p.numel()
+            st = sd["state"].get(i)
+            if st is not None:
+                self.exp_avg[off:off + n].copy_(st["exp_avg"].reshape(-1))
+                self.exp_avg_sq[off:off + n].copy_(st["exp_avg_sq"].reshape(-1))
+            off += n
+        self.step_count = max(steps)

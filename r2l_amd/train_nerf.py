@@ -1,0 +1,146 @@
+"""Step 1 of the pipeline: train the NeRF teacher, the `python main.py --model_name nerf --config configs/lego.txt` command of
+the reference (main.py:1199-1513, images mode with no_batching), here `python utils/train_nerf.py --config configs/lego.txt`.
+
+Each iteration draws one training image (np.random.choice(i_train)), centre-crops it for precrop_iters, takes N_rand of its
+pixels without replacement (rand_pixel, helpers:385-392) and runs one TeacherTrainer step (r2l_amd/teacher_train.py) at the
+learning rate of lr_schedule.  The numpy and torch generators are re-seeded from (R2L_SEED, iteration) at every iteration, so a
+run is reproducible and a --resume from a checkpoint of iteration k continues exactly as the uninterrupted run would.
+Checkpoints are the reference's layout (checkpoint.save_ckpt, model_name='nerf'): utils/create_data.py --teacher_ckpt and
+main.py --model_name nerf --render_only read them unchanged.
+"""
+import os
+import time
+
+import numpy as np
+import torch
+
+from . import data as D
+from .checkpoint import load_ckpt, save_ckpt
+from .driver import apply_arithmetic, create_nerf_teacher, init_distributed, render_path
+from .logger import Logger
+from .options import parse_args, validate_accelerated
+from .render import get_rays
+from .teacher_train import TeacherTrainer
+from .train_step import lr_schedule
+
+
+def validate_teacher_training(args):
+    """Loud refusals for what this path does not implement."""
+    validate_accelerated(args)
+    if int(os.environ.get("WORLD_SIZE", "1")) > 1:
+        raise NotImplementedError("teacher training runs on one GPU (WORLD_SIZE > 1 is not supported)")
+    if not args.no_batching:
+        raise NotImplementedError("teacher training implements images mode with --no_batching (use_batching is out of scope)")
+    if args.r2l_precision not in ("auto", "fp32_mfma"):
+        raise NotImplementedError("teacher training is exact fp32 (--r2l_precision auto | fp32_mfma), got %s" % args.r2l_precision)
+    if not args.use_viewdirs or args.N_importance < 0:
+        raise NotImplementedError("teacher training implements NeRF(D=8, W=256, 63+27, skips=[4], use_viewdirs)")
+
+
+def precrop_coords(H, W, frac):
+    """[2dH, 2dW, 2] pixel coordinates of the centre crop (main.py:1273-1284)."""
+    dH, dW = int(H // 2 * frac), int(W // 2 * frac)
+    return torch.stack(torch.meshgrid(torch.linspace(H // 2 - dH, H // 2 + dH - 1, 2 * dH),
+                                      torch.linspace(W // 2 - dW, W // 2 + dW - 1, 2 * dW), indexing="ij"), -1)
+
+
+def full_coords(H, W):
+    return torch.stack(torch.meshgrid(torch.linspace(0, H - 1, H), torch.linspace(0, W - 1, W), indexing="ij"), -1)
+
+
+def select_rand_pixels(coords, N_rand):
+    """get_selected_coords(coords, N_rand, 'rand_pixel') (helpers:385-392): N_rand distinct pixels."""
+    coords = coords.long()
+    H, W = coords.shape[:2]
+    rand_ix = np.random.choice(H * W, size=[N_rand], replace=False)
+    return coords.view(-1, 2)[rand_ix]
+
+
+def sample_batch(i, args, images, poses, i_train, H, W, focal):
+    """(rays_o, rays_d, viewdirs, target) of iteration i (main.py:1260-1302)."""
+    img_i = np.random.choice(i_train)
+    target = images[img_i]
+    pose = poses[img_i, :3, :4]
+    rays_o, rays_d = get_rays(H, W, focal, torch.as_tensor(pose, dtype=torch.float32))
+    coords = precrop_coords(H, W, args.precrop_frac) if i < args.precrop_iters else full_coords(H, W)
+    sel = select_rand_pixels(coords, args.N_rand)
+    rays_o, rays_d = rays_o[sel[:, 0], sel[:, 1]], rays_d[sel[:, 0], sel[:, 1]]
+    target = torch.as_tensor(target)[sel[:, 0], sel[:, 1]]
+    viewdirs = rays_d / torch.norm(rays_d, dim=-1, keepdim=True)
+    return rays_o, rays_d, viewdirs, target
+
+
+def _seed(i):
+    s = (int(os.environ.get("R2L_SEED", "0")) * 1000003 + i) % (2**32)
+    np.random.seed(s)
+    torch.manual_seed(s)
+
+
+def main(argv=None):
+    args = parse_args(argv)
+    args.model_name = "nerf"
+    validate_teacher_training(args)
+    rank, world, device = init_distributed()
+    _seed(0)
+    logger = Logger(args, rank)
+    images, poses, _, hwf, i_split = D.load_blender_data(args.datadir, args.half_res, args.testskip)
+    logger.info("Loaded blender", tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
+    i_train, _, i_test = i_split
+    near, far = 2., 6.
+    images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:]) if args.white_bkgd else images[..., :3]
+    H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
+
+    kwargs_test = create_nerf_teacher(args, device, logger, near, far)
+    coarse, fine = kwargs_test["network_fn"], kwargs_test["network_fine"]
+    for net in (coarse, fine):
+        if net is not None:
+            net.train()
+            for p in net.parameters():
+                p.requires_grad = device.type != "cuda"  # the device path computes its gradients by hand
+    r2l_config = apply_arithmetic(args, device, logger, teachers=(coarse, fine))
+    trainer = TeacherTrainer(coarse, fine, N_samples=args.N_samples, N_importance=args.N_importance, perturb=args.perturb,
+                             white_bkgd=args.white_bkgd, raw_noise_std=args.raw_noise_std)
+    start, best_psnr, best_psnr_step = 0, 0., 0
+    if args.pretrained_ckpt and args.resume:
+        ckpt = load_ckpt(args.pretrained_ckpt, map_location=device)
+        start = int(ckpt["global_step"])
+        best_psnr, best_psnr_step = float(ckpt.get("best_psnr", 0.)), int(ckpt.get("best_psnr_step", 0))
+        trainer.load_optimizer_state_dict(ckpt["optimizer_state_dict"])
+        logger.info("Resume from %s at iteration %d" % (args.pretrained_ckpt, start))
+    teacher = dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kwargs_test, render_factor=0)
+    test_poses, test_images = poses[i_test], images[i_test]
+
+    def save(path, i, lr):
+        return save_ckpt(path, i, coarse, trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, model_name="nerf",
+                         model_fine=fine, r2l_config=r2l_config)
+
+    history, lr, t0 = [], args.lrate, time.time()
+    for i in range(start + 1, args.N_iters + 1):
+        _seed(i)
+        rays_o, rays_d, viewdirs, target = sample_batch(i, args, images, poses, i_train, H, W, focal)
+        if i == start + 1 and i < args.precrop_iters:
+            dH, dW = int(H // 2 * args.precrop_frac), int(W // 2 * args.precrop_frac)
+            logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (2 * dH, 2 * dW, args.precrop_iters))
+        lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
+        loss, psnr = trainer.step(rays_o.to(device), rays_d.to(device), viewdirs.to(device), near, far, target.to(device), lr)
+        history.append((loss, psnr))
+        if i % args.i_print == 0:
+            logger.info("[TRAIN] Iter %d Loss %.4f PSNR %.4f LR %.8f Time %.1fs" % (i, loss, psnr, lr, time.time() - t0))
+        if i % args.i_testset == 0 and len(i_test):
+            savedir = os.path.join(logger.gen_img_path, "testset_%s_iter%d" % (logger.ExpID, i))
+            _, misc = render_path(test_poses, coarse, None, device, logger, gt_imgs=test_images, savedir=savedir,
+                                  teacher=teacher)
+            for net in (coarse, fine):
+                if net is not None:
+                    net.train()
+            if misc["test_psnr_v2"].item() > best_psnr:
+                best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
+                save(os.path.join(logger.weights_path, "ckpt_best.tar"), i, lr)
+            logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f BestPSNRv2 %.4f (Iter %d)" %
+                        (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), best_psnr, best_psnr_step))
+        if i % args.i_weights == 0:
+            name = "ckpt_%d.tar" % i if args.save_intermediate_models else "ckpt.tar"
+            path = save(os.path.join(logger.weights_path, name), i, lr)
+            logger.info('Iter %d Save checkpoint: "%s".' % (i, path))
+    return {"trainer": trainer, "logger": logger, "history": history, "coarse": coarse, "fine": fine,
+            "r2l_config": r2l_config}
