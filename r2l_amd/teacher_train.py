@@ -15,6 +15,8 @@ from . import render
 from .engine import _ptr, _stream
 from .metrics import img2mse, mse2psnr
 
+MAX_SAMPLES = 256  # r2l_raw2outputs_backward stages one ray's samples in LDS
+
 
 class TeacherTrainer:
     def __init__(self, coarse, fine=None, N_samples=64, N_importance=128, perturb=1., white_bkgd=True, raw_noise_std=0.,
@@ -31,6 +33,10 @@ class TeacherTrainer:
         if not self.on_gpu:
             self.opt = torch.optim.Adam(self.params, lr=0., betas=self.betas, eps=eps)
             return
+        S = N_samples + (N_importance if len(self.nets) > 1 else 0)
+        if S > MAX_SAMPLES:  # refused here, before a step runs the forward passes the backward would then refuse
+            raise ValueError("teacher training on the device takes at most %d samples per ray (N_samples + N_importance), "
+                             "got %d" % (MAX_SAMPLES, S))
         self.lib = _lib.load()
         self.engines = [render.teacher_engine(net) for net in self.nets]
         self.n_net = self.lib.r2l_teacher_param_count()

@@ -20,7 +20,7 @@ from .driver import apply_arithmetic, create_nerf_teacher, init_distributed, ren
 from .logger import Logger
 from .options import parse_args, validate_accelerated
 from .render import get_rays
-from .teacher_train import TeacherTrainer
+from .teacher_train import MAX_SAMPLES, TeacherTrainer
 from .train_step import lr_schedule
 
 
@@ -35,6 +35,10 @@ def validate_teacher_training(args):
         raise NotImplementedError("teacher training is exact fp32 (--r2l_precision auto | fp32_mfma), got %s" % args.r2l_precision)
     if not args.use_viewdirs or args.N_importance < 0:
         raise NotImplementedError("teacher training implements NeRF(D=8, W=256, 63+27, skips=[4], use_viewdirs)")
+    S = args.N_samples + max(args.N_importance, 0)
+    if S > MAX_SAMPLES:
+        raise NotImplementedError("teacher training takes at most %d samples per ray (N_samples + N_importance), got %d"
+                                  % (MAX_SAMPLES, S))
 
 
 def precrop_coords(H, W, frac):

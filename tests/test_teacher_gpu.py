@@ -7,6 +7,7 @@ import pytest
 import torch
 
 from oracle import r2l_oracle as O
+from tests.teacher_util import scene_rays, trained_like_pair
 
 pytestmark = pytest.mark.gpu
 
@@ -275,31 +276,6 @@ def test_render_frame_chunks():
 # Teacher parity OFF the init distribution: a coarse / fine pair fitted to an analytic scene
 # (tests/teacher_util.py) — sigma pre-activations -10^2 .. 10^3, hidden activations of a few 10^2, like a trained NeRF.
 # ---------------------------------------------------------------------------------------------------------------------
-_TRAINED = {}
-
-
-def trained_like_pair():
-    if not _TRAINED:
-        from tests.teacher_util import fit_teacher, teacher_stats
-        for name, seed in (("coarse", 21), ("fine", 22)):
-            _TRAINED[name] = fit_teacher(seed, steps=800, n=4096, device="cuda")
-        for name, sd in _TRAINED.items():
-            hmax, smin, smax = teacher_stats(sd)
-            print("trained-like %s: max |hidden| %.0f, sigma pre-activation %.0f .. %.0f" % (name, hmax, smin, smax))
-            assert hmax > 50 and smax > 200 and smin < -20  # the fit really left the init distribution
-    return _TRAINED["coarse"], _TRAINED["fine"]
-
-
-def scene_rays(R, seed, H=181, W=181, focal=250.):
-    """R rays of one camera on the r = 4 sphere looking at the analytic scene, as render() packs them (create_data.py:97-176)."""
-    from r2l_amd.render import get_rays
-    c2w = T(O.pose_spherical(35., -25., 4.)[:3, :4])
-    ro, rd = get_rays(H, W, focal, c2w)
-    ro, rd = ro.reshape(-1, 3)[:R], rd.reshape(-1, 3)[:R]
-    vd = rd / rd.norm(dim=-1, keepdim=True)
-    return torch.cat([ro, rd, 2. * torch.ones_like(rd[:, :1]), 6. * torch.ones_like(rd[:, :1]), vd], -1).float()
-
-
 def test_teacher_mlp_trained_like_vs_oracle(mlp_path):
     """r2l_teacher*_mlp raw on trained-like weights: sigma reaches 10^3, so the bar is relative to the value (fp32 itself
     resolves 6e-5 at 10^3); the colour logits keep the absolute bar of the init-distribution test."""

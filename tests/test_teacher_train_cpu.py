@@ -134,6 +134,8 @@ def test_cli_checkpoint_layout_and_resume_cpu(tmp_path, monkeypatch):
     ([], {"WORLD_SIZE": "2"}, "one GPU"),
     (["--r2l_precision", "fp16x2"], {}, "fp32"),
     (["--dataset_type", "llff"], {}, "blender"),
+    (["--N_samples", "64", "--N_importance", "193"], {}, "at most 256 samples"),
+    (["--N_samples", "257", "--N_importance", "0"], {}, "at most 256 samples"),
 ])
 def test_loud_refusals(extra, env, match, monkeypatch):
     from r2l_amd import train_nerf
@@ -153,3 +155,32 @@ def test_main_still_refuses_nerf_training():
     from r2l_amd import driver
     with pytest.raises(NotImplementedError, match="TRAINING"):
         driver.main(["--model_name", "nerf", "--config", os.path.join(ROOT, "configs", "lego.txt")])
+
+
+@pytest.mark.parametrize("R,S", [(1, 1), (1, 15), (3, 5), (2, 43)])
+def test_backward_yardstick_vs_fp64_autograd(R, S):
+    """tests/teacher_util.teacher_backward_from_stash, fed the stash of an fp64 forward, is fp64 autograd of run_network
+    contracted with draw (1e-12 of each entry's magnitude), and its magnitudes bound the gradients.  This pins the yardstick of
+    tests/test_teacher_backward_gpu.py without a GPU."""
+    from tests.teacher_util import layer_outputs, teacher_backward_from_stash
+    sd = O.make_teacher_state_dicts(7, 1, alpha_bias=0.5)[0]
+    g = torch.Generator().manual_seed(R * 100 + S)
+    o = torch.randn(R, 3, generator=g) * .5
+    d = torch.randn(R, 3, generator=g)
+    vd = d / d.norm(dim=-1, keepdim=True)
+    z = torch.sort(torch.rand(R, S, generator=g) * 4 + 2, -1)[0]
+    draw = torch.randn(R, S, 4, generator=g, dtype=torch.float64)
+    pts = (o[:, None, :] + d[:, None, :] * z[:, :, None]).double()  # the fp32 points, as the kernels form them
+    sd64 = {k: v.double().requires_grad_(True) for k, v in sd.items()}
+    raw = O.run_network(sd64, pts, vd.double())
+    (raw * draw).sum().backward()
+    with torch.no_grad():
+        emb = torch.cat([O.nerf_embed(pts.reshape(-1, 3), 10), O.nerf_embed(vd.double()[:, None].expand(R, S, 3).reshape(-1, 3), 4)], -1)
+        stash = torch.cat([t.reshape(-1) for t in layer_outputs({k: v.detach() for k, v in sd64.items()}, emb)])
+    grads, mags = teacher_backward_from_stash(sd, o, d, vd, z, stash, draw)
+    assert list(grads) == list(sd) == list(mags)
+    for k, want in ((k, v.grad) for k, v in sd64.items()):
+        err = (grads[k] - want).abs()
+        assert (err <= 1e-12 * mags[k] + 1e-300).all(), (k, (err / mags[k].clamp_min(1e-300)).max().item())
+        assert (want.abs() <= mags[k] * (1 + 1e-12)).all(), k
+        assert mags[k].max().item() > 0, k

@@ -9,6 +9,7 @@ import pytest
 import torch
 
 from oracle import r2l_oracle as O
+from tests.teacher_util import layer_outputs, scene_rays, stash_slots, trained_like_pair
 
 pytestmark = pytest.mark.gpu
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
@@ -28,20 +29,6 @@ def rays(R, seed):
     vd = d / d.norm(dim=-1, keepdim=True)
     tgt = torch.rand(R, 3, generator=g)
     return o, d, vd, tgt
-
-
-def layer_outputs(sd, emb):
-    """The stashed quantities restated from the oracle's weights: relu(h0..h7), feature, relu(views)."""
-    pts, views = emb[:, :63], emb[:, 63:]
-    h, outs = pts, []
-    for i in range(8):
-        h = torch.relu(h @ sd["pts_linears.%d.weight" % i].T + sd["pts_linears.%d.bias" % i])
-        outs.append(h)
-        if i == 4:
-            h = torch.cat([pts, h], -1)
-    feat = h @ sd["feature_linear.weight"].T + sd["feature_linear.bias"]
-    v = torch.relu(torch.cat([feat, views], -1) @ sd["views_linears.0.weight"].T + sd["views_linears.0.bias"])
-    return outs + [feat, v]
 
 
 def test_forward_with_stash():
@@ -118,11 +105,14 @@ def draws(R, NS=64, NI=128, seed=0):
     return torch.rand(R, NS, generator=g), torch.rand(R, NI, generator=g)
 
 
-def oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, dtype=torch.float64, NS=64, NI=128, white=True, z_dev=None):
+def oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, dtype=torch.float64, NS=64, NI=128, white=True, z_dev=None,
+                      noise=None, z_tol=1e-4, info=None):
     """Autograd of img2mse(rgb) + img2mse(rgb0) built from oracle pieces, z_samples detached (main.py:728).
     z_dev: the (coarse, fine) sample depths the device used.  The oracle's own agree with them to an ulp or so, but the
     encoding's 2^9 frequency turns one ulp of z into ~1e-4 of phase, which the layer-0 weight gradient shows; the yardstick
-    restates the step at the device's depths instead (checked against the oracle's below)."""
+    restates the step at the device's depths instead (checked against the oracle's below, the fine ones to z_tol; None: not
+    checked).  noise: the (coarse [R,NS], fine [R,NS+NI]) draws the device added to sigma (raw_noise_std > 0).  info: a dict
+    that receives the largest distance of the oracle's fine depths from the device's ("z_fine")."""
     sds = [{k: v.to(dtype).clone().requires_grad_(True) for k, v in sd.items()} for sd in (csd, fsd)]
     R = o.shape[0]
     t = torch.linspace(0., 1., steps=NS)
@@ -135,48 +125,167 @@ def oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, dtype=torch.float64, N
     def net(sd, zz):
         pts = o[:, None, :] + d[:, None, :] * zz[:, :, None]
         return O.run_network(sd, pts.to(dtype), vd.to(dtype))
+    nc, nf = (None, None) if noise is None else noise
     raw0 = net(sds[0], z)
-    rgb0, _, _, w0, _ = O.raw2outputs(raw0, z.to(dtype), d.to(dtype), None, white)
+    rgb0, _, _, w0, _ = O.raw2outputs(raw0, z.to(dtype), d.to(dtype), None if nc is None else nc.to(dtype), white)
     with torch.no_grad():  # the samples are placed by the fp32 weights, as on the device
-        w32 = O.raw2outputs(raw0.float(), z, d, None, white)[3]
+        w32 = O.raw2outputs(raw0.float(), z, d, None if nc is None else nc.float(), white)[3]
         zs = O.sample_pdf(.5 * (z[..., 1:] + z[..., :-1]), w32[..., 1:-1], NI, u=u)
         z_all = torch.sort(torch.cat([z, zs], -1), -1)[0]
         if z_dev is not None:
-            assert (z_all - z_dev[1]).abs().max().item() <= 1e-4
+            dz = (z_all - z_dev[1]).abs().max().item()
+            if info is not None:
+                info["z_fine"] = dz
+            assert z_tol is None or dz <= z_tol, dz
             z_all = z_dev[1]
     raw = net(sds[1], z_all)
-    rgb = O.raw2outputs(raw, z_all.to(dtype), d.to(dtype), None, white)[0]
+    rgb = O.raw2outputs(raw, z_all.to(dtype), d.to(dtype), None if nf is None else nf.to(dtype), white)[0]
     loss = torch.mean((rgb - tgt.to(dtype))**2) + torch.mean((rgb0 - tgt.to(dtype))**2)
     loss.backward()
     return [{k: v.grad for k, v in sd.items()} for sd in sds], loss.item()
 
 
-@pytest.mark.parametrize("R", [64, 1024])
-def test_full_step_gradients_vs_fp64(R):
+# (id, case): R rays, NS + NI samples, background, raw_noise_std, weights.  The ids "64" and "1024" are the original cases.
+# R = 37 gives P = 2368 coarse / 7104 fine points (partial chunks, tiles and k-steps), R = 1 a single ray; 64 + 192 = 256 samples
+# is the most the raw2outputs backward takes.
+FULL_STEP_CASES = [
+    ("64", dict(R=64, original=True)), ("1024", dict(R=1024, original=True)), ("37", dict(R=37)), ("1", dict(R=1)),
+    ("64-black", dict(R=64, white=False)), ("64-noise", dict(R=64, noise_std=1.)),
+    ("64-32+96", dict(R=64, NS=32, NI=96)), ("64-64+192", dict(R=64, NS=64, NI=192)),
+    ("64-trained", dict(R=64, trained=True)),
+]
+C_BWD = 3e-6  # per-entry bar of the network backward against its stash yardstick (tests/test_teacher_backward_gpu.py)
+C_R2O = 2e-5  # per-entry bar of the raw2outputs backward, relative to the ray's largest |draw| (same module)
+
+
+def scene_batch(R, seed):
+    """R rays through the dense middle of the trained-like scene (pixels of the central 61 x 61 of the 181 x 181 camera)."""
+    rb = scene_rays(181 * 181, 0).view(181, 181, -1)[60:121, 60:121].reshape(-1, 11)
+    rb = rb[torch.randperm(rb.shape[0], generator=torch.Generator().manual_seed(seed))[:R]]
+    tgt = torch.rand(R, 3, generator=torch.Generator().manual_seed(seed + 1))
+    return rb[:, 0:3].contiguous(), rb[:, 3:6].contiguous(), rb[:, 8:11].contiguous(), tgt
+
+
+def draw_fp64(raw, z, d, noise, white, tgt):
+    """fp64 autograd of img2mse(raw2outputs(raw)) with respect to raw (one net's term of the step's loss)."""
+    raw = raw.detach().cpu().double().requires_grad_(True)
+    rgb = O.raw2outputs(raw, z.cpu().double(), d.double(), None if noise is None else noise.double(), white)[0]
+    torch.mean((rgb - tgt.double())**2).backward()
+    return raw.grad
+
+
+@pytest.mark.parametrize("case", [c for _, c in FULL_STEP_CASES], ids=[i for i, _ in FULL_STEP_CASES])
+def test_full_step_gradients_vs_fp64(case, monkeypatch):
+    """The whole step (forward with stash, sample_pdf, raw2outputs backward, network backward of both nets) against two fp64
+    yardsticks.
+    (a) The stash yardstick, at each net's own raw and stash as the step made them: with the step's own draw, every entry within
+    3e-6 of its magnitude (the per-layer bar); with draw from fp64 autograd of raw2outputs + img2mse, every tensor within 1e-5
+    norm-relative, except the alpha head: its weight and bias are sums of dL/dsigma, which cancel within each ray, so they are held
+    to what the raw2outputs backward's own bar allows, 2e-5 of each ray's largest |draw| per point.  Measured on one MI355X:
+    no entry past the first bar; 6.4e-6 on the second (alpha head: up to 1.5e-3 norm-relative, inside its bound).
+    (b) A fresh fp64 forward (oracle_step_grads): the original cases at 5e-4 norm-relative, as before.  The added cases at 5e-4
+    plus the share of what comes before the network backward, the distance of (a) with the step's own draw from (b): the fp32
+    forward flips ReLU masks of activations within rounding of zero (measured up to 8.6e-4 on layer 0 at 32 + 96 samples, where
+    one coarse mask flips; the count is printed) and the raw2outputs backward's rounding of the cancelling dL/dsigma (up to 1.5e-3
+    on the alpha head, black background); (a) shows that the network backward adds nothing to them."""
     from r2l_amd.teacher_train import TeacherTrainer
-    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
-    tr = TeacherTrainer(make_teacher(csd), make_teacher(fsd), perturb=1., white_bkgd=True)
-    o, d, vd, tgt = rays(R, 3)
-    t_rand, u = draws(R)
-    out = tr.forward_backward(o.cuda(), d.cuda(), vd.cuda(), 2., 6., tgt.cuda(), t_rand=t_rand.cuda(), u=u.cuda())
-    want, loss = oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, z_dev=[z.cpu() for z in tr.last_z])
+    from tests.teacher_util import teacher_backward_from_stash
+    R, NS, NI = case["R"], case.get("NS", 64), case.get("NI", 128)
+    white, std, trained = case.get("white", True), case.get("noise_std", 0.), case.get("trained", False)
+    csd, fsd = trained_like_pair() if trained else O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    noise = None
+    if std > 0:  # the step's noise fixed by the test and handed to the yardstick
+        g = torch.Generator().manual_seed(77)
+        noise = (torch.randn(R, NS, generator=g) * std, torch.randn(R, NS + NI, generator=g) * std)
+        fixed = {NS: noise[0].cuda(), NS + NI: noise[1].cuda()}
+        monkeypatch.setattr(TeacherTrainer, "_noise", lambda self, R_, S_: fixed[S_])
+    tr = TeacherTrainer(make_teacher(csd), make_teacher(fsd), N_samples=NS, N_importance=NI, perturb=1., white_bkgd=white,
+                        raw_noise_std=std)
+    seen = {}
+    backward = tr._backward
+
+    def keep(i, rays_o, rays_d, viewdirs, z, raw, stash, nz, target):  # each net's raw, stash and draw as the step used them
+        out = backward(i, rays_o, rays_d, viewdirs, z, raw, stash, nz, target)
+        seen[i] = (raw, stash, tr._bufs["draw"][:z.numel() * 4].clone().view(*z.shape, 4))
+        return out
+    tr._backward = keep
+    o, d, vd, tgt = scene_batch(R, 5) if trained else rays(R, 3)
+    t_rand, u = draws(R, NS, NI)
+    og, dg, vdg = o.cuda(), d.cuda(), vd.cuda()
+    out = tr.forward_backward(og, dg, vdg, 2., 6., tgt.cuda(), t_rand=t_rand.cuda(), u=u.cuda())
+    z_dev = [z.cpu() for z in tr.last_z]
+    info = {}
+    # fine depths: 1e-4, as before; where the pdf is flat at 1e-5 an fp32 difference of the weights moves a fine sample far
+    # (measured 3.2e-3 with noise, 3.9e-2 on the trained-like pair)
+    z_tol = 0.16 if trained else (1.3e-2 if std > 0 else 1e-4)
+    kw = dict(NS=NS, NI=NI, white=white, z_dev=z_dev, noise=noise, z_tol=z_tol, info=info)
+    want, loss = oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, **kw)
     assert abs(out[0].item() - loss) < 1e-5 * max(loss, 1.)
+    if trained:
+        with torch.no_grad():
+            sig = max(O.run_network(sd, o[:, None, :] + d[:, None, :] * z[:, :, None], vd)[..., 3].max().item()
+                      for sd, z in zip((csd, fsd), z_dev))
+        assert sig > 200, sig  # the rays do cross the dense parts
+    ref32, _ = oracle_step_grads(csd, fsd, o, d, vd, tgt, t_rand, u, dtype=torch.float32, **kw)
     g = tr.grads.cpu()
-    off = 0
-    worst = []
-    for net in want:
-        for k, w in net.items():
+    off, rows, fails, flips = 0, [], [], []
+    for i, sd in enumerate((csd, fsd)):
+        raw, stash, draw_dev = seen[i]
+        zi = tr.last_z[i]
+        d64 = draw_fp64(raw, zi, d, None if noise is None else noise[i], white, tgt)
+        with torch.no_grad():  # ReLU masks of the device's forward that differ from an fp64 forward's
+            P = zi.numel()
+            pts = (og[:, None, :] + dg[:, None, :] * zi[:, :, None]).reshape(P, 3).double()
+            emb = torch.cat([O.nerf_embed(pts, 10), O.nerf_embed(vdg.double()[:, None].expand(*zi.shape, 3).reshape(P, 3), 4)], -1)
+            acts = layer_outputs({k: v.double().cuda() for k, v in sd.items()}, emb)
+            flips.append(sum(int(((st > 0) != (a > 0)).sum()) for l, (st, a) in enumerate(zip(stash_slots(stash, P), acts))
+                             if l != 8))
+        ys, _ = teacher_backward_from_stash(sd, og, dg, vdg, zi, stash, d64.cuda(), device="cuda")
+        ys_dev, mags = teacher_backward_from_stash(sd, og, dg, vdg, zi, stash, draw_dev, device="cuda")
+        raymax = d64.abs().amax(dim=(1, 2), keepdim=True).expand(d64.shape).contiguous()
+        _, mr = teacher_backward_from_stash(sd, og, dg, vdg, zi, stash, raymax.cuda(), device="cuda")  # sum_p raymax |A|
+        for k, w in want[i].items():
             got = g[off:off + w.numel()].view(w.shape)
             off += w.numel()
-            e = nrel(got, w)
+            e_ys = nrel(got, ys[k].cpu())
+            viol = int(((got.double() - ys_dev[k].cpu()).abs() > C_BWD * mags[k].cpu() + 1e-12 * mags[k].max().item()).sum())
+            fwd = nrel(ys_dev[k].cpu(), w)
+            e, e32 = nrel(got, w), nrel(ref32[i][k], w)
             cos = torch.nn.functional.cosine_similarity(got.double().reshape(1, -1), w.reshape(1, -1)).item()
-            worst.append((e, cos, k))
-            # Bar 5e-4, not 1e-4: the step's fp32 forward already differs from fp64 by ~1e-7 per activation, ReLU masks of
-            # activations that close to zero flip, and the 2^9-frequency encoding columns amplify both in the layer-0
-            # gradients.  torch's own fp32 autograd of this step (R = 64) lands at 1.6e-3 on pts_linears.0.weight of the fine
-            # net (4.6e-4 on layer 1); the device step measured 2.3e-4 there.
-            assert e <= 5e-4 and cos >= 0.99999, (k, e, cos)
-    print("worst norm-relative error", max(worst))
+            rows.append((k, i, e_ys, viol, fwd, e, e32))
+            if cos < 0.99999:
+                fails.append(("cosine", i, k, cos))
+            if viol:
+                fails.append(("stash yardstick, own draw", i, k, viol))
+            if k.startswith("alpha_linear"):
+                over = (got.double() - ys[k].cpu()).abs() > C_BWD * mags[k].cpu() + C_R2O * mr[k].cpu()
+                if over.any() and e_ys > 1e-5:
+                    fails.append(("stash yardstick, alpha head", i, k, e_ys))
+            elif e_ys > 1e-5:
+                fails.append(("stash yardstick", i, k, e_ys))
+            bar = 5e-4 if case.get("original") else 5e-4 + fwd
+            if e > bar:
+                fails.append(("fresh fp64", i, k, e, bar))
+    print("full step %s: z_fine %.2g; flipped ReLU masks (coarse, fine) %s; worst: vs stash yardstick %.3g (alpha head %.3g), "
+          "upstream share %.3g, vs fresh fp64 %.3g, torch fp32 %.3g"
+          % (str(case), info.get("z_fine", 0), flips, max(r[2] for r in rows if not r[0].startswith("alpha")),
+             max(r[2] for r in rows if r[0].startswith("alpha")), max(r[4] for r in rows), max(r[5] for r in rows),
+             max(r[6] for r in rows)))
+    for r in sorted(rows, key=lambda r: -r[5])[:4]:
+        print("   %-22s net %d: vs stash %.3g (entries past the bar: %d), upstream share %.3g, vs fresh %.3g, torch fp32 %.3g" % r)
+    assert not fails, fails
+
+
+def test_more_than_256_samples_refused_before_any_work():
+    """N_samples + N_importance > 256 (N_samples > 256 without a fine net) is refused when the trainer is built, not by the
+    raw2outputs backward after two forward passes and sample_pdf."""
+    from r2l_amd.teacher_train import TeacherTrainer
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    with pytest.raises(ValueError, match="at most 256 samples"):
+        TeacherTrainer(make_teacher(csd), make_teacher(fsd), N_samples=64, N_importance=193)
+    with pytest.raises(ValueError, match="at most 256 samples"):
+        TeacherTrainer(make_teacher(csd), None, N_samples=257, N_importance=0)
+    TeacherTrainer(make_teacher(csd), make_teacher(fsd), N_samples=64, N_importance=192)  # 256, the maximum: accepted
 
 
 def test_three_adam_steps_vs_torch():
