@@ -8,7 +8,7 @@
 //                             fp32 MFMA, operands streamed straight from HBM with coalesced 16-byte loads.
 //   3. r2l_dw_head_kernel   : dW_head = G_head^T PE(rays) with the 1008-d positional encoding recomputed on the fly.
 //   4. r2l_dw_tail_kernel   : tail weight/bias gradients (3x256) by plain reduction.
-#include "r2l_common.h"
+#include "r2l_dispatch.h"
 #include "r2l_f2.h"
 #include "r2l_dw.h"
 #include "r2l_hip.h"
@@ -1167,14 +1167,12 @@ extern "C" int64_t r2l_stash_slot_floats(int64_t N) { return R2L_TRIO_SLOT(R2L_P
 // cooperative fp16 chains (small launches of the default trio), else 0.
 extern "C" int r2l_chain_segments_ok_cfg(int64_t N, int n_block, const r2l_config* cfg) {
     R2L_CFG_QUERY(cfg);
-    return (N > 0 && r2l_chain_variant(N) == R2L_VARIANT_MAIN && r2l_use_fwd3() && r2l_use_trio16() && r2l_use_coopf(N, n_block)) ? 1 : 0;
+    return r2l_plan(cfg, N, n_block, true, false).chain_segments_ok ? 1 : 0;
 }
 // Device word that the fp16 dX chain raises when a step needs the bf16x3 fallback (range guard, or the forward fell back):
 // 0 after a clean step.  A host that runs steps with R2L_BWD_NOFALLBACK hands it to r2l_adam_step_guarded.
 extern "C" const unsigned* r2l_backward_status_word(const float* wstream_bwd, int n_block) {
-    const float* w3 = wstream_bwd + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block);
-    const float* w2 = w3 + r2l_bwd3_stream_floats(n_block);
-    return reinterpret_cast<const unsigned*>(w2 + r2l_bwd2_status_offset(n_block));
+    return r2l_bwd_streams(wstream_bwd, n_block).status;
 }
 
 extern "C" const unsigned* r2l_backward_status_words(const float* wstream_bwd, int n_block) {
@@ -1207,14 +1205,6 @@ extern "C" int r2l_backward_part(const float* rays_o, const float* rays_d, const
                                  grad_scale, dpre, gx, gt, sqerr_partial, grads, dw_slab, N, stream_, parts, layer_lo, layer_hi,
                                  nullptr);
 }
-// largest step whose head / tail gradients run beside the body's (R2L_DW_OVERLAP_MAX_RAYS: tuning knob, tools/run_ab.sh)
-static int64_t r2l_dw_overlap_max() {
-    static const int64_t v = [] {
-        const char* e = getenv("R2L_DW_OVERLAP_MAX_RAYS");
-        return e ? (int64_t)atoll(e) : (int64_t)R2L_COOPF_MAX_RAYS;
-    }();
-    return v;
-}
 extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                                      const float* emb, const float* rgb, const float* target, const float* drgb,
                                      const float* save_x, const float* save_t,
@@ -1240,28 +1230,11 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
         return (int)hipErrorInvalidValue;
     }
     hipStream_t stream = (hipStream_t)stream_;
-    static int n_cu_cached = 0;  // one device type per process
-    if (n_cu_cached == 0) {
-        int dev = 0, v = 0;
-        if (hipGetDevice(&dev) == hipSuccess &&
-            hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0)
-            n_cu_cached = v;
-        else
-            n_cu_cached = 256;
-    }
-    // Data-parallel hosts overlap the gradient all-reduce with the weight-gradient stages (r2l_backward_part).  Those kernels
-    // are persistent workgroups that take every register of their CU, so a collective launched beside them would wait for
-    // a whole stage to finish: R2L_RESERVE_CUS=n (set by the host when world_size > 1; r2l_amd/train_step.py uses 8) keeps n
-    // CUs out of the weight-gradient launches for the RCCL kernels.  Default 0.
-    int reserve = 0;
-    if (g_r2l_cfg.reserve_cus) reserve = g_r2l_cfg.reserve_cus;  // (-1: none)
-    else if (const char* e = getenv("R2L_RESERVE_CUS")) reserve = atoi(e);
-    if (reserve < 0 || reserve > n_cu_cached / 2) reserve = 0;
-    const int n_cu = n_cu_cached - reserve;
-    // 1. dX chain
-    const int variant = r2l_chain_variant(N);
-    // the bf16x3 trio (r2l_fwd3 wrote the stash): chunked stash layout, see r2l_common.h
-    const bool split = r2l_stash_chunked(N, emb != nullptr);
+    // what runs: the same plan the forward of this step resolved (r2l_dispatch.h)
+    const R2LPlan plan = r2l_plan(cfg, N, n_block, true, emb != nullptr);
+    const R2LDwGrids grid = r2l_dw_grids(plan, layer_hi - layer_lo);
+    // the one-wave-per-tile trios (their forward wrote the stash): private stash layout, see r2l_dispatch.h R2L_STASH_*
+    const bool split = plan.stash != R2L_STASH_ROWMAJOR;
     // MSE mode of the trio: the dX chain runs on gscale * g, gscale = 2^(8 - e) for grad_scale = m * 2^e (m in [0.5, 1)): the
     // seed gscale * dL/dpre is then <= 64 |rgb - target|, which puts the chain's values into fp16's range for the fp16
     // gradient kernels; powers of two commute with fp32 rounding, so the scaled chain is bit-identical after unscaling
@@ -1271,29 +1244,27 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
         (void)frexpf(grad_scale, &e);
         gscale = ldexpf(1.0f, 8 - e);
     }
-    // the default trio of one-wave-per-tile steps: fp16 chains + fp16 weight-gradient GEMMs on fp16 stage pieces (the forward
-    // of such a step wrote that stash: r2l_forward_rays decides by the same rule)
-    const bool trio16 = split && r2l_use_trio16();
-    const float* w3 = wstream_bwd + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block);
-    const float* w2 = w3 + r2l_bwd3_stream_floats(n_block);
+    // the default trio of one-wave-per-tile steps: fp16 chains + fp16 weight-gradient GEMMs on fp16 stage pieces
+    const bool trio16 = plan.stash == R2L_STASH_FP16;
+    const R2LStreams w = r2l_bwd_streams(wstream_bwd, n_block);
     // raised by r2l_bwd2_kernel when this step has to run on the bf16x3 kernels (range guard / the forward fell back)
-    unsigned* bwd_status = reinterpret_cast<unsigned*>(const_cast<float*>(w2) + r2l_bwd2_status_offset(n_block));
+    unsigned* bwd_status = w.status;
     // generic mode (dL/drgb from the caller, no known scale): {gscale, 1 / gscale} are chosen on the device from max |drgb| and
     // live in words 4, 5 of the status area; every kernel of the step reads them there
     // (round 4: MSE mode as well — the step's scale is chosen on the device from the previous step's largest chain value,
     // r2l_bwd_prepare_kernel; the host-side gscale below remains the bf16x3-only trio's)
     const float* scale_dev = trio16 ? reinterpret_cast<const float*>(bwd_status + B2S_GSCALE) : nullptr;
     if (!(parts & R2L_BWD_CHAIN)) {
-    } else if (variant == R2L_VARIANT_COOP16) {
-        const int rc = r2l_coop16_backward(rgb, target, drgb, save_x, save_t, wstream_bwd + r2l_bwd32_stream_floats(n_block),
-                                           params, n_block, grad_scale, dpre, gx, gt, sqerr_partial, N, stream);
+    } else if (plan.chain == R2L_CHAIN_COOP16) {
+        const int rc = r2l_coop16_backward(rgb, target, drgb, save_x, save_t, w.w16, params, n_block, grad_scale, dpre, gx, gt,
+                                           sqerr_partial, N, stream);
         if (rc) return rc;
     } else if (split) {
         // one-wave-per-tile dX chain.  Default trio (MSE mode: scaled chain, values in fp16's range up to the guard): two-way fp16
         // splits, 3 fp16 products per fp32 product (r2l_bwd2.hip), stashing fp16 stage pieces for r2l_dw16.hip, with the
         // bf16x3 chain behind it as fallback (returns at once unless the status word behind the bwd2 stream was raised: range
         // guard, or the forward already fell back and left an fp32 stash); otherwise the bf16x3 chain (r2l_bwd3.hip)
-        if (chain_seg && !(trio16 && r2l_use_coopf(N, n_block) && no_fallback)) {
+        if (chain_seg && !(plan.chain_segments_ok && no_fallback)) {
             r2l_set_error_msg("r2l_backward_part: chain segments need the cooperative fp16 chains (r2l_chain_segments_ok_cfg) and "
                               "R2L_BWD_NOFALLBACK");
             return (int)hipErrorInvalidValue;
@@ -1310,19 +1281,23 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
                     R2L_CHECK(hipGetLastError());
                 }
             }
-            const int rc2 = r2l_bwd2_backward(rgb, target, drgb, save_x, save_t, w2, params, n_block, grad_scale, dpre, gx, gt,
-                                              sqerr_partial, N, stream, gscale, bwd_status, scale_dev,
-                                              chain_seg ? layer_hi / 2 - 1 : -1, chain_seg ? layer_lo / 2 : 0);
+            // small launches: the cooperative chain (r2l_coopf_bwd.hip), same stream / stash / status word; only it is cut into segments
+            const int rc2 = plan.tiling == R2L_TILING_COOPF
+                                ? r2l_coopf_backward(rgb, target, drgb, save_x, save_t, w.w2, params, n_block, grad_scale, dpre, gx, gt,
+                                                     sqerr_partial, N, stream, gscale, bwd_status, scale_dev, plan,
+                                                     chain_seg ? layer_hi / 2 - 1 : -1, chain_seg ? layer_lo / 2 : 0)
+                                : r2l_bwd2_backward(rgb, target, drgb, save_x, save_t, w.w2, params, n_block, grad_scale, dpre, gx, gt,
+                                                    sqerr_partial, N, stream, gscale, bwd_status, scale_dev, plan.stash_mid);
             if (rc2) return rc2;
             if (!no_fallback) {
                 // the fallback's stream is packed in front of it, and only when it will run
                 // (... and an fp16 forward stash is expanded for the bf16x3 kernels: a chain-only trip, r2l_bwd3.hip)
-                const int rp = r2l_bwd3_pack(params, n_block, const_cast<float*>(w3), stream, bwd_status, save_x, save_t, N);
+                const int rp = r2l_bwd3_pack(params, n_block, w.w3, stream, bwd_status, save_x, save_t, N);
                 if (rp) return rp;
             }
         }
         if (!(trio16 && no_fallback)) {
-            const int rc = r2l_bwd3_backward(rgb, target, drgb, save_x, save_t, w3, params, n_block, grad_scale, dpre, gx, gt,
+            const int rc = r2l_bwd3_backward(rgb, target, drgb, save_x, save_t, w.w3, params, n_block, grad_scale, dpre, gx, gt,
                                              sqerr_partial, N, stream, gscale, trio16 ? bwd_status : nullptr, scale_dev);
             if (rc) return rc;
         }
@@ -1362,11 +1337,9 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
     {
         static thread_local hipStream_t side[16] = {nullptr};
         static thread_local hipEvent_t ev_fork[16], ev_join[16];
-        static const bool overlap_off = r2l_env_on("R2L_NO_DW_OVERLAP");
-        const int64_t overlap_max = r2l_dw_overlap_max();
         int dev = 0;
-        if (!overlap_off && (parts & R2L_BWD_BODY) && (parts & R2L_BWD_HEAD) && layer_hi > layer_lo && dw_slab != nullptr &&
-            N <= overlap_max && hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
+        if (plan.dw_overlap && (parts & R2L_BWD_BODY) && (parts & R2L_BWD_HEAD) && layer_hi > layer_lo && dw_slab != nullptr &&
+            hipGetDevice(&dev) == hipSuccess && dev >= 0 && dev < 16) {
             if (side[dev] == nullptr) {
                 hipStream_t st = nullptr;
                 R2L_CHECK(hipStreamCreateWithFlags(&st, hipStreamNonBlocking));
@@ -1388,27 +1361,7 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
         a.layer0 = layer_lo; a.n_layers = layer_hi - layer_lo;
         a.units_per_layer = (N + DW_CHUNK - 1) / DW_CHUNK;
         const int64_t total = a.units_per_layer * a.n_layers;
-        int64_t wgs = n_cu < DW_MAX_WGS ? n_cu : DW_MAX_WGS;
-        // small steps: two workgroups per layer, none across a layer boundary (one slab flush each, half the reduce): measured
-        // at 4096 rays 97 + 16 us against 111 + 22 us for 251 workgroups; at 12 288 rays the full grid wins again (229 + 22
-        // against 242 + 16)
-        // (that is the fp16 trio's kernel, which is bound by the slab traffic at this size; the fp32-MFMA / bf16x3 kernels are bound by
-        // their MFMAs — 32 units on 172 workgroups against 22 on 251 — and keep the full grid: round 6, profiles/r06_graded_step_ab.txt E)
-        if (trio16 && N <= 6144 && 2 * (int64_t)a.n_layers <= wgs) wgs = 2 * (int64_t)a.n_layers;
-        // above that, up to the largest step whose head / tail gradients run beside this kernel: 11/16 of the CUs.  On the full grid the
-        // head kernel (VALU-bound, 4 workgroups per ray slice) queues behind the persistent workgroups and the overlap is one in name
-        // only (12 288 rays: 1.251 ms with 251 workgroups = 1.285 with the overlap off; 1.231 with 176, 1.239 with 144: round 6,
-        // profiles/r06_small_step_dw_grid.txt); the kernel is HBM-bound, fewer workgroups cost it little
-        if (trio16 && N > 6144 && N <= r2l_dw_overlap_max() && wgs > n_cu * 11 / 16) wgs = n_cu * 11 / 16;
-        // the MFMA-bound kernels with the head / tail gradients beside them (small steps): an eighth of the CUs stays free for those,
-        // or they queue behind the persistent grid (4096 rays, fp32 family: 1.358 ms with 172 workgroups, 1.367 with 251, 1.317 with 224)
-        // (decided by the step size alone, not by whether THIS call overlaps: the staged form — body buckets in calls of their own —
-        // must cut the same work list as the one-call form, tests: staged with one bucket == one call, bit for bit)
-        if (!trio16 && N <= r2l_dw_overlap_max() && wgs > n_cu - n_cu / 8) wgs = n_cu - n_cu / 8;
-        if (const char* e = getenv("R2L_DW_WGS")) {  // tuning knob (tools/small_prof.sh)
-            const int64_t v = atoll(e);
-            if (v >= a.n_layers && v <= wgs) wgs = v;
-        }
+        int64_t wgs = grid.body_wgs;
         if (wgs > total) wgs = total;
         a.units_per_wg = (total + wgs - 1) / wgs;
         wgs = (total + a.units_per_wg - 1) / a.units_per_wg;
@@ -1424,7 +1377,7 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
         // and the bf16x3 kernel behind it does the work
         if (trio16) {
             // (exact mode: the chains of this step stashed the mid halves too — the same config / environment as the forward)
-            a.mid_off = r2l_dw_exact() ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
+            a.mid_off = plan.stash_mid ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
             a.act_scale = save_x + R2L_STASH_FMT_WORD(n_block, R2L_PAD_ROWS(N)) + 1;  // the scale the forward stashed x, relu(t) at
             const int rc = r2l_dw16_launch(a, wgs, bwd_status, stream);
             a.mid_off = 0u;
@@ -1432,10 +1385,10 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
             if (rc) return rc;
             a.run_if = bwd_status;
             if (!no_fallback) hipLaunchKernelGGL(r2l_dw_body3c_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a);
-        } else if (split) {
+        } else if (plan.dw_body == R2L_DWBODY_BODY3C) {
             hipLaunchKernelGGL(r2l_dw_body3c_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a);
         }
-        else if (r2l_use_fwd3()) hipLaunchKernelGGL(r2l_dw_body3_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a);
+        else if (plan.dw_body == R2L_DWBODY_BODY3) hipLaunchKernelGGL(r2l_dw_body3_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a);
         else hipLaunchKernelGGL(r2l_dw_body_kernel, dim3((unsigned)wgs), dim3(256), 0, stream, a);
         R2L_CHECK(hipGetLastError());
         if (a.slab != nullptr) {
@@ -1448,17 +1401,7 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
     if (parts & R2L_BWD_HEAD) {
         R2LDwHeadArgs a{};
         a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab; a.emb = emb; a.gh = gx; a.grads = grads; a.N = N;
-        int64_t slices = n_cu / 4;
-        if (slices > DW_HEAD_SLAB_MAX / (R2L_W * 1024)) slices = DW_HEAD_SLAB_MAX / (R2L_W * 1024);  // (what the slab region holds)
-        // small launches: >= 256 rays per slice (each slice costs a 1 MB partial).  (Round 5 tried 128 and 64 rays per slice for the
-        // 4096-ray step — 32 / 64 slices instead of 16: 0.789 / 0.823 ms per step against 0.789, same box: what the wider grid gains
-        // the 1 MB-per-slice reduce gives back; profiles/r05_small_step_ab.txt)
-        if (slices > (N + 255) / 256) slices = (N + 255) / 256;
-        if (slices < 1) slices = 1;
-        int64_t per = (N + slices - 1) / slices;
-        per = (per + 1) & ~(int64_t)1;  // even: a k-step pairs rays 2s, 2s+1
-        if (per < 2) per = 2;
-        slices = (N + per - 1) / per;
+        const int64_t slices = grid.head_slices, per = grid.head_rays;
         a.rays_per_wg = per;
         // per-slice partials go to the head's region of dw_slab, else to the (by now dead) gt scratch when
         // it is large enough, else fp32 atomics
@@ -1468,20 +1411,20 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
         // (never `gt` beside the body kernels of an overlapped call: they are still reading it on the other stream)
         else a.slab = (slices > 1 && slab_floats <= gt_floats && !overlap) ? gt : nullptr;
         const dim3 hg((unsigned)(slices * 4)), hb(256);
-        if (trio16 && emb == nullptr) {
+        if (plan.dw_head16) {
             // default trio: the same GEMM on the fp16 matrix pipe (r2l_dw_head16.hip); the fp32 kernel behind it runs only when
             // the dX chain raised its status word (range guard / bf16x3 fallback step)
             a.gscale = gscale;
             a.unscale = 1.0f / gscale;
             a.scale_dev = scale_dev;
             a.run_unless = bwd_status;
-            a.exact = r2l_dw_exact();
+            a.exact = plan.stash_mid;
             const int rc = r2l_dw_head16_launch(a, slices, hstream);
             if (rc) return rc;
             a.run_unless = nullptr;
             a.run_if = bwd_status;
         }
-        if (trio16 && emb == nullptr && no_fallback) {
+        if (plan.dw_head16 && no_fallback) {
         } else if (emb != nullptr) hipLaunchKernelGGL((r2l_dw_head_kernel<true, false>), hg, hb, 0, hstream, a);
         else if (t_rand != nullptr) hipLaunchKernelGGL((r2l_dw_head_kernel<false, true>), hg, hb, 0, hstream, a);
         else hipLaunchKernelGGL((r2l_dw_head_kernel<false, false>), hg, hb, 0, hstream, a);
@@ -1494,11 +1437,7 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
     }
     // 4. tail gradients
     if (parts & R2L_BWD_TAIL) {
-        int64_t wgs = 2 * n_cu;
-        if (wgs > DW_TAIL_SLAB / (4 * R2L_W)) wgs = DW_TAIL_SLAB / (4 * R2L_W);  // (what the slab region holds: no switch of paths,
-        int64_t per = (N + wgs - 1) / wgs;                                      //  i.e. of summation order, on a larger device)
-        if (per < 1) per = 1;
-        wgs = (N + per - 1) / per;
+        const int64_t wgs = grid.tail_wgs, per = grid.tail_rays;
         // partials in the tail's region of dw_slab; summed in workgroup order
         float* part = (dw_slab != nullptr && wgs * (4 * R2L_W) <= DW_TAIL_SLAB) ? dw_slab + DW_TAIL_SLAB_BASE : nullptr;
         // (chunked stash: slot n of save_x holds y = x_n + x_0)

@@ -285,14 +285,7 @@ int r2l_bwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t
 int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
                       const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                      const float* scale_dev, int b_start, int b_end) {
-    if (r2l_use_coopf(N, n_block))  // small launches: the cooperative chain (r2l_coopf_bwd.hip), same stream / stash / status word
-        return r2l_coopf_backward(rgb, target, drgb, save_x, save_t, wstream_bwd2, params, n_block, grad_scale, dpre, gx, gt,
-                                  sqerr_partial, N, stream, gscale, status, scale_dev, b_start, b_end);
-    if (b_start >= 0 && !(b_start == n_block - 1 && b_end == 0)) {
-        r2l_set_error_msg("r2l_bwd2_backward: only the cooperative chains can be cut into block ranges");
-        return (int)hipErrorInvalidValue;
-    }
+                      const float* scale_dev, bool stash_mid) {
     B2Args a{};
     a.status = status;
     a.scale_dev = scale_dev;
@@ -301,7 +294,7 @@ int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, 
     a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t;
     a.stream = reinterpret_cast<const unsigned char*>(wstream_bwd2); a.params = params; a.n_block = n_block;
     a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt; a.sqerr_partial = sqerr_partial; a.N = N;
-    a.stash_mid = r2l_dw_exact() ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
+    a.stash_mid = stash_mid ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     if (a.stash_mid != 0u) hipLaunchKernelGGL(r2l_bwd2_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(r2l_bwd2_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);

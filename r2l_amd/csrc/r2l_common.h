@@ -485,9 +485,7 @@ int r2l_bwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t
 int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
                       const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                      const float* scale_dev = nullptr, int b_start = -1, int b_end = 0);
-// forward launches (with or without the training stash) big enough for the one-wave-per-tile kernels take the bf16x3
-// kernel (R2L_NO_FWD3=1: fp32 MFMA)
+                      const float* scale_dev, bool stash_mid);  // stash_mid: the step stashes the mid halves too (exact dW)
 // pose mode: the camera of ray rc and its pixel index.  One pose by value (c2w), or — one launch over several frames
 // (r2l_forward_poses: no tail round and no launch gap per frame) — a device table c2w_dev[K][12], frame = rc / (H * W)
 struct R2LPoseRay { float c[12]; int64_t pix; };
@@ -505,31 +503,6 @@ __device__ __forceinline__ R2LPoseRay r2l_pose_of(const float (&c2w)[12], const 
     }
     return r;
 }
-// the multi-pose launch in progress on this thread (set by r2l_forward_poses_cfg around the single-pose dispatch)
-extern thread_local const float* g_r2l_c2w_dev;  // r2l_error.hip
-
-// Explicit dispatch (include/r2l_hip.h r2l_config): the *_cfg entry points install the caller's config for the duration of
-// the call (R2LCfgScope, thread-local), and every decision below looks at it first; an AUTO (0) field falls through to the
-// R2L_* environment switch it replaces, read per call (~100 ns) so tests can flip it.
-extern thread_local r2l_config g_r2l_cfg;  // r2l_error.hip
-struct R2LCfgScope {
-    r2l_config saved;
-    explicit R2LCfgScope(const r2l_config* c) : saved(g_r2l_cfg) { if (c) g_r2l_cfg = *c; }
-    ~R2LCfgScope() { g_r2l_cfg = saved; }
-};
-// What is wrong with a caller's r2l_config, or nullptr.  Every *_cfg entry point checks before it does anything else:
-// launch entry points fail with hipErrorInvalidValue (R2L_CFG_ENTER), the host-side queries return -1 (R2L_CFG_QUERY).
-static inline const char* r2l_cfg_check(const r2l_config* c) {
-    if (c == nullptr) return nullptr;
-    if (c->precision < 0 || c->precision > R2L_PRECISION_FP32_MFMA) return "r2l_config.precision: not an R2L_PRECISION_* value";
-    if (c->tiling < 0 || c->tiling > R2L_TILING_COOPF) return "r2l_config.tiling: not an R2L_TILING_* value";
-    if (c->tiling == R2L_TILING_COOP_RETIRED) return "r2l_config.tiling: 2 (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5 — R2L_TILING_COOP16 serves those launches";
-    if (c->coop_tiles < 0 || c->coop_tiles > 3) return "r2l_config.coop_tiles: 0 (auto), 1, 2 or 3 (mixed)";
-    if (c->reserve_cus < -1) return "r2l_config.reserve_cus: -1 (none), 0 (auto) or a CU count";
-    if (c->dw_mode < 0 || c->dw_mode > R2L_DW_EXACT) return "r2l_config.dw_mode: not an R2L_DW_* value";
-    if (c->reserved[0] || c->reserved[1] || c->reserved[2]) return "r2l_config.reserved: must be 0";
-    return nullptr;
-}
 // argument checks of the C ABI: a bad pointer / size is an error code here, not a memory fault on the device
 #define R2L_REQUIRE(cond, msg)                            \
     do {                                                  \
@@ -539,37 +512,11 @@ static inline const char* r2l_cfg_check(const r2l_config* c) {
         }                                                 \
     } while (0)
 #define R2L_MAX_BLOCKS 1024  // body blocks of a student net: the kernels address a weight stream (~0.57 MB per block) with 32-bit offsets
-#define R2L_CFG_ENTER(cfg)                                \
-    if (const char* r2l_why_ = r2l_cfg_check(cfg)) {      \
-        r2l_set_error_msg(r2l_why_);                      \
-        return (int)hipErrorInvalidValue;                 \
-    }                                                     \
-    R2LCfgScope scope(cfg)
-#define R2L_CFG_QUERY(cfg)                                \
-    if (const char* r2l_why_ = r2l_cfg_check(cfg)) {      \
-        r2l_set_error_msg(r2l_why_);                      \
-        return -1;                                        \
-    }                                                     \
-    R2LCfgScope scope(cfg)
-static inline bool r2l_env_on(const char* name) {
-    const char* e = getenv(name);
-    return e && e[0] && e[0] != '0';
-}
-static inline bool r2l_use_fwd3() {
-    if (g_r2l_cfg.precision) return g_r2l_cfg.precision != R2L_PRECISION_FP32_MFMA;
-    return !r2l_env_on("R2L_NO_FWD3");
-}
-// one-wave-per-tile forward launches: three fp16 products per fp32 product, ~2^-21 relative (r2l_fwd2.hip), with
-// the bf16x3 kernel launched behind it as the range-guard fallback (it returns at once unless the status word is raised).
-// R2L_NO_FWD2=1: bf16x3 only.
-static inline bool r2l_use_fwd2() {
-    if (g_r2l_cfg.precision) return g_r2l_cfg.precision == R2L_PRECISION_FP16X2;
-    return r2l_use_fwd3() && !r2l_env_on("R2L_NO_FWD2");
-}
 int r2l_fwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t stream);
 int r2l_fwd2_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                      const float* c2w_host12, int H, int W, float focal, const float* wstream2, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream);
+                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
+                     const float* c2w_dev, bool stash_mid);  // c2w_dev: pose table of a multi-frame launch (r2l_pose_of), or nullptr
 int r2l_fwd3_pack(const float* params, int n_block, float* wstream3, hipStream_t stream, const unsigned* run_if = nullptr);
 // Behind every fp16x2 forward launch: returns at once (GO = 0) unless that launch raised FLAG; else packs the bf16x3 stream,
 // re-packs the scale-dependent stages of the fp16x2 stream for the next activation scale and commits it (GO = 1, FLAG = 0
@@ -580,100 +527,18 @@ int r2l_fwd2_fallback_pack(const float* params, int n_block, float* wstream3, fl
 int r2l_fwd3_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                      const float* c2w_host12, int H, int W, float focal, const float* wstream3, const float* params,
                      int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const unsigned* run_if = nullptr, const float* x0_in = nullptr);  // x0_in: body + tail from a given X_0
+                     const unsigned* run_if = nullptr, const float* x0_in = nullptr,  // x0_in: body + tail from a given X_0
+                     const float* c2w_dev = nullptr);
 
-// Which chain variant is fastest for N rays.  In units of one main-kernel round (1024 wave slots x 32 rays): main needs
-// ceil(N/32768) rounds; coop (4 waves share a 32-ray tile, 256 workgroups) ceil(N/8192) rounds of ~0.34 (measured: fwd
-// 0.81 ms at 4096 rays, 0.94 ms at 8192); coop16 (4 waves share a 16-ray tile: fills all 256 CUs from 4096 rays)
-// ceil(N/4096) rounds of ~0.174 (0.47 ms at 4096 rays, 0.91 ms at 8192).
-// R2L_FORCE_VARIANT=main|coop|coop16 in the environment overrides (tests, A/B).
-#ifndef R2L_C16_ROUND
-#define R2L_C16_ROUND 0.174
-#endif
-enum { R2L_VARIANT_MAIN = 0, R2L_VARIANT_COOP16 = 2 };  // (1: the 32-ray fp32-MFMA cooperative family, retired in round 5)
-// Cooperative fp16x2 kernels (r2l_coopf.h: one 32-ray tile per WORKGROUP): a sub-family of the MAIN variant — same streams,
-// stash and fallbacks as r2l_fwd2 / r2l_bwd2, taken instead of them for launches of at most R2L_COOPF_MAX_RAYS rays, and
-// for launches between one and one and a half ROUNDS of the one-wave-per-tile kernels (a round = 256 CUs x 128 rays): the
-// two-tile cooperative kernels then run three full rounds of 16 384 rays where those run two, the second half empty
-// (measured, tools/variant_sweep.py, 49 152 rays: step 4.19 vs 4.51 ms, forward 1.44 vs 1.53 ms; 24 576: 2.55 vs 2.44,
-// 65 536: 5.53 vs 5.29, 98 304: 8.20 vs 7.81 — the one-wave-per-tile kernels everywhere else)
-// (R2L_FORCE_VARIANT=coopf: always; =main: never).  Only with the whole fp16 trio enabled (no R2L_NO_* switch).
+// launches of at most this many rays take the cooperative fp16x2 kernels (compile-time knob; the rule: r2l_dispatch.hip)
 #ifndef R2L_COOPF_MAX_RAYS
 #define R2L_COOPF_MAX_RAYS 16384
 #endif
-#define R2L_MAIN_ROUND_RAYS 32768  // one wave per 32-ray tile, four per workgroup, one workgroup per CU, 256 CUs
 // Keep a scalar fp32 chain scalar.  hipcc's SLP vectoriser pairs independent fp32 chains into packed ops with op_sel swizzles;
 // the form whose LOW lane reads the HIGH dword of src1 (`v_pk_fma_f32 ... op_sel:[0,1,0]`) lost results on gfx950 under two
 // waves per SIMD (r2l_coopf.h) and r2l_amd/build.py refuses objects that contain it: an empty asm on the value
 // between the operations is enough to keep them apart.
 __device__ __forceinline__ void r2l_no_pack(float& v) { asm volatile("" : "+v"(v)); }
-
-static inline bool r2l_fp16_trio_env() {
-    if (g_r2l_cfg.precision) return g_r2l_cfg.precision == R2L_PRECISION_FP16X2;
-    return !r2l_env_on("R2L_NO_FWD3") && !r2l_env_on("R2L_NO_FWD2") && !r2l_env_on("R2L_NO_BWD2") && !r2l_env_on("R2L_NO_DW2");
-}
-// the tiling a host pinned: cfg->tiling, else R2L_FORCE_VARIANT=main|coop|coop16|coopf, else R2L_TILING_AUTO
-static inline int r2l_forced_tiling() {
-    if (g_r2l_cfg.tiling) return g_r2l_cfg.tiling;
-    const char* e = getenv("R2L_FORCE_VARIANT");
-    if (!e || !e[0]) return R2L_TILING_AUTO;
-    if (e[0] == 'm') return R2L_TILING_WAVE_PER_TILE;
-    if (e[0] == 'c' && e[1] && e[2] && e[3] && e[4] == 'f') return R2L_TILING_COOPF;
-    if (e[0] == 'c') {  // coop16; "coop" named the retired 32-ray family: its launches are coop16's now — said once, not silently
-        if (e[1] && e[2] && e[3] && !e[4]) {
-            static bool warned = false;
-            if (!warned) {
-                warned = true;
-                fprintf(stderr, "libr2l_hip: R2L_FORCE_VARIANT=coop names the kernel family retired in round 5; taking coop16\n");
-            }
-        }
-        return R2L_TILING_COOP16;
-    }
-    return R2L_TILING_WAVE_PER_TILE;  // (anything else used to mean "not the cooperative fp16 kernels")
-}
-static inline bool r2l_use_coopf(int64_t N, int n_block) {
-    if (n_block <= 0 || !r2l_fp16_trio_env()) return false;
-    const int t = r2l_forced_tiling();
-    if (t == R2L_TILING_COOPF) return true;
-    if (t != R2L_TILING_AUTO) return false;
-    return N <= R2L_COOPF_MAX_RAYS || (N > R2L_MAIN_ROUND_RAYS && N <= R2L_MAIN_ROUND_RAYS + R2L_MAIN_ROUND_RAYS / 2);
-}
-static inline int r2l_chain_variant(int64_t N) {
-    const int t = r2l_forced_tiling();
-    if (t == R2L_TILING_WAVE_PER_TILE || t == R2L_TILING_COOPF) return R2L_VARIANT_MAIN;  // coopf: kernels of the MAIN family
-    if (t == R2L_TILING_COOP16) return R2L_VARIANT_COOP16;
-    if (r2l_fp16_trio_env() && N <= R2L_COOPF_MAX_RAYS) return R2L_VARIANT_MAIN;  // served by the cooperative fp16x2 kernels
-    // (one main round on the fp16x2 kernels costs 0.30 of a round of the fp32-MFMA kernel the unit was defined on; measured,
-    // tools/variant_sweep.py: 98 304-ray-style steps of 6144 rays 1.99 ms on the one-wave-per-tile kernels vs 2.11 ms on the
-    // 16-ray cooperative ones, 20 480 rays 2.9 vs 5.9 ms; 4096 rays 1.94 vs 1.34 ms)
-    // (round 5: the 32-ray fp32-MFMA cooperative family — 0.34 per round of 8192 rays — is retired: AUTO reached it only under a
-    // pinned fp32_mfma precision, in the bands where it beat two 16-ray rounds by 2 %: profiles/r05_dispatch_table.md)
-    const double main_t = (double)((N + 32767) / 32768) * (r2l_use_fwd3() ? 0.30 : 1.0);
-    const double c16_t = (double)((N + 4095) / 4096) * R2L_C16_ROUND;
-    return c16_t < main_t ? R2L_VARIANT_COOP16 : R2L_VARIANT_MAIN;
-}
-
-// The one-wave-per-tile training trios keep their stash (save_x[0..n-1], save_t, gx[1..n], gt) in a private layout: fp16
-// stage pieces (the default trio, r2l_f2.h) or the chunked fp32 layout above (bf16x3 trio); slot n of save_x then holds
-// y = x_n + x_0 row-major (all the tail gradient needs) and gx[0] stays row-major (head gradient).
-// Every other combination (cooperative chains, fp32 chains, the pre-embedded module-boundary path) is row-major throughout.
-static inline bool r2l_stash_chunked(int64_t N, bool pre_embedded) {
-    return !pre_embedded && N > 0 && r2l_chain_variant(N) == R2L_VARIANT_MAIN && r2l_use_fwd3();
-}
-
-// The default TRAINING trio of one-wave-per-tile MSE-mode steps: fp16x2 forward (r2l_fwd2.hip) and dX chain (r2l_bwd2.hip)
-// stashing fp16 stage pieces, and the fp16 weight-gradient GEMMs on them (r2l_dw16.hip).  Any of R2L_NO_FWD3 / R2L_NO_FWD2 /
-// R2L_NO_BWD2 / R2L_NO_DW2 = 1 puts the whole step on the bf16x3 trio (r2l_fwd3 / r2l_bwd3 / r2l_dw_body3c, chunked fp32
-// stash) — the kernels the range guards fall back to.  (Forward-only launches look at R2L_NO_FWD2 alone.)
-static inline bool r2l_use_trio16() {
-    if (g_r2l_cfg.precision) return g_r2l_cfg.precision == R2L_PRECISION_FP16X2;
-    return r2l_use_fwd2() && !r2l_env_on("R2L_NO_BWD2") && !r2l_env_on("R2L_NO_DW2");
-}
-// weight-gradient GEMMs of the fp16 trio with the ray-side operand as hi + mid (two products): cfg->dw_mode, else R2L_DW_EXACT=1
-static inline bool r2l_dw_exact() {
-    if (g_r2l_cfg.dw_mode) return g_r2l_cfg.dw_mode == R2L_DW_EXACT;
-    return r2l_env_on("R2L_DW_EXACT");
-}
 
 // error plumbing shared by the C-ABI translation units
 extern "C" const char* r2l_last_error(void);

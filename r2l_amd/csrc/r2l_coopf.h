@@ -20,6 +20,7 @@
 //   * The kernel is bound by that weight stream (256 KiB per layer and workgroup from L2), not by the matrix pipe.
 #pragma once
 #include "r2l_f2.h"
+#include "r2l_dispatch.h"
 #include <stdio.h>
 
 // register-ring depth (stages of A operands in flight per wave), per tiles-per-workgroup.  A one-tile workgroup has the CU
@@ -43,7 +44,7 @@ template <int NT> struct FcRingOf { static constexpr int value = NT == 1 ? FC_RI
 // the absence of a second wave is known to avoid — every one-tile launch still carries FC_SOLO_LDS_BYTES of dynamic LDS
 // (64 - 72 KiB static + 24 KiB > half of the CU's 160 KiB), checked per kernel with hipOccupancyMaxActiveBlocksPerMultiprocessor
 // before its first launch (fc_check_solo).  It costs nothing: these launches have at most one tile per CU by construction
-// (r2l_coopf_two_tiles), and two-tile workgroups (143 KiB) cannot share a CU at all.  Only the reproducer builds
+// (R2LPlan.coop_tiles), and two-tile workgroups (143 KiB) cannot share a CU at all.  Only the reproducer builds
 // (tools/build_variant.sh ... -DFC_ALLOW_SHARE_CU) drop the padding.
 #ifdef FC_ALLOW_SHARE_CU
 #define FC_SOLO_LDS_BYTES 0
@@ -255,34 +256,7 @@ __device__ __forceinline__ void fc_produce(const f32x16 (&frag)[2], unsigned bop
 // weight stream each XCD's L2 serves its CUs (~1.2 - 1.6 TB/s per XCD at 24 - 32 streaming workgroups), so putting the idle
 // CUs to work on one more stream each slows every workgroup down by more than the shorter two-tile queue gains
 // (profiles/r06_mixed_coopf_ab.txt).  AUTO therefore keeps the round-5 policy.
-static inline int r2l_coopf_n_cu() {
-    static int n_cu = 0;  // one device type per process
-    if (n_cu == 0) {
-        int dev = 0, v = 0;
-        n_cu = (hipGetDevice(&dev) == hipSuccess && hipDeviceGetAttribute(&v, hipDeviceAttributeMultiprocessorCount, dev) == hipSuccess && v > 0) ? v : 256;
-    }
-    return n_cu;
-}
-static inline int r2l_coopf_policy(int64_t tiles) {
-    int want = g_r2l_cfg.coop_tiles;
-    if (want == 0) {
-        if (const char* e = getenv("R2L_COOPF_TILES")) {
-            if (e[0] >= '1' && e[0] <= '3') want = e[0] - '0';
-        }
-    }
-    if (want == 1 || want == 2) return want;
-    const int n_cu = r2l_coopf_n_cu();
-    if (tiles <= n_cu) return 1;
-    if (tiles >= 2 * (int64_t)n_cu) return 2;
-#ifndef FC_MIXED_AUTO  // (A/B builds with -DFC_MIXED_AUTO: AUTO takes the mixed grid in its band)
-    if (want == 0) return 2;
-#endif
-    return 3;
-}
-static inline bool r2l_coopf_two_tiles(int64_t tiles) { return r2l_coopf_policy(tiles) == 2; }
-// two-tile workgroups of a MIXED launch (its grid has tiles - this many workgroups), or 0: not a mixed launch
-static inline int r2l_coopf_mixed_two(int64_t tiles) { return r2l_coopf_policy(tiles) == 3 ? (int)(tiles - r2l_coopf_n_cu()) : 0; }
-
+// (r2l_dispatch.hip r2l_plan resolves the policy: R2LPlan.coop_tiles / n_two)
 // Position of this workgroup in the role order of a MIXED launch.  The two roles run at different paces (one tile: ~3.1 us per
 // layer, two tiles: ~4.5 us), and the workgroups of one XCD share the weight stream through that XCD's 4 MiB L2 only while they
 // stay within a few blocks (0.57 MB each) of each other: with the roles interleaved over the XCDs (position = blockIdx) the
@@ -296,16 +270,3 @@ __device__ __forceinline__ int fc_mixed_index(int xcd_major) {
     if (!xcd_major || (g & 7) != 0) return b;
     return (b & 7) * (g >> 3) + (b >> 3);
 }
-static inline int r2l_coopf_mixed_xcd_major() {
-    const char* e = getenv("R2L_MIXED_MAP");  // A/B knob: 0 (default) = roles by blockIdx, 1 = XCD-major
-    return (e && e[0] == '1') ? 1 : 0;
-}
-
-// launchers (called from r2l_fwd2_forward / r2l_bwd2_backward when the launch is small: r2l_use_coopf)
-int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab, const float* c2w_host12,
-                      int H, int W, float focal, const float* wstream2, const float* params, int n_block, float* rgb,
-                      float* save_x, float* save_t, int64_t N, hipStream_t stream);
-int r2l_coopf_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                       const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                       const float* scale_dev, int b_start = -1, int b_end = 0);  // blocks b_start (-1: the last) down to b_end

@@ -297,7 +297,7 @@ __global__ __launch_bounds__(256, 1) void r2l_coopf_bwd_mixed_kernel(const CfBwd
 int r2l_coopf_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
                        const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
                        float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                       const float* scale_dev, int b_start, int b_end) {
+                       const float* scale_dev, const R2LPlan& plan, int b_start, int b_end) {
     CfBwdArgs a{};
     a.b_start = b_start < 0 ? n_block - 1 : b_start;
     a.b_end = b_end;
@@ -308,23 +308,23 @@ int r2l_coopf_backward(const float* rgb, const float* target, const float* drgb,
     a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t;
     a.stream = reinterpret_cast<const unsigned char*>(wstream_bwd2); a.params = params; a.n_block = n_block;
     a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt; a.sqerr_partial = sqerr_partial; a.N = N;
-    a.mid_units = r2l_dw_exact() ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
+    a.mid_units = plan.stash_mid ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     static int solo_ok[2] = {0, 0};
-    if (const int n_two = r2l_coopf_mixed_two(tiles); n_two > 0) {  // between one and two tiles per CU: one workgroup on every CU
+    if (const int n_two = plan.n_two; n_two > 0) {  // between one and two tiles per CU: one workgroup on every CU
         a.n_two = n_two;
-        a.xcd_major = r2l_coopf_mixed_xcd_major();
+        a.xcd_major = plan.xcd_major;
         const dim3 grid((unsigned)(tiles - n_two));
         if (a.mid_units != 0) hipLaunchKernelGGL((r2l_coopf_bwd_mixed_kernel<true>), grid, dim3(256), 0, stream, a);
         else hipLaunchKernelGGL((r2l_coopf_bwd_mixed_kernel<false>), grid, dim3(256), 0, stream, a);
     } else if (a.mid_units != 0) {  // exact weight gradients: the mid halves of g / masked u are stashed too
-        if (r2l_coopf_two_tiles(tiles))
+        if (plan.coop_tiles == 2)
             hipLaunchKernelGGL((r2l_coopf_bwd_kernel<2, true>), dim3((unsigned)((tiles + 1) / 2)), dim3(256), 0, stream, a);
         else {
             if (int e = fc_check_solo(r2l_coopf_bwd_kernel<1, true>, "r2l_coopf_bwd_kernel<1, mid>", &solo_ok[1])) return e;
             hipLaunchKernelGGL((r2l_coopf_bwd_kernel<1, true>), dim3((unsigned)tiles), dim3(256), FC_SOLO_LDS_BYTES, stream, a);
         }
-    } else if (r2l_coopf_two_tiles(tiles)) {
+    } else if (plan.coop_tiles == 2) {
         hipLaunchKernelGGL((r2l_coopf_bwd_kernel<2>), dim3((unsigned)((tiles + 1) / 2)), dim3(256), 0, stream, a);
     } else {
         if (int e = fc_check_solo(r2l_coopf_bwd_kernel<1>, "r2l_coopf_bwd_kernel<1>", &solo_ok[0])) return e;

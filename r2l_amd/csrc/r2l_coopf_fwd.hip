@@ -387,20 +387,20 @@ __global__ __launch_bounds__(256, 1) void r2l_coopf_fwd_mixed_kernel(const CfFwd
 
 int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab, const float* c2w_host12,
                       int H, int W, float focal, const float* wstream2, const float* params, int n_block, float* rgb,
-                      float* save_x, float* save_t, int64_t N, hipStream_t stream) {
+                      float* save_x, float* save_t, int64_t N, hipStream_t stream, const R2LPlan& plan) {
     CfFwdArgs a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = params;
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + r2l_fwd2_status_offset(n_block));
     a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
     if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.mid_units = (save_x != nullptr && r2l_dw_exact()) ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
+    a.mid_units = (save_x != nullptr && plan.stash_mid) ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     // up to one workgroup per CU: one ray tile each; beyond, two tiles per workgroup share every weight load; between one and
     // two tiles per CU: the mixed grid (explicit rays only: the single-pose render launches are far above this band)
-    if (const int n_two = r2l_coopf_mixed_two(tiles); n_two > 0 && !c2w_host12) {
+    if (const int n_two = plan.n_two; n_two > 0 && !c2w_host12) {
         a.n_two = n_two;
-        a.xcd_major = r2l_coopf_mixed_xcd_major();
+        a.xcd_major = plan.xcd_major;
         const dim3 grid((unsigned)(tiles - n_two)), block(256);
         if (save_x && a.mid_units != 0) hipLaunchKernelGGL((r2l_coopf_fwd_mixed_kernel<true, true>), grid, block, 0, stream, a);
         else if (save_x) hipLaunchKernelGGL((r2l_coopf_fwd_mixed_kernel<true, false>), grid, block, 0, stream, a);
@@ -408,7 +408,7 @@ int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_r
         R2L_CHECK(hipGetLastError());
         return 0;
     }
-    const bool two = r2l_coopf_two_tiles(tiles);
+    const bool two = plan.coop_tiles == 2;
     const dim3 grid((unsigned)(two ? (tiles + 1) / 2 : tiles)), block(256);
     static int solo_ok[4] = {0, 0, 0, 0};  // one-tile kernels: at most one workgroup per CU, verified before the first launch
     if (c2w_host12) {
@@ -444,7 +444,6 @@ int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_r
 // that many ray tiles per workgroup (host-side decision, no device work; include/r2l_hip.h)
 extern "C" int r2l_coop_tiles_for_cfg(int64_t N, int n_block, const r2l_config* cfg) {
     R2L_CFG_QUERY(cfg);
-    if (!r2l_use_coopf(N, n_block)) return 0;
-    return r2l_coopf_policy((N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS);
+    return r2l_plan(cfg, N, n_block, false, false).coop_tiles;
 }
 extern "C" int r2l_coop_tiles_for(int64_t N, int n_block) { return r2l_coop_tiles_for_cfg(N, n_block, nullptr); }

@@ -6,7 +6,7 @@
 //
 // One wavefront = 32 rays for the whole network, activations register-resident in MFMA fragment layout
 // (see r2l_common.h); exact-fp32 v_mfma_f32_32x32x2_f32; 4 independent waves per 256-thread block, one per SIMD.
-#include "r2l_common.h"
+#include "r2l_dispatch.h"
 
 struct R2LFwdArgs {
     // inputs (exactly one of {rays_o/rays_d}, {pose}, {emb} is used, selected by the MODE template argument)
@@ -258,6 +258,37 @@ static int launch_fwd(const R2LFwdArgs& a, hipStream_t stream) {
 // ------------------------------------------------------------------------------------------------------------------
 // C ABI (declared in include/r2l_hip.h)
 // ------------------------------------------------------------------------------------------------------------------
+// One forward launch, as the plan says, of the rays in `a`: given explicitly (rays_o / rays_d, with or without the training
+// stash), by one pose (c2w_host12: a.c2w), or by a device table of poses (c2w_dev: several frames).  Behind a fp16x2 launch
+// comes its range-guard fallback: stream pack + the bf16x3 launch, both returning at once unless it raised its status word.
+static int forward_launch(const R2LPlan& plan, const R2LFwdArgs& a, const float* c2w_host12, const float* c2w_dev, hipStream_t stream) {
+    const R2LStreams w = r2l_fwd_streams(a.wstream, a.n_block);
+    if (plan.fwd == R2L_CHAIN_COOP16)
+        return r2l_coop16_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w16, a.params, a.n_block,
+                                  a.rgb, a.save_x, a.save_t, a.N, stream);
+    const unsigned* run_if = nullptr;
+    if (plan.fwd == R2L_CHAIN_FP16) {
+        // small launches: one 32-ray tile per workgroup instead of per wave (r2l_coopf_fwd.hip), same stream / stash / status word
+        const int rc = plan.tiling == R2L_TILING_COOPF
+                           ? r2l_coopf_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w2, a.params,
+                                               a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, plan)
+                           : r2l_fwd2_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w2, a.params,
+                                              a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, c2w_dev, plan.stash_mid);
+        if (rc) return rc;
+        const int rp = r2l_fwd2_fallback_pack(a.params, a.n_block, w.w3, w.w2, stream);
+        if (rp) return rp;
+        run_if = w.status + F2S_GO;
+    }
+    if (plan.fwd == R2L_CHAIN_FP16 || plan.fwd == R2L_CHAIN_BF16X3)
+        return r2l_fwd3_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w3, a.params, a.n_block,
+                                a.rgb, a.save_x, a.save_t, a.N, stream, run_if, nullptr, c2w_dev);
+    if (c2w_host12 == nullptr) return launch_fwd<MODE_RAYS>(a, stream);
+    return launch_fwd<MODE_POSE>(a, stream);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// C ABI (declared in include/r2l_hip.h)
+// ------------------------------------------------------------------------------------------------------------------
 extern "C" int r2l_forward_rays(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                                 const float* wstream, const float* params, int n_block, float* rgb, float* save_x,
                                 float* save_t, int64_t N, void* stream) {
@@ -275,37 +306,32 @@ extern "C" int r2l_forward_rays_cfg(const float* rays_o, const float* rays_d, co
     a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.wstream = wstream; a.params = params; a.n_block = n_block;
     a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
-    const int variant = N > 0 ? r2l_chain_variant(N) : R2L_VARIANT_MAIN;
-    if (variant == R2L_VARIANT_COOP16)
-        return r2l_coop16_forward(rays_o, rays_d, t_rand, ztab, nullptr, 0, 0, 0.f, wstream + r2l_fwd32_stream_floats(n_block),
-                                  params, n_block, rgb, save_x, save_t, N, (hipStream_t)stream);
-    // (with the training stash: only as part of the default fp16 trio, whose stash format it writes)
-    if (N > 0 && (save_x != nullptr ? r2l_use_trio16() : r2l_use_fwd2())) {
-        const float* w3 = wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block);
-        const float* w2 = w3 + r2l_fwd3_stream_floats(n_block);
-        const int rc = r2l_fwd2_forward(rays_o, rays_d, t_rand, ztab, nullptr, 0, 0, 0.f, w2, params, n_block, rgb, save_x,
-                                        save_t, N, (hipStream_t)stream);
-        if (rc) return rc;
-        // range-guard fallback: stream pack + launch, both returning at once unless the fp16x2 launch raised its status word
-        const unsigned* st = reinterpret_cast<const unsigned*>(w2 + r2l_fwd2_status_offset(n_block));
-        const int rp = r2l_fwd2_fallback_pack(params, n_block, const_cast<float*>(w3), const_cast<float*>(w2), (hipStream_t)stream);
-        if (rp) return rp;
-        return r2l_fwd3_forward(rays_o, rays_d, t_rand, ztab, nullptr, 0, 0, 0.f, w3, params, n_block, rgb, save_x, save_t, N,
-                                (hipStream_t)stream, st + F2S_GO);
-    }
-    if (N > 0 && r2l_use_fwd3())
-        return r2l_fwd3_forward(rays_o, rays_d, t_rand, ztab, nullptr, 0, 0, 0.f,
-                                wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block), params,
-                                n_block, rgb, save_x, save_t, N, (hipStream_t)stream);
-    return launch_fwd<MODE_RAYS>(a, (hipStream_t)stream);
+    return forward_launch(r2l_plan(cfg, N, n_block, save_x != nullptr, false), a, nullptr, nullptr, (hipStream_t)stream);
 }
 
 extern "C" int r2l_forward_pose(const float* c2w_host12, int H, int W, float focal, const float* ztab,
                                 const float* wstream, const float* params, int n_block, float* rgb, void* stream) {
     return r2l_forward_pose_cfg(c2w_host12, H, W, focal, ztab, wstream, params, n_block, rgb, stream, nullptr);
 }
-static int forward_pose_impl(const float* c2w_host12, int64_t n_frames, int H, int W, float focal, const float* ztab,
-                             const float* wstream, const float* params, int n_block, float* rgb, void* stream);
+// n_frames poses: one by value (c2w_host12), or — c2w_host12 == nullptr — a device table (c2w_dev)
+static int forward_poses(const r2l_config* cfg, const float* c2w_host12, const float* c2w_dev, int64_t n_frames, int H, int W,
+                         float focal, const float* ztab, const float* wstream, const float* params, int n_block, float* rgb,
+                         void* stream) {
+    R2LFwdArgs a{};
+    a.c2w_dev = c2w_dev;
+    a.H = H; a.Wimg = W; a.focal = focal; a.ztab = ztab;
+    a.wstream = wstream; a.params = params; a.n_block = n_block;
+    a.rgb = rgb; a.N = n_frames * H * W;
+    const R2LPlan plan = r2l_plan(cfg, a.N, n_block, false, false);
+    if (c2w_host12 != nullptr) {
+        for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
+    } else if (c2w_dev == nullptr || plan.tiling != R2L_TILING_WAVE_PER_TILE) {
+        r2l_set_error_msg("r2l_forward_poses: needs a device pose table and a one-wave-per-tile tiling (cooperative tilings: "
+                          "call r2l_forward_pose per frame)");
+        return (int)hipErrorInvalidValue;
+    }
+    return forward_launch(plan, a, c2w_host12 ? c2w_host12 : a.c2w, c2w_dev, (hipStream_t)stream);
+}
 
 extern "C" int r2l_forward_pose_cfg(const float* c2w_host12, int H, int W, float focal, const float* ztab,
                                     const float* wstream, const float* params, int n_block, float* rgb, void* stream,
@@ -313,7 +339,7 @@ extern "C" int r2l_forward_pose_cfg(const float* c2w_host12, int H, int W, float
     R2L_CFG_ENTER(cfg);
     R2L_REQUIRE(H > 0 && W > 0 && focal != 0.f && n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_forward_pose: H / W / focal / n_block out of range");
     R2L_REQUIRE(c2w_host12 && ztab && wstream && params && rgb, "r2l_forward_pose: a required pointer is NULL");
-    return forward_pose_impl(c2w_host12, 1, H, W, focal, ztab, wstream, params, n_block, rgb, stream);
+    return forward_poses(cfg, c2w_host12, nullptr, 1, H, W, focal, ztab, wstream, params, n_block, rgb, stream);
 }
 
 // K frames in ONE launch: rgb[K*H*W,3], poses from a device table (include/r2l_hip.h).  The cooperative tilings (small
@@ -325,56 +351,13 @@ extern "C" int r2l_forward_poses_cfg(const float* c2w_dev, int K, int H, int W, 
     if (K <= 0) return 0;
     R2L_REQUIRE(H > 0 && W > 0 && focal != 0.f && n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_forward_poses: H / W / focal / n_block out of range");
     R2L_REQUIRE(ztab && wstream && params && rgb, "r2l_forward_poses: a required pointer is NULL");
-    const int64_t N = (int64_t)K * H * W;
-    if (c2w_dev == nullptr || r2l_chain_variant(N) != R2L_VARIANT_MAIN || r2l_use_coopf(N, n_block)) {
-        r2l_set_error_msg("r2l_forward_poses: needs a device pose table and a one-wave-per-tile tiling (cooperative tilings: "
-                          "call r2l_forward_pose per frame)");
-        return (int)hipErrorInvalidValue;
-    }
-    const float dummy[12] = {0};
-    g_r2l_c2w_dev = c2w_dev;
-    const int rc = forward_pose_impl(dummy, K, H, W, focal, ztab, wstream, params, n_block, rgb, stream);
-    g_r2l_c2w_dev = nullptr;
-    return rc;
-}
-
-static int forward_pose_impl(const float* c2w_host12, int64_t n_frames, int H, int W, float focal, const float* ztab,
-                             const float* wstream, const float* params, int n_block, float* rgb, void* stream) {
-    R2LFwdArgs a{};
-    for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.c2w_dev = g_r2l_c2w_dev;
-    a.H = H; a.Wimg = W; a.focal = focal; a.ztab = ztab;
-    a.wstream = wstream; a.params = params; a.n_block = n_block;
-    a.rgb = rgb; a.N = n_frames * H * W;
-    const int variant = a.N > 0 ? r2l_chain_variant(a.N) : R2L_VARIANT_MAIN;
-    if (variant == R2L_VARIANT_COOP16)
-        return r2l_coop16_forward(nullptr, nullptr, nullptr, ztab, c2w_host12, H, W, focal,
-                                  wstream + r2l_fwd32_stream_floats(n_block), params, n_block, rgb, nullptr, nullptr, a.N,
-                                  (hipStream_t)stream);
-    if (a.N > 0 && r2l_use_fwd2()) {
-        const float* w3 = wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block);
-        const float* w2 = w3 + r2l_fwd3_stream_floats(n_block);
-        const int rc = r2l_fwd2_forward(nullptr, nullptr, nullptr, ztab, c2w_host12, H, W, focal, w2, params, n_block, rgb,
-                                        nullptr, nullptr, a.N, (hipStream_t)stream);
-        if (rc) return rc;
-        const unsigned* st = reinterpret_cast<const unsigned*>(w2 + r2l_fwd2_status_offset(n_block));
-        const int rp = r2l_fwd2_fallback_pack(params, n_block, const_cast<float*>(w3), const_cast<float*>(w2), (hipStream_t)stream);
-        if (rp) return rp;
-        return r2l_fwd3_forward(nullptr, nullptr, nullptr, ztab, c2w_host12, H, W, focal, w3, params, n_block, rgb, nullptr,
-                                nullptr, a.N, (hipStream_t)stream, st + F2S_GO);
-    }
-    if (a.N > 0 && r2l_use_fwd3())
-        return r2l_fwd3_forward(nullptr, nullptr, nullptr, ztab, c2w_host12, H, W, focal,
-                                wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block), params,
-                                n_block, rgb, nullptr, nullptr, a.N, (hipStream_t)stream);
-    return launch_fwd<MODE_POSE>(a, (hipStream_t)stream);
+    return forward_poses(cfg, nullptr, c2w_dev, K, H, W, focal, ztab, wstream, params, n_block, rgb, stream);
 }
 
 // The 16 status words of the fp16x2 forward stream inside `wstream` (include/r2l_hip.h: range control, telemetry)
 extern "C" const unsigned* r2l_forward_status_words(const float* wstream, int n_block) {
     if (wstream == nullptr || n_block < 0 || n_block > R2L_MAX_BLOCKS) return nullptr;
-    const float* w2 = wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block) + r2l_fwd3_stream_floats(n_block);
-    return reinterpret_cast<const unsigned*>(w2 + r2l_fwd2_status_offset(n_block));
+    return r2l_fwd_streams(wstream, n_block).status;
 }
 
 // The module-boundary path with a config (round 5).  precision = bf16x3 (or fp16x2: this path has no range-guard
@@ -388,7 +371,7 @@ extern "C" int r2l_forward_emb_cfg(const float* emb, const float* wstream, const
                                    float* save_x, float* save_t, int64_t N, float* x0_scratch, void* stream,
                                    const r2l_config* cfg) {
     R2L_CFG_ENTER(cfg);
-    const bool chain16 = g_r2l_cfg.precision == R2L_PRECISION_BF16X3 || g_r2l_cfg.precision == R2L_PRECISION_FP16X2;
+    const bool chain16 = r2l_plan(cfg, N, n_block, save_x != nullptr, true).fwd == R2L_CHAIN_BF16X3;
     if (!chain16 || save_x != nullptr || save_t != nullptr || x0_scratch == nullptr || n_block <= 0 || N <= 0)
         return r2l_forward_emb(emb, wstream, params, n_block, rgb, save_x, save_t, N, stream);
     R2L_REQUIRE(n_block <= R2L_MAX_BLOCKS, "r2l_forward_emb_cfg: n_block out of range");
@@ -398,9 +381,8 @@ extern "C" int r2l_forward_emb_cfg(const float* emb, const float* wstream, const
     a.rgb = rgb; a.save_x = x0_scratch; a.save_t = nullptr; a.N = N;
     const int rc = launch_fwd<MODE_EMB>(a, (hipStream_t)stream);
     if (rc) return rc;
-    return r2l_fwd3_forward(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f,
-                            wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block), params, n_block, rgb,
-                            nullptr, nullptr, N, (hipStream_t)stream, nullptr, x0_scratch);
+    return r2l_fwd3_forward(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, r2l_fwd_streams(wstream, n_block).w3, params,
+                            n_block, rgb, nullptr, nullptr, N, (hipStream_t)stream, nullptr, x0_scratch);
 }
 
 extern "C" int r2l_forward_emb(const float* emb, const float* wstream, const float* params, int n_block, float* rgb,

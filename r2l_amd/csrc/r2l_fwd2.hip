@@ -369,11 +369,8 @@ int r2l_fwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t
 
 int r2l_fwd2_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                      const float* c2w_host12, int H, int W, float focal, const float* wstream2, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream) {
-    // small launches: one 32-ray tile per workgroup instead of per wave (r2l_coopf_fwd.hip), same stream / stash / status word
-    if (r2l_use_coopf(N, n_block))
-        return r2l_coopf_forward(rays_o, rays_d, t_rand, ztab, c2w_host12, H, W, focal, wstream2, params, n_block, rgb, save_x,
-                                 save_t, N, stream);
+                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
+                     const float* c2w_dev, bool stash_mid) {
     F2Args a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = params;
@@ -381,8 +378,8 @@ int r2l_fwd2_forward(const float* rays_o, const float* rays_d, const float* t_ra
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + r2l_fwd2_status_offset(n_block));
     a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
     if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.c2w_dev = c2w_host12 ? g_r2l_c2w_dev : nullptr;
-    a.stash_mid = (save_x != nullptr && r2l_dw_exact()) ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
+    a.c2w_dev = c2w_host12 ? c2w_dev : nullptr;
+    a.stash_mid = (save_x != nullptr && stash_mid) ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
     if (c2w_host12) hipLaunchKernelGGL((r2l_fwd2_kernel<true, false>), grid, block, 0, stream, a);

@@ -396,14 +396,14 @@ int r2l_fwd2_fallback_pack(const float* params, int n_block, float* wstream3, fl
 int r2l_fwd3_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                      const float* c2w_host12, int H, int W, float focal, const float* wstream3, const float* params,
                      int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const unsigned* run_if, const float* x0_in) {
+                     const unsigned* run_if, const float* x0_in, const float* c2w_dev) {
     F3Args a{};
     a.run_if = run_if;
     a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.stream = reinterpret_cast<const unsigned char*>(wstream3); a.params = params;
     a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
     if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.c2w_dev = c2w_host12 ? g_r2l_c2w_dev : nullptr;
+    a.c2w_dev = c2w_host12 ? c2w_dev : nullptr;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
     if (x0_in != nullptr) {  // body + tail from a given X_0: the stream starts at the first body stage

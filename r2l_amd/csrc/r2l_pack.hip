@@ -1,7 +1,7 @@
 // r2l_pack.hip — re-pack the nn.Linear weights of NeRF_v3_2 (flat state_dict-order fp32 buffer; layer shapes from
 // /root/reference/model/nerf_raybased.py:500-537) into the per-lane MFMA A-operand weight streams that the chain
 // kernels consume sequentially (layout contract: r2l_common.h).  Runs once per optimizer step (23.7 MB gather).
-#include "r2l_common.h"
+#include "r2l_dispatch.h"
 
 __host__ __device__ static inline int64_t pk_off_body_w(int layer) {
     return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
@@ -120,8 +120,7 @@ extern "C" int64_t r2l_param_count(int n_block) {
     return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)2 * n_block * (R2L_W * R2L_W + R2L_W) + 3 * R2L_W + 3;
 }
 
-// a stream buffer = [32-ray-tile layout | 16-ray-tile layout | bf16x3 stages | fp16x2 stages (forward stream only)]; every
-// kernel finds its part by offset
+// a stream buffer holds every layout (r2l_dispatch.h R2LStreams); every kernel finds its part there
 extern "C" int64_t r2l_fwd_stream_floats(int n_block) {
     return r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block) + r2l_fwd3_stream_floats(n_block) +
            r2l_fwd2_stream_floats(n_block);
@@ -136,7 +135,7 @@ extern "C" int64_t r2l_bwd_stream_floats(int n_block) {
 // launches use (r2l_variant_for) can skip the other half of the stream: 10 us each, 3 % of a 4096-ray step.
 extern "C" int r2l_variant_for_cfg(int64_t N, const r2l_config* cfg) {
     R2L_CFG_QUERY(cfg);
-    return r2l_chain_variant(N);
+    return r2l_plan(cfg, N, 0, false, false).tiling == R2L_TILING_COOP16 ? 2 : 0;  // (0: main family; 1: retired in round 5; 2: coop16)
 }
 extern "C" int r2l_variant_for(int64_t N) { return r2l_variant_for_cfg(N, nullptr); }
 // stream layout a forward launch with N rays reads: 16 / 32 (cooperative variants / fp32-MFMA kernels), 3 (the bf16x3
@@ -145,105 +144,59 @@ extern "C" int r2l_variant_for(int64_t N) { return r2l_variant_for_cfg(N, nullpt
 extern "C" int r2l_forward_layout_for(int64_t N, int with_stash) { return r2l_forward_layout_for_cfg(N, with_stash, nullptr); }
 extern "C" int r2l_forward_layout_for_cfg(int64_t N, int with_stash, const r2l_config* cfg) {
     R2L_CFG_QUERY(cfg);
-    const int v = r2l_chain_variant(N);
-    if (v == R2L_VARIANT_COOP16) return 16;
-    if (v == R2L_VARIANT_MAIN && (with_stash ? r2l_use_trio16() : r2l_use_fwd2())) return 2;
-    if (v == R2L_VARIANT_MAIN && r2l_use_fwd3()) return 3;
-    return 32;
+    return r2l_plan(cfg, N, 0, with_stash != 0, false).fwd_layout;
 }
 // transposed-stream layout the backward of an N-ray launch reads: 16 / 32 as the forward, 3 (bf16x3 dX chain) or 2 (fp16x2 dX
 // chain with the bf16x3 stream behind it as range-guard fallback: r2l_pack_backward_layout(2) fills both)
 extern "C" int r2l_backward_layout_for(int64_t N) { return r2l_backward_layout_for_cfg(N, nullptr); }
 extern "C" int r2l_backward_layout_for_cfg(int64_t N, const r2l_config* cfg) {
     R2L_CFG_QUERY(cfg);
-    const int v = r2l_chain_variant(N);
-    if (v == R2L_VARIANT_COOP16) return 16;
-    if (v == R2L_VARIANT_MAIN && r2l_use_fwd3()) return r2l_use_trio16() ? 2 : 3;
-    return 32;
+    return r2l_plan(cfg, N, 0, true, false).bwd_layout;
+}
+// every stream layout (layout 0), or the one named
+static int pack_layouts(bool fwd, const float* params, int n_block, float* wstream, int layout, hipStream_t stream) {
+    const R2LStreams w = fwd ? r2l_fwd_streams(wstream, n_block) : r2l_bwd_streams(wstream, n_block);
+    if (layout == 0 || layout == 32) {
+        if (fwd) hipLaunchKernelGGL(r2l_pack_fwd_kernel, dim3(2048), dim3(256), 0, stream, params, w.w32, n_block);
+        else hipLaunchKernelGGL(r2l_pack_bwd_kernel, dim3(2048), dim3(256), 0, stream, params, w.w32, n_block);
+        R2L_CHECK(hipGetLastError());
+    }
+    if (layout == 0 || layout == 16) {
+        if (fwd) hipLaunchKernelGGL(r2l_pack_fwd16_kernel, dim3(2048), dim3(256), 0, stream, params, w.w16, n_block);
+        else hipLaunchKernelGGL(r2l_pack_bwd16_kernel, dim3(2048), dim3(256), 0, stream, params, w.w16, n_block);
+        R2L_CHECK(hipGetLastError());
+    }
+    if (layout == 0 || layout == 3) {  // (layout 2's bf16x3 fallback stream is packed by the fallback launch itself, when it runs)
+        const int rc = fwd ? r2l_fwd3_pack(params, n_block, w.w3, stream) : r2l_bwd3_pack(params, n_block, w.w3, stream);
+        if (rc) return rc;
+    }
+    if (layout == 0 || layout == 2) {
+        const int rc = fwd ? r2l_fwd2_pack(params, n_block, w.w2, stream) : r2l_bwd2_pack(params, n_block, w.w2, stream);
+        if (rc) return rc;
+    }
+    return 0;
 }
 extern "C" int r2l_pack_forward_layout(const float* params, int n_block, float* wstream, int layout, void* stream) {
     R2L_REQUIRE(params && wstream, "r2l_pack_forward_layout: params / wstream is NULL");
     R2L_REQUIRE(n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_pack_forward_layout: n_block out of range");
     R2L_REQUIRE(layout == 0 || layout == 32 || layout == 16 || layout == 3 || layout == 2, "r2l_pack_forward_layout: layout is 0, 32, 16, 3 or 2");
-    if (layout == 0 || layout == 32) {
-        hipLaunchKernelGGL(r2l_pack_fwd_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params, wstream, n_block);
-        R2L_CHECK(hipGetLastError());
-    }
-    if (layout == 0 || layout == 16) {
-        hipLaunchKernelGGL(r2l_pack_fwd16_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params,
-                           wstream + r2l_fwd32_stream_floats(n_block), n_block);
-        R2L_CHECK(hipGetLastError());
-    }
-    if (layout == 0 || layout == 3) {  // (layout 2's bf16x3 fallback stream is packed by the fallback launch itself, when it runs)
-        const int rc = r2l_fwd3_pack(params, n_block, wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block),
-                                     (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    if (layout == 0 || layout == 2) {
-        const int rc = r2l_fwd2_pack(params, n_block,
-                                     wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block) +
-                                         r2l_fwd3_stream_floats(n_block),
-                                     (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return pack_layouts(true, params, n_block, wstream, layout, (hipStream_t)stream);
 }
 extern "C" int r2l_pack_backward_layout(const float* params, int n_block, float* wstream, int layout, void* stream) {
     R2L_REQUIRE(params && wstream, "r2l_pack_backward_layout: params / wstream is NULL");
     R2L_REQUIRE(n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_pack_backward_layout: n_block out of range");
     R2L_REQUIRE(layout == 0 || layout == 32 || layout == 16 || layout == 3 || layout == 2, "r2l_pack_backward_layout: layout is 0, 32, 16, 3 or 2");
-    if (layout == 0 || layout == 32) {
-        hipLaunchKernelGGL(r2l_pack_bwd_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params, wstream, n_block);
-        R2L_CHECK(hipGetLastError());
-    }
-    if (layout == 0 || layout == 16) {
-        hipLaunchKernelGGL(r2l_pack_bwd16_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params,
-                           wstream + r2l_bwd32_stream_floats(n_block), n_block);
-        R2L_CHECK(hipGetLastError());
-    }
-    if (layout == 0 || layout == 3) {  // (layout 2's bf16x3 fallback stream is packed by the fallback launch itself, when it runs)
-        const int rc = r2l_bwd3_pack(params, n_block, wstream + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block),
-                                     (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    if (layout == 0 || layout == 2) {
-        const int rc = r2l_bwd2_pack(params, n_block,
-                                     wstream + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block) +
-                                         r2l_bwd3_stream_floats(n_block),
-                                     (hipStream_t)stream);
-        if (rc) return rc;
-    }
-    return 0;
+    return pack_layouts(false, params, n_block, wstream, layout, (hipStream_t)stream);
 }
 
 extern "C" int r2l_pack_forward(const float* params, int n_block, float* wstream, void* stream) {
     R2L_REQUIRE(params && wstream, "r2l_pack_forward: params / wstream is NULL");
     R2L_REQUIRE(n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_pack_forward: n_block out of range");
-    hipLaunchKernelGGL(r2l_pack_fwd_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params, wstream, n_block);
-    R2L_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(r2l_pack_fwd16_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params,
-                       wstream + r2l_fwd32_stream_floats(n_block), n_block);
-    R2L_CHECK(hipGetLastError());
-    const int rc = r2l_fwd3_pack(params, n_block, wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block),
-                                 (hipStream_t)stream);
-    if (rc) return rc;
-    return r2l_fwd2_pack(params, n_block,
-                         wstream + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block) + r2l_fwd3_stream_floats(n_block),
-                         (hipStream_t)stream);
+    return pack_layouts(true, params, n_block, wstream, 0, (hipStream_t)stream);
 }
 
 extern "C" int r2l_pack_backward(const float* params, int n_block, float* wstream, void* stream) {
     R2L_REQUIRE(params && wstream, "r2l_pack_backward: params / wstream is NULL");
     R2L_REQUIRE(n_block >= 0 && n_block <= R2L_MAX_BLOCKS, "r2l_pack_backward: n_block out of range");
-    hipLaunchKernelGGL(r2l_pack_bwd_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params, wstream, n_block);
-    R2L_CHECK(hipGetLastError());
-    hipLaunchKernelGGL(r2l_pack_bwd16_kernel, dim3(2048), dim3(256), 0, (hipStream_t)stream, params,
-                       wstream + r2l_bwd32_stream_floats(n_block), n_block);
-    R2L_CHECK(hipGetLastError());
-    const int rc = r2l_bwd3_pack(params, n_block, wstream + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block),
-                                 (hipStream_t)stream);
-    if (rc) return rc;
-    return r2l_bwd2_pack(params, n_block,
-                         wstream + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block) + r2l_bwd3_stream_floats(n_block),
-                         (hipStream_t)stream);
+    return pack_layouts(false, params, n_block, wstream, 0, (hipStream_t)stream);
 }

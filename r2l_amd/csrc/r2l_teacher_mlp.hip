@@ -5,7 +5,7 @@
 //   ->  Linear(283,128)+ReLU on [feature, dir-embedding]  ->  rgb = Linear(128,3)   ->  raw[point] = (r,g,b,sigma)
 // Same register-resident chain as the student (r2l_common.h): one wavefront = 32 consecutive sample points, exact-fp32
 // MFMA, weights pre-packed into ONE stream in consumption order (r2l_pack_teacher below).
-#include "r2l_common.h"
+#include "r2l_dispatch.h"
 
 #define T_W 256
 #define T_XYZ 63
@@ -363,6 +363,9 @@ int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream)
 int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream);
 static inline int64_t t_stream32_floats() { return (int64_t)TG_TOTAL * R2L_GROUP_FLOATS + R2L_STREAM_PAD; }
+// a teacher stream buffer = [fp32 groups | bf16x3 stages | fp16x2 stages + status words]
+static inline float* t_w3(const float* wstream) { return const_cast<float*>(wstream) + t_stream32_floats(); }
+static inline float* t_w2(const float* wstream) { return t_w3(wstream) + r2l_teacher3_stream_floats(); }
 
 extern "C" int64_t r2l_teacher_stream_floats(void) {
     return t_stream32_floats() + r2l_teacher3_stream_floats() + r2l_teacher2_stream_floats();
@@ -371,16 +374,16 @@ extern "C" int64_t r2l_teacher_stream_floats(void) {
 // the 16 status words of the fp16x2 teacher stream inside `wstream` (include/r2l_hip.h: range control, telemetry)
 extern "C" const unsigned* r2l_teacher_status_words(const float* wstream) {
     if (wstream == nullptr) return nullptr;
-    return r2l_teacher2_status(wstream + t_stream32_floats() + r2l_teacher3_stream_floats());
+    return r2l_teacher2_status(t_w2(wstream));
 }
 
 extern "C" int r2l_pack_teacher(const float* params, float* wstream, void* stream) {
     R2L_REQUIRE(params && wstream, "r2l_pack_teacher: tparams / wstream is NULL");
     hipLaunchKernelGGL(r2l_pack_teacher_kernel, dim3(512), dim3(256), 0, (hipStream_t)stream, params, wstream);
     R2L_CHECK(hipGetLastError());
-    const int rc = r2l_teacher3_pack(params, wstream + t_stream32_floats(), (hipStream_t)stream);
+    const int rc = r2l_teacher3_pack(params, t_w3(wstream), (hipStream_t)stream);
     if (rc) return rc;
-    return r2l_teacher2_pack(params, wstream + t_stream32_floats() + r2l_teacher3_stream_floats(), (hipStream_t)stream);
+    return r2l_teacher2_pack(params, t_w2(wstream), (hipStream_t)stream);
 }
 
 extern "C" int r2l_teacher_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
@@ -398,17 +401,15 @@ extern "C" int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, con
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
     a.raw = raw; a.n_pts = R * (int64_t)S; a.S = S;
     if (a.n_pts <= 0) return 0;
-    if (r2l_use_fwd2()) {  // default: 3 fp16 products per fp32 product, the bf16x3 kernel behind it as range-guard fallback
-        const float* w3 = wstream + t_stream32_floats();
-        const float* w2 = w3 + r2l_teacher3_stream_floats();
-        const int rc = r2l_teacher2_mlp(rays_o, rays_d, viewdirs, z, w2, params, raw, a.n_pts, S, (hipStream_t)stream);
+    const int arith = r2l_plan(cfg, a.n_pts, 0, false, false).arith_fwd;  // (a forward-only launch)
+    if (arith == R2L_ARITH_FP16X2) {  // default: 3 fp16 products per fp32 product, the bf16x3 kernel behind it as range-guard fallback
+        const int rc = r2l_teacher2_mlp(rays_o, rays_d, viewdirs, z, t_w2(wstream), params, raw, a.n_pts, S, (hipStream_t)stream);
         if (rc) return rc;
-        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, w3, params, raw, a.n_pts, S, (hipStream_t)stream,
-                                r2l_teacher2_status(w2) + F2S_GO);
+        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, a.n_pts, S, (hipStream_t)stream,
+                                r2l_teacher2_status(t_w2(wstream)) + F2S_GO);
     }
-    if (r2l_use_fwd3())  // R2L_NO_FWD2=1: fp32-exact products on the bf16 matrix pipe (R2L_NO_FWD3=1: fp32 MFMA)
-        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, wstream + t_stream32_floats(), params, raw, a.n_pts, S,
-                                (hipStream_t)stream, nullptr);
+    if (arith == R2L_ARITH_BF16X3)  // R2L_NO_FWD2=1: fp32-exact products on the bf16 matrix pipe (R2L_NO_FWD3=1: fp32 MFMA)
+        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, a.n_pts, S, (hipStream_t)stream, nullptr);
     const int64_t tiles = (a.n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     hipLaunchKernelGGL(r2l_teacher_mlp_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
     R2L_CHECK(hipGetLastError());

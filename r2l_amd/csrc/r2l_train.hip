@@ -8,6 +8,7 @@
 //                     contiguous 1 KiB pieces); one small kernel behind it packs the head / bias stages for the activation
 //                     scale and commits it.  Two launches instead of four (adam, pack_fwd2, commit, pack_bwd2) per step.
 #include "r2l_f2.h"
+#include "r2l_dispatch.h"
 
 struct R2LAdamK {
     float step_size, b1, b2, eps, sqrt_bc2, gscale;
@@ -144,9 +145,9 @@ extern "C" int r2l_adam_step_packed(float* params, const float* grads, float* ex
     const double bc1 = 1.0 - pow((double)beta1, (double)step);
     const double bc2 = 1.0 - pow((double)beta2, (double)step);
     const R2LAdamK k{lr / (float)bc1, beta1, beta2, eps, (float)sqrt(bc2), grad_scale};
-    float* w2f = wstream_fwd + r2l_fwd32_stream_floats(n_block) + r2l_fwd16_stream_floats(n_block) + r2l_fwd3_stream_floats(n_block);
-    float* w2b = wstream_bwd + r2l_bwd32_stream_floats(n_block) + r2l_bwd16_stream_floats(n_block) + r2l_bwd3_stream_floats(n_block);
-    unsigned* status = reinterpret_cast<unsigned*>(w2f + r2l_fwd2_status_offset(n_block));
+    float* w2f = r2l_fwd_streams(wstream_fwd, n_block).w2;
+    float* w2b = r2l_bwd_streams(wstream_bwd, n_block).w2;
+    unsigned* status = r2l_fwd_streams(wstream_fwd, n_block).status;
     hipLaunchKernelGGL(r2l_adam_pack_kernel, dim3((unsigned)(128 * n_block + AP_REST_WGS)), dim3(256), 0, (hipStream_t)stream, params,
                        grads, exp_avg, exp_avg_sq, n_block, k, skip_if, reinterpret_cast<unsigned short*>(w2f),
                        reinterpret_cast<unsigned short*>(w2b), status);

@@ -35,11 +35,11 @@ def merged_config(cfg):
 def arithmetic(cfg=None):
     """{'precision': 'fp16x2'|'bf16x3'|'fp32_mfma', 'dw_mode': 'fp16'|'exact'}: the arithmetic the launches made with `cfg`
     (an r2l_config, AUTO fields filled from DEFAULT_CONFIG) run on, AUTO resolved the way the library resolves it
-    (csrc/r2l_common.h r2l_use_fwd3 / r2l_use_fwd2 / r2l_use_trio16 / r2l_dw_exact: the R2L_NO_* / R2L_DW_EXACT environment
-    switches an AUTO field falls through to).  What the drivers log and store in the checkpoints they write."""
+    (csrc/r2l_dispatch.hip r2l_plan: arith_step / stash_mid, and the R2L_NO_* / R2L_DW_EXACT environment switches an AUTO
+    field falls through to).  What the drivers log and store in the checkpoints they write."""
     import os
     cfg = merged_config(cfg if cfg is not None else _lib.Config())
-    on = lambda k: os.environ.get(k, "")[:1] not in ("", "0")  # r2l_env_on
+    on = lambda k: os.environ.get(k, "")[:1] not in ("", "0")  # as r2l_dispatch.hip reads a switch
     names = {v: k for k, v in _lib.PRECISION.items()}
     if cfg.precision:
         prec = names[cfg.precision]

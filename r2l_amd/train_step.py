@@ -495,7 +495,7 @@ def bench(net, ps, a, world, rank, distributed, device, timed, flop_per_ray, pea
             # cooperative chains (r2l_coopf: one or two 32-ray tiles per workgroup), each workgroup streaming the 25 MB of
             # packed weights per chain from L2 — measured ~45 B/clk per CU, which is what bounds the small launches
             tiles = (n + 31) // 32
-            if nt == 3:  # mixed grid (csrc/r2l_coopf.h r2l_coopf_policy): one workgroup per CU
+            if nt == 3:  # mixed grid (csrc/r2l_dispatch.hip r2l_plan: coop_tiles): one workgroup per CU
                 n_cu = torch.cuda.get_device_properties(device).multi_processor_count
                 wgs = n_cu
                 path += "; chains: cooperative kernels, MIXED grid (%d two-tile + %d one-tile workgroups = one per CU), L2 weight " \

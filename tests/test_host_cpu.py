@@ -219,6 +219,29 @@ def test_dispatch_and_buffer_size_helpers(monkeypatch):
     assert lib.r2l_dw_slab_floats() == 256 * 2 * (256 * 256 + 256) + 64 * 256 * 1024 + 512 * 4 * 256 + 16
 
 
+def test_dispatch_matrix_matches_recorded(golden_dir):
+    """Every host-side dispatch answer (variant, coop tiles, forward layout without / with stash, backward layout, chain
+    segments) over the full matrix of environment switches x r2l_config fields x n_block x ray counts at every boundary of a
+    rule — 4 341 760 points — equals what the library answered BEFORE the launch plan (csrc/r2l_dispatch.h) replaced the
+    scattered predicates: tests/golden/dispatch_matrix.npz, recorded by tests/golden/gen_dispatch_matrix.py from a build of that
+    commit.  The walk is the generator's own, so the two cannot drift apart; no point is skipped."""
+    import importlib.util
+    from r2l_amd import _lib
+    spec = importlib.util.spec_from_file_location("gen_dispatch_matrix", os.path.join(golden_dir, "gen_dispatch_matrix.py"))
+    gen = importlib.util.module_from_spec(spec)
+    spec.loader.exec_module(gen)
+    with np.load(os.path.join(golden_dir, "dispatch_matrix.npz")) as z:
+        want, rays = z["matrix"], z["rays"]
+    assert want.shape == gen.SHAPE and want.dtype == np.int8 and tuple(int(n) for n in rays) == gen.RAYS
+    assert want.size // 6 == 4341760
+    before = {k: v for k, v in os.environ.items() if k.startswith("R2L_")}
+    got = gen.record(_lib.load(), _lib.Config)
+    assert {k: v for k, v in os.environ.items() if k.startswith("R2L_")} == before
+    wrong = np.argwhere((got != want).any(axis=-1))
+    first = [(tuple(int(i) for i in w), got[tuple(w)].tolist(), want[tuple(w)].tolist()) for w in wrong[:5]]
+    assert len(wrong) == 0, "%d of %d points differ; first (index, got, recorded): %s" % (len(wrong), want.size // 6, first)
+
+
 def test_options_readme_command(tmp_path):
     from r2l_amd.options import parse_args
     cfg = os.path.join(ROOT, "configs", "lego_noview.txt")

@@ -1,5 +1,5 @@
 """Step / forward time of the chain variants over N (GPU box): which N should switch from the cooperative fp16x2 kernels
-(one tile per workgroup, r2l_coopf) to the one-wave-per-tile ones (R2L_COOPF_MAX_RAYS, csrc/r2l_common.h); the 16-ray
+(one tile per workgroup, r2l_coopf) to the one-wave-per-tile ones (R2L_COOPF_MAX_RAYS, csrc/r2l_common.h; the rule: csrc/r2l_dispatch.hip); the 16-ray
 fp32-MFMA cooperative family for comparison (R2L_FORCE_VARIANT=coop16 by hand); coopf/1, coopf/2 = ray tiles per workgroup."""
 import os, sys, time
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
