@@ -327,6 +327,22 @@ int64_t r2l_ssim_partial_count(int H, int W, int C);
 int r2l_ssim(const float* img1, const float* img2, int H, int W, int C, const float* window_host, float* partial,
              float* out, void* stream);
 
+/* out[k] = mean over the pixels of frame k of the FLIP difference map of img_a[k] against img_b[k]: utils/flip_loss.py:70-130
+ * (compute_flip: sRGB -> YCxCz, spatial CSF filters, L*a*b* + Hunt, HyAB^0.7 redistributed with pc 0.4 / pt 0.95 and
+ * cmax = HyAB(green, blue)^0.7; edge and point detectors on Y; per pixel dE_c^(1 - dE_f)), replicate padding, fused into
+ * one kernel + a fixed-order finish (no float atomics: bit-reproducible).  The function is symmetric in its two images.
+ * img_a/img_b: device [K, H, W, 3] fp32 (the layout render_path holds, no permute); values are clamped to [0,1] first, as the
+ * reference clamps them.  pixels_per_degree: main.py:373-377's standard is 0.7 * (3840 / 0.7) * pi / 180 = 67.02; the filter
+ * radii ceil(0.13505 * ppd) and ceil(0.123 * ppd) are derived from it and must not exceed the compiled 10 and 9:
+ * supported 0 < ppd <= 73.1, anything else is hipErrorInvalidValue.  rescale_dev: NULL (plain FLIP) or a device pointer to
+ * {min_a, max_a, min_b, max_b}: each image is first mapped by 2 / (max - min) * (x - min) - 1, the [-1, 1] rescale that
+ * main.py:361-363 applies to the whole stack before FLIP (a device pointer: the caller needs no host sync for the extrema).
+ * map: NULL or device [K, H, W], receives the per-pixel value.  partial: device scratch of r2l_flip_partial_count(H, W, K)
+ * floats.  Filter taps and constants are built on the host in double per call and passed by value. */
+int64_t r2l_flip_partial_count(int H, int W, int K);
+int r2l_flip(const float* img_a, const float* img_b, int K, int H, int W, float pixels_per_degree,
+             const float* rescale_dev, float* partial, float* map, float* out, void* stream);
+
 /* ---- hard-ray pool (training data path) ---------------------------------------------------------------------------------
  * The three data movements of main.py:1325-1347 (n_hard_out random pool rows [o, d, rgb] appended to every batch) and
  * main.py:1410-1425 (the hard rays of the step enter the pool, appended until it is full, then replacing the rows that were

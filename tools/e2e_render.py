@@ -1,4 +1,4 @@
-"""Wall-clock of the test-set evaluation loop (driver.render_path: render + PSNR + SSIM + PNG writing of prediction and
+"""Wall-clock of the test-set evaluation loop (driver.render_path: render + PSNR + SSIM + FLIP + PNG writing of prediction and
 ground truth) on 40 synthetic 400x400 views, W256 D88."""
 import argparse
 import os
@@ -44,8 +44,8 @@ def main(n=40):
         _, misc = driver.render_path(poses, net, ps, dev, _Log(), gt_imgs=gts, savedir=sd)
         torch.cuda.synchronize()
         dt = time.perf_counter() - t0
-        print("%-15s: %.1f ms/frame (%d frames, psnr %.3f ssim %.4f)" % (tag, dt * 1e3 / n, n, misc["test_psnr"].item(),
-                                                                      misc["test_ssim"].item()))
+        print("%-15s: %.1f ms/frame (%d frames, psnr %.3f ssim %.4f flip %.4f)" %
+              (tag, dt * 1e3 / n, n, misc["test_psnr"].item(), misc["test_ssim"].item(), misc["test_flip"].item()))
     print("files:", len(os.listdir(out)))
 
 
