@@ -317,6 +317,53 @@ int r2l_raw2outputs(const float* raw, const float* z, const float* rays_d, const
 int r2l_sample_pdf_sort(const float* z, const float* weights, const float* u, int64_t u_stride, float* z_samples,
                         float* z_all, float* z_std, int64_t R, int S, int NI, void* stream);
 
+/* ---- teacher frames from camera poses (one library call per group of frames) ------------------------------------------------
+ * What r2l_amd/render.py assembles per pose from the stages above, behind the C ABI: a host that binds this header renders a
+ * teacher frame from a pose without re-implementing the ray set-up or the random draws (csrc/r2l_teacher_frame.hip).
+ *
+ * out[i] = (w >> 8) * 2^-24 in [0,1), w = word (i & 3) of Philox4x32-10 with
+ * counter = { lo32(i>>2), hi32(i>>2), lo32(stream_id), hi32(stream_id) },
+ * key = { lo32(seed), hi32(seed) }.  Pure function of (seed, stream_id, i). */
+int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
+
+/* Rays of K whole frames (helpers:231-257 get_rays + the viewdirs of create_data.py:138-147), one launch.
+ * Ray r = (k*H + row)*W + col.  focal_dev: K device floats or NULL (focal for all).
+ * Any of rays_o / rays_d / viewdirs [K*H*W,3] and rows [K*H*W,9] may be NULL; rows gets columns 0..5 = o, d.
+ * Separately rounded fp32, in this order:  dirs = ((col - W*0.5)/focal, -(row - H*0.5)/focal, -1);
+ * d_i = (dirs_x*R_i0 + dirs_y*R_i1) + dirs_z*R_i2;  o_i = c2w[i][3];  viewdirs = d / sqrt((d_x^2 + d_z^2) + d_y^2)
+ * (the association torch.norm(d, dim=-1) uses on the GPU for a 3-vector: render() normalising these rays_d gives the same bits). */
+int r2l_frame_rays(const float* c2w_dev /*[K][3][4]*/, const float* focal_dev, float focal, int K, int H, int W,
+                   float* rays_o, float* rays_d, float* viewdirs, float* rows, void* stream);
+
+typedef struct r2l_teacher_frame_desc {
+    int H, W; float focal; float near, far;
+    int N_samples, N_importance;   /* N_importance 0: coarse pass only; with N_importance > 0: 3 <= N_samples <= 64,
+                                      N_importance <= 192 (r2l_sample_pdf_sort); N_samples + N_importance <= 256 */
+    int perturb;                   /* 0 | 1 */
+    int white_bkgd; float raw_noise_std;   /* raw_noise_std must be 0 */
+    int chunk_rays;                /* 0: a whole frame per pass */
+    uint64_t seed, frame_id0;      /* draws of frame k: t_rand stream_id = 2*(frame_id0+k), u stream_id = 2*(frame_id0+k)+1 */
+    int reserved[4];               /* must be 0 */
+} r2l_teacher_frame_desc;
+
+/* Frame k = render(H, W, focal_k, c2w = c2w_k, ndc = False, near, far, use_viewdirs = True, ...) of create_data.py:97-176:
+ * r2l_frame_rays, r2l_stratified_z, coarse r2l_teacher_mlp_cfg, r2l_raw2outputs (with weights), r2l_sample_pdf_sort, fine
+ * r2l_teacher_mlp_cfg, r2l_raw2outputs — those very kernels, enqueued on `stream` with no allocation and no host
+ * synchronisation; frames (and passes of chunk_rays rays within a frame) run back to back through `work`, 16-byte aligned,
+ * r2l_teacher_frames_work_floats(d) floats (-1 for an invalid descriptor), sized for min(chunk_rays or H*W, H*W) rays.
+ * perturb == 1: t_rand[r, s] and u[r, i] are r2l_draw_uniform elements r*N_samples + s and r*N_importance + i (r: ray within
+ * its frame) of the frame's two streams, so the outputs do not depend on the grouping into calls or on chunk_rays.
+ * perturb == 0: no t_rand; u_det is the one shared row of uniforms (u_stride 0).  rows[:, 6:9] receives rgb.  rgb0 (the coarse
+ * pass's rgb) is written only when N_importance > 0.  K == 0 is a successful no-op. */
+int64_t r2l_teacher_frames_work_floats(const r2l_teacher_frame_desc* d);
+int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                           const float* ttab /*dev [2*N_samples], as r2l_stratified_z*/,
+                           const float* u_det /*dev [N_importance], used when perturb == 0*/,
+                           const float* wstream_coarse, const float* tparams_coarse,
+                           const float* wstream_fine, const float* tparams_fine /*NULL pair: coarse net serves both passes*/,
+                           float* rows /*[K*H*W,9] o,d,rgb or NULL*/, float* rgb, float* disp, float* acc, float* depth,
+                           float* rgb0 /*each [K*H*W(,3)] or NULL*/, float* work, void* stream, const r2l_config* cfg);
+
 /* ---- test-set metric ------------------------------------------------------------------------------------------------
  * out[0] = SSIM(img1, img2): utils/ssim_torch.py:28-56,86-94 as called at main.py:46,254,334 (11x11 Gaussian sigma 1.5,
  * zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over every pixel and channel), fused into one kernel + a fixed-order

@@ -28,6 +28,16 @@ DW_MODE = {"auto": 0, "fp16": 1, "exact": 2}
 _cfgp = ctypes.POINTER(Config)
 
 
+class TeacherFrameDesc(ctypes.Structure):
+    """r2l_teacher_frame_desc of include/r2l_hip.h (r2l_teacher_frames_cfg)."""
+    _fields_ = [("H", _i), ("W", _i), ("focal", _f), ("near", _f), ("far", _f), ("N_samples", _i), ("N_importance", _i),
+                ("perturb", _i), ("white_bkgd", _i), ("raw_noise_std", _f), ("chunk_rays", _i), ("seed", ctypes.c_uint64),
+                ("frame_id0", ctypes.c_uint64), ("reserved", _i * 4)]
+
+
+_descp = ctypes.POINTER(TeacherFrameDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -93,6 +103,10 @@ SIGNATURES = {
     "r2l_stratified_z": (_i, [_p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "r2l_raw2outputs": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_sample_pdf_sort": (_i, [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _p]),
+    "r2l_draw_uniform": (_i, [_p, _l, ctypes.c_uint64, ctypes.c_uint64, _p]),
+    "r2l_frame_rays": (_i, [_p, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p]),
+    "r2l_teacher_frames_work_floats": (_l, [_descp]),
+    "r2l_teacher_frames_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 14 + [_cfgp]),
     "r2l_ssim_partial_count": (_l, [_i, _i, _i]),
     "r2l_ssim": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "r2l_flip_partial_count": (_l, [_i, _i, _i]),

@@ -3,7 +3,8 @@
 random poses; the rays [o, d, rgb] are shuffled and written as data_<k>.npy shards of 4096 rays.
 
 Per pose the whole stack runs on the GPU through libr2l_hip.so: get_rays -> stratified z -> fused embed+MLP (coarse)
--> raw2outputs -> sample_pdf + sort -> fused embed+MLP (fine) -> raw2outputs.  Poses are partitioned over ranks
+-> raw2outputs -> sample_pdf + sort -> fused embed+MLP (fine) -> raw2outputs (assembled per pose by render(), or with
+--r2l_fused_frames per flush group inside the library: render_frames).  Poses are partitioned over ranks
 (i % world == rank) with rank-disjoint shard indices and NO collective; each rank uses its own
 RandomState, so the reference's single global np.random replay is distributional, not bitwise.
 """
@@ -19,11 +20,11 @@ import torch
 
 from . import data as D
 from .checkpoint import load_weights
-from .driver import apply_arithmetic, init_distributed, sync
+from .driver import _runs, apply_arithmetic, init_distributed, sync
 from .logger import Logger
 from .nerf_raybased import NeRF
 from .options import parse_args, validate_accelerated
-from .render import get_embedder, get_rays, render, run_network
+from .render import get_embedder, get_rays, render, render_frames, run_network
 
 
 def create_teacher(args, device):
@@ -111,7 +112,8 @@ def main(argv=None):
         images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:]) if args.white_bkgd else images[..., :3]
         kw_test = dict(kwargs, perturb=args.perturb_test, raw_noise_std=0., near=near, far=far)
         _, misc = render_path(poses[i_split[2]], coarse, None, device, logger, gt_imgs=images[i_split[2]], rank=rank, world=world,
-                              teacher=dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kw_test, render_factor=args.render_factor))
+                              teacher=dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kw_test, render_factor=args.render_factor,
+                                           fused=args.r2l_fused_frames))
         logger.info("Teacher test: Loss %.4f PSNR %.4f" % (misc["test_loss"].item(), misc["test_psnr"].item()))
 
     datadir_new = args.datadir_kd.split(":")[-1]
@@ -160,9 +162,52 @@ def main(argv=None):
     th = threading.Thread(target=writer, daemon=True)
     th.start()
     t0, n_rays, k, filled = time.time(), 0, 0, 0
+
+    def flush(k, filled, next_index, j):
+        """Hand staging buffer k to the writer; returns (k, filled, next_index) of the next flush group."""
+        sync(device)  # the staged rows have landed
+        if errors:
+            raise errors[0]
+        free[k].clear()
+        jobs.put((stage[k][:filled].numpy(), int(rng.randint(0, 2**31 - 1)), next_index, k))
+        next_index += filled // rays_per_file
+        dt = time.time() - t0
+        logger.info("[%d/%d poses on rank %d] %d rays in %.1fs = %.0f rays/s; shards up to data_%d.npy" %
+                    (j, len(mine), rank, n_rays, dt, n_rays / dt, next_index - 1))
+        return 1 - k, 0, next_index
+
+    fused = bool(args.r2l_fused_frames)
+    if fused and device.type != "cuda":
+        raise NotImplementedError("--r2l_fused_frames renders through libr2l_hip.so: it needs a GPU")
+    if fused and (args.lindisp or args.raw_noise_std or not args.use_viewdirs):
+        raise NotImplementedError("--r2l_fused_frames: lindisp, raw_noise_std > 0 and use_viewdirs=False are outside the fused path")
+    logger.info("teacher frames: " + ("fused, one library call per flush group of %d poses (render_frames)" % chunk_poses if fused
+                                      else "render() per pose"))
+    group = []  # fused: (pose number, pose, focal) of the flush group being collected
     for j, i in enumerate(mine, 1):
-        pose = D.get_rand_pose(rng).to(device)
+        pose = D.get_rand_pose(rng)
         focal_ = focal * (1 + rng.rand()) if args.use_rand_focal else focal  # focal x U[1,2) (create_data.py:816)
+        if fused:
+            # same draws in the same order as below (pose, focal scale, ..., then the flush seed); the frames of the group are
+            # rendered when it is complete: one library call (per run of consecutive pose numbers), one copy to the host
+            group.append((i, pose[:3, :4], focal_))
+            n_rays += H * W
+            if j % chunk_poses == 0 or j == len(mine):
+                ids = [g[0] for g in group]
+                c2ws = torch.stack([g[1] for g in group], 0).to(device)
+                focals = torch.tensor([g[2] for g in group], dtype=torch.float32, device=device)
+                with torch.no_grad():
+                    parts = [render_frames(c2ws[a:a + n], H, W, focals[a:a + n], near, far, coarse, fine, args.N_samples,
+                                           args.N_importance, args.perturb, args.white_bkgd, seed=1000003 * rank,
+                                           frame_id0=ids[a], rows=True)["rows"]  # (a whole frame per pass, as below)
+                             for a, n in _runs(ids)]
+                filled = len(group) * H * W
+                free[k].wait()  # the flush that last used this buffer has been written
+                stage[k][:filled].copy_(parts[0] if len(parts) == 1 else torch.cat(parts, 0), non_blocking=True)
+                group = []
+                k, filled, next_index = flush(k, filled, next_index, j)
+            continue
+        pose = pose.to(device)
         # whole frame per launch on the GPU: --chunk (32 768 rays in the reference's configs) is a memory work-around of
         # the op-by-op path; the fused kernels need 0.5 GB of scratch for a 400x400 frame at 192 samples
         chunk = max(args.chunk, H * W) if device.type == "cuda" else args.chunk
@@ -173,16 +218,7 @@ def main(argv=None):
         filled += H * W
         n_rays += H * W
         if j % chunk_poses == 0 or j == len(mine):
-            sync(device)  # the staged rows have landed
-            if errors:
-                raise errors[0]
-            free[k].clear()
-            jobs.put((stage[k][:filled].numpy(), int(rng.randint(0, 2**31 - 1)), next_index, k))
-            next_index += filled // rays_per_file
-            k, filled = 1 - k, 0
-            dt = time.time() - t0
-            logger.info("[%d/%d poses on rank %d] %d rays in %.1fs = %.0f rays/s; shards up to data_%d.npy" %
-                        (j, len(mine), rank, n_rays, dt, n_rays / dt, next_index - 1))
+            k, filled, next_index = flush(k, filled, next_index, j)
     jobs.put(None)
     th.join()
     if errors:

@@ -1,0 +1,259 @@
+// r2l_teacher_frame.hip — teacher frames from camera poses in one library call (include/r2l_hip.h "teacher frames").
+//   r2l_frame_rays        : get_rays (utils/run_nerf_raybased_helpers.py:231-257) + the viewdirs of
+//                           create_data.py:138-147 for K whole frames, one launch
+//   r2l_draw_uniform      : counter-based uniforms (Philox4x32-10), a pure function of (seed, stream_id, element index): every
+//                           host of the C ABI draws the same t_rand / u, whatever its grouping of frames or chunks of rays
+//   r2l_teacher_frames_cfg: rays -> stratified z -> coarse MLP -> raw2outputs -> sample_pdf + sort -> fine MLP -> raw2outputs,
+//                           the EXISTING kernels of those stages enqueued back to back on the caller's stream through one work
+//                           buffer the caller sized once: no allocation, no host synchronisation
+// The three kernels here move 12 - 72 bytes per ray: a thread per ray (per Philox block of four draws), no LDS.
+#include "r2l_dispatch.h"
+#include <math.h>
+
+namespace {
+
+// ---- Philox4x32-10 (Salmon et al., "Parallel random numbers: as easy as 1, 2, 3", SC'11) ---------------------------------
+__device__ __forceinline__ void philox4x32_10(unsigned (&c)[4], unsigned k0, unsigned k1) {
+#pragma unroll
+    for (int r = 0; r < 10; ++r) {
+        const unsigned hi0 = __umulhi(0xD2511F53u, c[0]), lo0 = 0xD2511F53u * c[0];
+        const unsigned hi1 = __umulhi(0xCD9E8D57u, c[2]), lo1 = 0xCD9E8D57u * c[2];
+        const unsigned n0 = hi1 ^ c[1] ^ k0, n2 = hi0 ^ c[3] ^ k1;
+        c[0] = n0; c[1] = lo1; c[2] = n2; c[3] = lo0;
+        k0 += 0x9E3779B9u; k1 += 0xBB67AE85u;
+    }
+}
+
+// out[j] = uniform of element i0 + j, j < n.  Thread t owns Philox block (i0 >> 2) + t = elements 4 b .. 4 b + 3.
+__global__ void r2l_draw_uniform_kernel(float* __restrict__ out, int64_t n, int64_t i0, unsigned long long seed,
+                                        unsigned long long stream_id) {
+    const int64_t b0 = i0 >> 2, nb = ((i0 + n + 3) >> 2) - b0;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nb; t += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long b = (unsigned long long)(b0 + t);
+        unsigned c[4] = {(unsigned)b, (unsigned)(b >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32)};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int64_t j = (int64_t)(b << 2) + w - i0;
+            if (j >= 0 && j < n) out[j] = (float)(c[w] >> 8) * 5.9604644775390625e-08f;  // 2^-24: exact, in [0, 1)
+        }
+    }
+}
+
+// Rays first .. first + n of the K*H*W rays of K frames (ray r = (k*H + row)*W + col); outputs are indexed by r - first.
+// Separately rounded fp32 in the order of include/r2l_hip.h (the build passes -ffp-contract=off).
+__global__ void r2l_frame_rays_kernel(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H, int W,
+                                      int64_t first, int64_t n, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                      float* __restrict__ viewdirs, float* __restrict__ rows, float* __restrict__ nearfar, float near,
+                                      float far) {
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = first + j, k = r / hw, pix = r - k * hw;
+        const int row = (int)(pix / W), col = (int)(pix - (int64_t)row * W);
+        const float* c = c2w + k * 12;
+        const float f = focal_dev != nullptr ? focal_dev[k] : focal;
+        const float dx = ((float)col - (float)W * .5f) / f, dy = -(((float)row - (float)H * .5f) / f), dz = -1.f;
+        float o[3], d[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            d[i] = (dx * c[i * 4 + 0] + dy * c[i * 4 + 1]) + dz * c[i * 4 + 2];
+            o[i] = c[i * 4 + 3];
+        }
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            if (rays_o != nullptr) rays_o[j * 3 + i] = o[i];
+            if (rays_d != nullptr) rays_d[j * 3 + i] = d[i];
+            if (rows != nullptr) { rows[j * 9 + i] = o[i]; rows[j * 9 + 3 + i] = d[i]; }
+        }
+        if (viewdirs != nullptr) {
+            // (x^2 + z^2) + y^2: the association of torch.norm's reduction over a 3-vector, so that render()'s own
+            // normalisation of these rays_d gives these bits (tests/test_teacher_frames_gpu.py: fused = unfused)
+            const float nrm = sqrtf((d[0] * d[0] + d[2] * d[2]) + d[1] * d[1]);
+#pragma unroll
+            for (int i = 0; i < 3; ++i) viewdirs[j * 3 + i] = d[i] / nrm;
+        }
+        if (nearfar != nullptr && j == 0) { nearfar[0] = near; nearfar[1] = far; }
+    }
+}
+
+// rows[r, 6:9] = rgb[r, :]
+__global__ void r2l_rows_rgb_kernel(const float* __restrict__ rgb, float* __restrict__ rows, int64_t n) {
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < n * 3; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t r = e / 3;
+        rows[r * 9 + 6 + (e - r * 3)] = rgb[e];
+    }
+}
+
+unsigned grid_for(int64_t total) {
+    const int64_t g = (total + 255) / 256;
+    return (unsigned)(g < 1 ? 1 : (g > 4096 ? 4096 : g));
+}
+
+int launch_draw(float* out, int64_t n, int64_t i0, uint64_t seed, uint64_t stream_id, hipStream_t stream) {
+    hipLaunchKernelGGL(r2l_draw_uniform_kernel, dim3(grid_for((n + 3) / 4 + 1)), dim3(256), 0, stream, out, n, i0,
+                       (unsigned long long)seed, (unsigned long long)stream_id);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+int launch_rays(const float* c2w, const float* focal_dev, float focal, int H, int W, int64_t first, int64_t n, float* rays_o,
+                float* rays_d, float* viewdirs, float* rows, float* nearfar, float near, float far, hipStream_t stream) {
+    hipLaunchKernelGGL(r2l_frame_rays_kernel, dim3(grid_for(n)), dim3(256), 0, stream, c2w, focal_dev, focal, H, W, first, n, rays_o,
+                       rays_d, viewdirs, rows, nearfar, near, far);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// What is wrong with a descriptor, or nullptr
+const char* desc_check(const r2l_teacher_frame_desc* d) {
+    if (d == nullptr) return "r2l_teacher_frame_desc: desc is NULL";
+    if (d->H < 1 || d->W < 1) return "r2l_teacher_frame_desc.H / .W: need H >= 1 and W >= 1";
+    if (!(d->near < d->far)) return "r2l_teacher_frame_desc.near / .far: need near < far";
+    if (d->N_samples < 1) return "r2l_teacher_frame_desc.N_samples: need N_samples >= 1";
+    if (d->N_importance < 0) return "r2l_teacher_frame_desc.N_importance: need N_importance >= 0";
+    if (d->N_importance > 0 && d->N_samples < 3) return "r2l_teacher_frame_desc.N_samples: need N_samples >= 3 with N_importance > 0";
+    if ((int64_t)d->N_samples + d->N_importance > 256) return "r2l_teacher_frame_desc.N_samples + .N_importance: at most 256";
+    if (d->N_importance > 0 && (d->N_samples > 64 || d->N_importance > 192))
+        return "r2l_teacher_frame_desc.N_samples / .N_importance: r2l_sample_pdf_sort needs N_samples <= 64 and N_importance <= 192";
+    if (d->perturb != 0 && d->perturb != 1) return "r2l_teacher_frame_desc.perturb: 0 or 1";
+    if (d->raw_noise_std != 0.f) return "r2l_teacher_frame_desc.raw_noise_std: must be 0";
+    if (d->chunk_rays < 0) return "r2l_teacher_frame_desc.chunk_rays: need chunk_rays >= 0";
+    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return "r2l_teacher_frame_desc.reserved: must be 0";
+    return nullptr;
+}
+
+// The work buffer: every part starts on a 16-byte boundary (the quarter-wave kernels of r2l_render.hip take aligned pointers)
+struct FrameWork {
+    int64_t nearfar, o, d, v, z, raw, wts, zs, zall, trand, u, rgb_c, s_c, rgb_f, s_f, total;
+};
+int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }
+FrameWork frame_work(const r2l_teacher_frame_desc* d) {
+    const int64_t hw = (int64_t)d->H * d->W;
+    const int64_t cr = d->chunk_rays > 0 && d->chunk_rays < hw ? d->chunk_rays : hw;
+    const int64_t S = d->N_samples, NI = d->N_importance, T = S + NI;
+    FrameWork w{};
+    int64_t at = 0;
+    auto take = [&](int64_t n) { const int64_t a = at; at += r4(n); return a; };
+    w.nearfar = take(2);
+    w.o = take(cr * 3); w.d = take(cr * 3); w.v = take(cr * 3);
+    w.z = take(cr * S);
+    w.raw = take(cr * T * 4);
+    w.wts = take(NI > 0 ? cr * S : 0);
+    w.zs = take(cr * NI);
+    w.zall = take(NI > 0 ? cr * T : 0);
+    w.trand = take(d->perturb ? cr * S : 0);
+    w.u = take(d->perturb ? cr * NI : 0);
+    w.rgb_c = take(cr * 3); w.s_c = take(r4(cr) * 3);  // coarse rgb0 | disp0, acc0, depth0
+    w.rgb_f = take(cr * 3); w.s_f = take(r4(cr) * 3);  // stand-ins for final outputs the caller passed as NULL
+    w.total = at;
+    return w;
+}
+
+}  // namespace
+
+extern "C" int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
+    R2L_REQUIRE(n >= 0, "r2l_draw_uniform: n is negative");
+    if (n == 0) return 0;
+    R2L_REQUIRE(out != nullptr, "r2l_draw_uniform: out is NULL");
+    return launch_draw(out, n, 0, seed, stream_id, (hipStream_t)stream);
+}
+
+extern "C" int r2l_frame_rays(const float* c2w_dev, const float* focal_dev, float focal, int K, int H, int W, float* rays_o,
+                              float* rays_d, float* viewdirs, float* rows, void* stream) {
+    R2L_REQUIRE(K >= 0, "r2l_frame_rays: K is negative");
+    R2L_REQUIRE(H >= 1 && W >= 1, "r2l_frame_rays: need H >= 1 and W >= 1");
+    R2L_REQUIRE(focal_dev != nullptr || focal > 0.f, "r2l_frame_rays: need focal > 0 (or focal_dev)");
+    if (K == 0) return 0;
+    R2L_REQUIRE(c2w_dev != nullptr, "r2l_frame_rays: c2w_dev is NULL");
+    if (!rays_o && !rays_d && !viewdirs && !rows) return 0;
+    return launch_rays(c2w_dev, focal_dev, focal, H, W, 0, (int64_t)K * H * W, rays_o, rays_d, viewdirs, rows, nullptr, 0.f, 0.f,
+                       (hipStream_t)stream);
+}
+
+extern "C" int64_t r2l_teacher_frames_work_floats(const r2l_teacher_frame_desc* d) {
+    if (const char* why = desc_check(d)) {
+        r2l_set_error_msg(why);
+        return -1;
+    }
+    return frame_work(d).total;
+}
+
+extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                                      const float* ttab, const float* u_det, const float* wstream_coarse, const float* tparams_coarse,
+                                      const float* wstream_fine, const float* tparams_fine, float* rows, float* rgb, float* disp,
+                                      float* acc, float* depth, float* rgb0, float* work, void* stream, const r2l_config* cfg) {
+    if (const char* why = desc_check(d)) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    R2L_CFG_ENTER(cfg);
+    R2L_REQUIRE(K >= 0, "r2l_teacher_frames_cfg: K is negative");
+    R2L_REQUIRE((wstream_fine == nullptr) == (tparams_fine == nullptr),
+                "r2l_teacher_frames_cfg: wstream_fine / tparams_fine: both or neither (NULL pair: the coarse net serves both passes)");
+    R2L_REQUIRE(d->perturb != 0 || d->N_importance == 0 || u_det != nullptr,
+                "r2l_teacher_frames_cfg: u_det is NULL (needed with perturb == 0 and N_importance > 0)");
+    R2L_REQUIRE(focal_dev != nullptr || d->focal > 0.f, "r2l_teacher_frames_cfg: need r2l_teacher_frame_desc.focal > 0 (or focal_dev)");
+    if (K == 0) return 0;
+    R2L_REQUIRE(c2w_dev && ttab && wstream_coarse && tparams_coarse && work,
+                "r2l_teacher_frames_cfg: a required pointer is NULL (c2w_dev, ttab, wstream_coarse, tparams_coarse, work)");
+    R2L_REQUIRE(((uintptr_t)work & 15) == 0, "r2l_teacher_frames_cfg: work must be 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const int S = d->N_samples, NI = d->N_importance, T = S + NI;
+    const int64_t hw = (int64_t)d->H * d->W;
+    const int64_t cr_max = d->chunk_rays > 0 && d->chunk_rays < hw ? d->chunk_rays : hw;
+    const FrameWork w = frame_work(d);
+    float* const nf = work + w.nearfar;
+    float *const o = work + w.o, *const dd = work + w.d, *const v = work + w.v, *const z = work + w.z, *const raw = work + w.raw;
+    const float* wfine = wstream_fine ? wstream_fine : wstream_coarse;
+    const float* pfine = tparams_fine ? tparams_fine : tparams_coarse;
+    int rc;
+    for (int k = 0; k < K; ++k) {
+        const uint64_t fid = d->frame_id0 + (uint64_t)k;
+        for (int64_t r0 = 0; r0 < hw; r0 += cr_max) {
+            const int64_t cr = hw - r0 < cr_max ? hw - r0 : cr_max;
+            const int64_t g = (int64_t)k * hw + r0;  // first ray of this pass among the K*H*W
+            // final outputs of this pass: the caller's arrays, or stand-ins in the work buffer
+            float* f_rgb = rgb ? rgb + g * 3 : work + w.rgb_f;
+            float* f_disp = disp ? disp + g : work + w.s_f;
+            float* f_acc = acc ? acc + g : work + w.s_f + r4(cr_max);
+            float* f_depth = depth ? depth + g : work + w.s_f + 2 * r4(cr_max);
+            if ((rc = launch_rays(c2w_dev, focal_dev, d->focal, d->H, d->W, g, cr, o, dd, v, rows ? rows + g * 9 : nullptr, nf, d->near,
+                                  d->far, st)))
+                return rc;
+            float* t_rand = nullptr;
+            if (d->perturb) {
+                t_rand = work + w.trand;
+                if ((rc = launch_draw(t_rand, cr * S, r0 * S, d->seed, 2 * fid, st))) return rc;
+            }
+            if ((rc = r2l_stratified_z(nf, nf + 1, 0, ttab, t_rand, z, cr, S, stream))) return rc;
+            if ((rc = r2l_teacher_mlp_cfg(o, dd, v, z, wstream_coarse, tparams_coarse, raw, cr, S, stream, cfg))) return rc;
+            if (NI == 0) {
+                if ((rc = r2l_raw2outputs(raw, z, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, S, stream)))
+                    return rc;
+            } else {
+                float* c_rgb = rgb0 ? rgb0 + g * 3 : work + w.rgb_c;
+                float* c_s = work + w.s_c;
+                if ((rc = r2l_raw2outputs(raw, z, dd, nullptr, d->white_bkgd, c_rgb, c_s, c_s + r4(cr_max), work + w.wts,
+                                          c_s + 2 * r4(cr_max), cr, S, stream)))
+                    return rc;
+                const float* u = u_det;
+                if (d->perturb) {
+                    if ((rc = launch_draw(work + w.u, cr * NI, r0 * NI, d->seed, 2 * fid + 1, st))) return rc;
+                    u = work + w.u;
+                }
+                if ((rc = r2l_sample_pdf_sort(z, work + w.wts, u, d->perturb ? NI : 0, work + w.zs, work + w.zall, nullptr, cr, S, NI,
+                                              stream)))
+                    return rc;
+                if ((rc = r2l_teacher_mlp_cfg(o, dd, v, work + w.zall, wfine, pfine, raw, cr, T, stream, cfg))) return rc;
+                if ((rc = r2l_raw2outputs(raw, work + w.zall, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, T,
+                                          stream)))
+                    return rc;
+            }
+            if (rows != nullptr) {
+                hipLaunchKernelGGL(r2l_rows_rgb_kernel, dim3(grid_for(cr * 3)), dim3(256), 0, st, f_rgb, rows + g * 9, cr);
+                R2L_CHECK(hipGetLastError());
+            }
+        }
+    }
+    return 0;
+}

@@ -396,6 +396,16 @@ def _flip_sum(rgbs, gts, device, world):
     return total
 
 
+def _runs(idx):
+    """(start, length) of the runs of consecutive integers in idx: [3, 4, 5, 9] -> (0, 3), (3, 1)."""
+    out, k = [], 0
+    for j in range(1, len(idx) + 1):
+        if j == len(idx) or idx[j] != idx[j - 1] + 1:
+            out.append((k, j - k))
+            k = j
+    return out
+
+
 def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, savedir=None, rank=0, world=1, teacher=None):
     """Render poses[rank::world]; returns (rgbs [n,H,W,3], misc with test_loss/test_psnr/test_psnr_v2 over ALL frames)
     and test_ssim / test_flip — main.py:189-398 (LPIPS needs network weights that are absent: out of scope).  No host
@@ -405,7 +415,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
     teacher = None: the R2L branch (main.py:284-324), `model` = the student.
     teacher = dict(hwf=(H, W, focal), chunk=, render_kwargs=): the `model_name in ['nerf']` branch (main.py:275-282): every
     frame is render(H, W, focal, chunk, c2w=pose[:3,:4], **render_kwargs) of r2l_amd/render.py (coarse + fine NeRF on the
-    teacher kernels); `model` = render_kwargs['network_fn'], `point_sampler` unused."""
+    teacher kernels); `model` = render_kwargs['network_fn'], `point_sampler` unused.  With fused=True in that dict
+    (--r2l_fused_frames; GPU only) the frames come from render_frames in groups of POSES_PER_LAUNCH instead."""
     model.eval()
     mine = list(range(rank, len(poses), world))
     rgbs, gts, sq_err, psnrs, ssims, events, errors = [], [], [], [], [], [], []
@@ -441,7 +452,31 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
             H, W, focal = int(H / rf), int(W / rf), focal / rf
         # a whole frame per launch on the GPU (as create_data.main: --chunk is a memory work-around of the op-by-op path)
         chunk = max(int(teacher["chunk"]), H * W) if on_gpu else int(teacher["chunk"])
-        for i in mine:
+        fused = bool(teacher.get("fused"))
+        if fused and not on_gpu:
+            raise NotImplementedError("--r2l_fused_frames renders through libr2l_hip.so: it needs a GPU")
+        logger.info("teacher frames: " + ("fused, one library call per %d poses (render_frames)" % POSES_PER_LAUNCH if fused
+                                          else "render() per pose"))
+        if fused:  # groups of poses through r2l_teacher_frames_cfg, as the student branch below groups its frames
+            from .render import render_frames
+            kw = teacher["render_kwargs"]
+            if kw.get("lindisp") or kw.get("raw_noise_std", 0.) or not kw.get("use_viewdirs", True):
+                raise NotImplementedError("--r2l_fused_frames: lindisp, raw_noise_std > 0 and use_viewdirs=False are outside the fused path")
+            for g0 in range(0, len(mine), POSES_PER_LAUNCH):
+                idx = mine[g0:g0 + POSES_PER_LAUNCH]
+                e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+                e0.record()
+                c2ws = torch.stack([torch.as_tensor(poses[i], dtype=torch.float32)[:3, :4] for i in idx], 0).to(device)
+                with torch.no_grad():  # (draws of --perturb_test > 0: stream pair of frame i = its pose number, whatever the ranks)
+                    outs = [render_frames(c2ws[k:k + n], H, W, focal, kw["near"], kw["far"], kw["network_fn"], kw.get("network_fine"),
+                                          kw["N_samples"], kw.get("N_importance", 0), kw.get("perturb", 0.), kw.get("white_bkgd", False),
+                                          seed=int(teacher.get("seed", 0)), frame_id0=idx[k])["rgb"] for k, n in _runs(idx)]
+                frames = (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).view(len(idx), H, W, 3)
+                e1.record()
+                events.append((idx, e0, e1))
+                for k, i in enumerate(idx):
+                    account(i, frames[k])
+        for i in ([] if fused else mine):
             t0 = time.time()
             if on_gpu:
                 e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
@@ -541,7 +576,8 @@ def main(argv=None):
     if is_teacher:
         kwargs_test = create_nerf_teacher(args, device, logger, near, far)
         model, point_sampler = kwargs_test["network_fn"], None
-        teacher = dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kwargs_test, render_factor=args.render_factor)
+        teacher = dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kwargs_test, render_factor=args.render_factor,
+                       fused=args.r2l_fused_frames)
         history = {"start": 0, "best_psnr": 0, "best_psnr_step": 0}
         r2l_config = apply_arithmetic(args, device, logger, teachers=(model, kwargs_test["network_fine"]))
     else:

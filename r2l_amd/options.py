@@ -51,6 +51,9 @@ FLAGS = {
     # family every launch of the run uses.  auto = the library default (fp16x2 products, fp16 weight-gradient operands);
     # fp32_mfma = the reference's arithmetic (exact fp32 products and accumulation) — the graded numbers of bench.py
     "r2l_precision": (str, "auto"), "r2l_dw_mode": (str, "auto"),
+    # teacher frames (create_data, the teacher's test render) through ONE library call per group of poses
+    # (r2l_teacher_frames_cfg: rays, draws and all stages behind the C ABI) instead of render()'s per-pose assembly; opt-in
+    "r2l_fused_frames": ("flag", False),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),

@@ -372,3 +372,99 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
         all_ret[k] = all_ret[k].reshape(list(sh[:-1]) + list(all_ret[k].shape[1:]))
     main = ["rgb_map", "disp_map", "acc_map"]
     return [all_ret[k] for k in main] + [{k: v for k, v in all_ret.items() if k not in main}]
+
+
+# ---------------------------------------------------------------------------------------------------------------
+# teacher frames from poses in one library call (include/r2l_hip.h "teacher frames"; csrc/r2l_teacher_frame.hip)
+# ---------------------------------------------------------------------------------------------------------------
+def _need_gpu(t, what):
+    if not t.is_cuda:
+        raise NotImplementedError("%s runs on the GPU only (HIP kernels of libr2l_hip.so)" % what)
+
+
+def _pose_table(c2ws, device=None):
+    c2ws = torch.as_tensor(c2ws, dtype=torch.float32)
+    if c2ws.dim() == 2:
+        c2ws = c2ws[None]
+    if device is not None:
+        c2ws = c2ws.to(device)
+    return c2ws[:, :3, :4].contiguous()
+
+
+def _focals(focal, K, device):
+    """(focal_dev [K] or None, focal) of r2l_frame_rays / r2l_teacher_frames_cfg from a number or K per-frame values."""
+    if isinstance(focal, (int, float)):
+        return None, float(focal)
+    f = torch.as_tensor(focal, dtype=torch.float32).reshape(-1).to(device).contiguous()
+    if f.numel() != K:
+        raise ValueError("need one focal per frame: got %d for %d frames" % (f.numel(), K))
+    return f, 0.
+
+
+def frame_rays(c2ws, H, W, focal):
+    """(rays_o, rays_d, viewdirs), each [K*H*W, 3], of K whole frames in one launch (r2l_frame_rays): get_rays + the
+    normalised view directions of render().  c2ws [K,3|4,4] (or one pose) on the GPU; focal: a number or K per-frame values."""
+    c2ws = _pose_table(c2ws)
+    _need_gpu(c2ws, "frame_rays")
+    K = c2ws.shape[0]
+    fdev, f = _focals(focal, K, c2ws.device)
+    o, d, v = (torch.empty(K * H * W, 3, dtype=torch.float32, device=c2ws.device) for _ in range(3))
+    _lib.check(_lib.load().r2l_frame_rays(_ptr(c2ws), _ptr(fdev), f, K, H, W, _ptr(o), _ptr(d), _ptr(v), None, _stream()),
+               "r2l_frame_rays")
+    return o, d, v
+
+
+def draw_uniform(n, seed, stream_id, device):
+    """n uniforms in [0,1): elements 0..n-1 of the Philox4x32-10 stream (seed, stream_id) of r2l_draw_uniform."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NotImplementedError("draw_uniform runs on the GPU only (HIP kernels of libr2l_hip.so)")
+    out = torch.empty(int(n), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().r2l_draw_uniform(_ptr(out), int(n), int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1),
+                                                _stream()), "r2l_draw_uniform")
+    return out
+
+
+def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samples, N_importance, perturb, white_bkgd, seed,
+                  frame_id0=0, chunk=0, rows=False):
+    """K teacher frames from K poses in ONE library call (r2l_teacher_frames_cfg): what render(H, W, focal_k, c2w=c2ws[k],
+    ndc=False, near=, far=, use_viewdirs=True, ...) computes per pose, with the random draws of perturb > 0 made on the device
+    by draw_uniform (frame k: t_rand = stream 2*(frame_id0+k), u = stream 2*(frame_id0+k)+1 of `seed`).  GPU only.
+    focal: a number or K per-frame values; chunk: rays per pass (0: a whole frame); network_fine None: the coarse net serves
+    both passes.  Returns {'rgb' [K*H*W,3], 'disp', 'acc', 'depth' [K*H*W], 'rgb0' (None when N_importance == 0),
+    'rows' ([K*H*W,9] = [o, d, rgb] when rows=True, else None)}."""
+    c2ws = _pose_table(c2ws, next(network_fn.parameters()).device)
+    _need_gpu(c2ws, "render_frames")
+    dev = c2ws.device
+    K, R = c2ws.shape[0], c2ws.shape[0] * H * W
+    lib = _lib.load()
+    coarse = teacher_engine(network_fn)
+    fine = None if network_fine is None else teacher_engine(network_fine)
+    for e in (coarse, fine):
+        if e is not None:
+            e.ensure_packed()
+    fdev, f = _focals(focal, K, dev)
+    desc = _lib.TeacherFrameDesc(H=H, W=W, focal=f, near=near, far=far, N_samples=N_samples, N_importance=N_importance,
+                                 perturb=int(perturb > 0), white_bkgd=int(bool(white_bkgd)), raw_noise_std=0.,
+                                 chunk_rays=int(chunk), seed=int(seed) & (2**64 - 1), frame_id0=int(frame_id0) & (2**64 - 1))
+    n_work = lib.r2l_teacher_frames_work_floats(ctypes.byref(desc))
+    if n_work < 0:
+        _lib.check(1, "r2l_teacher_frames_work_floats")
+    work = getattr(coarse, "_frames_work", None)  # kept on the engine: frames of one size re-use it
+    if work is None or work.numel() < n_work or work.device != dev:
+        work = coarse._frames_work = torch.empty(n_work, dtype=torch.float32, device=dev)
+    # the tables of _coarse_z and sample_pdf_sort, by the same torch expressions
+    t = torch.linspace(0., 1., steps=N_samples)
+    ttab = torch.cat([t, 1. - t]).to(dev)
+    u_det = torch.linspace(0., 1., steps=N_importance).to(dev).float().contiguous() if N_importance > 0 else None
+    new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
+    out = {"rgb": new(R, 3), "disp": new(R), "acc": new(R), "depth": new(R), "rgb0": new(R, 3) if N_importance > 0 else None,
+           "rows": new(R, 9) if rows else None}
+    _lib.check(
+        lib.r2l_teacher_frames_cfg(_ptr(c2ws), _ptr(fdev), K, ctypes.byref(desc), _ptr(ttab), _ptr(u_det), _ptr(coarse.wstream),
+                                   _ptr(coarse.flat), _ptr(None if fine is None else fine.wstream),
+                                   _ptr(None if fine is None else fine.flat), _ptr(out["rows"]), _ptr(out["rgb"]),
+                                   _ptr(out["disp"]), _ptr(out["acc"]), _ptr(out["depth"]), _ptr(out["rgb0"]), _ptr(work),
+                                   _stream(), ctypes.byref(_engine.merged_config(coarse.cfg))), "r2l_teacher_frames_cfg")
+    return out
