@@ -409,6 +409,36 @@ int r2l_pool_store(const float* rays_o, const float* rays_d, const float* target
                    int64_t stride_t, const int64_t* hard, float* pool, const int64_t* dst_idx, int64_t dst0, int64_t n_in,
                    void* stream);
 
+/* ---- device-resident ray store (training data path without shard files) ---------------------------------------------------
+ * The teacher's [o, d, rgb] rows stay in device memory between their rendering and the student's steps, instead of being
+ * written as [4096,9] .npy shards (create_data.py:854-872) and read back (main.py:759-808).  The store is CALLER-OWNED memory:
+ * capacity_shards * rays_per_shard rows of 9 fp32, row-major; shard s is rows [s * rays_per_shard, (s+1) * rays_per_shard).
+ * Both calls are stateless, check their arguments before any launch, enqueue one kernel on `stream` and never synchronise.
+ * rays_per_shard must be a positive multiple of 4 (a shard is a whole number of 16-byte words); all offsets are 64-bit.
+ *
+ * pi(key, n) below is the bijection of [0, n) that the hard-ray pool's row choice evaluates (csrc/r2l_perm.h): with
+ * bits = the smallest even number >= 2 with 2^bits >= n, a 4-round Feistel network F on bits/2 + bits/2 bits, round function
+ * murmur3-finalizer(r ^ k[round]) masked to bits/2 bits, round keys k = mix(lo), mix(hi ^ 0x9e3779b9), mix(lo ^ 0x7f4a7c15),
+ * mix(hi + 0x6a09e667) of the key's low / high 32 bits; pi(i) = the first of F(i), F(F(i)), ... that is < n (cycle walking).
+ * epoch_key(seed, e) = the splitmix64 finalizer of seed + (e + 1) * 0x9E3779B97F4A7C15 (mod 2^64):
+ *   z ^= z >> 30; z *= 0xBF58476D1CE4E5B9; z ^= z >> 27; z *= 0x94D049BB133111EB; z ^= z >> 31.
+ * r2l_amd/raystore.py (perm, shard_ids) restates both in numpy.
+ *
+ *   r2l_store_append: writes m = floor(n_rows / rays_per_shard) shards starting at shard first_shard; output row i
+ *     (i < m * rays_per_shard) is input row pi(key, n_rows)(i), the remaining n_rows mod rays_per_shard rows of the permuted
+ *     sequence are dropped (create_data.py:862-872).  shuffle = 0: the identity instead of pi.  *n_written_out = m (host
+ *     arithmetic).  Needs first_shard + m <= capacity_shards.  rows_in: device [n_rows, 9] fp32, must not overlap the store.
+ *   r2l_store_batch: sampler and copy in one launch.  Draw t = draw0 + j, j < n_draw, takes shard
+ *     id = pi(epoch_key(seed, t / n_shards), n_shards)(t % n_shards) — a fresh permutation of the shards per epoch, without
+ *     replacement inside an epoch (the InfiniteSampler of main.py:759-767) — and copies it to rows
+ *     [j * rays_per_shard, (j+1) * rays_per_shard) of batch.  ids_out: device int32[n_draw] receiving the ids, or NULL.
+ *     A pure function of (seed, n_shards, t).  store and batch must be 16-byte aligned; n_shards >= 1 shards of the store are
+ *     read (the caller keeps n_shards within what it has filled). */
+int r2l_store_append(const float* rows_in, int64_t n_rows, float* store, int64_t capacity_shards, int64_t first_shard,
+                     int64_t rays_per_shard, uint64_t key, int shuffle, int64_t* n_written_out, void* stream);
+int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
+                    float* batch, int32_t* ids_out, void* stream);
+
 /* ---- frame writer (host threads; test-set evaluation) ------------------------------------------------------------------
  * Replaces `imageio.imwrite(filename, to8b(rgb))` of every prediction / ground-truth frame in render_path (main.py:337-344):
  * a pool of encoder threads (zlib, Sub filter; lossless, so the decoded pixels are the bytes handed over).  `pixels`: HOST

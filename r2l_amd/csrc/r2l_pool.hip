@@ -9,37 +9,15 @@
 // on the next even number of bits, cycle-walked back into the range — at i = 0 .. n_out-1.  A fresh key per step (host counter
 // through a mixer) gives a fresh permutation; distinctness is by construction.  HBM-bound trivia otherwise: 36 B per row.
 #include "r2l_common.h"
+#include "r2l_perm.h"
 
 namespace {
 
-__device__ __forceinline__ unsigned pool_mix(unsigned x) {  // murmur3 finalizer
-    x ^= x >> 16; x *= 0x85ebca6bu; x ^= x >> 13; x *= 0xc2b2ae35u; x ^= x >> 16;
-    return x;
-}
-// bijection of [0, 2^(2*half_bits)): 4 Feistel rounds with round keys k[r]
-__device__ __forceinline__ unsigned long long pool_feistel(unsigned long long x, int half_bits, const unsigned (&k)[4]) {
-    const unsigned mask = (1u << half_bits) - 1u;
-    unsigned l = (unsigned)(x >> half_bits) & mask, r = (unsigned)x & mask;
-#pragma unroll
-    for (int i = 0; i < 4; ++i) {
-        const unsigned f = pool_mix(r ^ k[i]) & mask;
-        const unsigned nl = r;
-        r = l ^ f;
-        l = nl;
-    }
-    return ((unsigned long long)l << half_bits) | r;
-}
-
 __global__ void r2l_pool_pick_kernel(int64_t* __restrict__ out, int64_t n_out, int64_t n_rows, int half_bits, unsigned long long key) {
-    const unsigned k[4] = {pool_mix((unsigned)key), pool_mix((unsigned)(key >> 32) ^ 0x9e3779b9u), pool_mix((unsigned)key ^ 0x7f4a7c15u),
-                           pool_mix((unsigned)(key >> 32) + 0x6a09e667u)};
-    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * blockDim.x) {
-        unsigned long long x = (unsigned long long)i;
-        do {
-            x = pool_feistel(x, half_bits, k);  // cycle walking: the domain is < 4 n_rows, ~2 trips on average at worst
-        } while (x >= (unsigned long long)n_rows);
-        out[i] = (int64_t)x;
-    }
+    unsigned k[4];
+    perm_round_keys(key, k);  // csrc/r2l_perm.h: the bijection is shared with the ray store
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < n_out; i += (int64_t)gridDim.x * blockDim.x)
+        out[i] = (int64_t)perm_at((unsigned long long)i, (unsigned long long)n_rows, half_bits, k);
 }
 
 // rows [0, B): the batch; rows [B, B + n_out): pool rows idx[i]; three contiguous [B + n_out, 3] outputs
@@ -83,10 +61,8 @@ extern "C" int r2l_pool_pick(int64_t* idx_out, int64_t n_out, int64_t n_rows, ui
     R2L_REQUIRE(n_out >= 0 && n_rows >= 0 && n_out <= n_rows && n_rows < ((int64_t)1 << 60), "r2l_pool_pick: need 0 <= n_out <= n_rows");
     if (n_out == 0) return 0;
     R2L_REQUIRE(idx_out != nullptr, "r2l_pool_pick: idx_out is NULL");
-    int bits = 2;
-    while (((int64_t)1 << bits) < n_rows) bits += 2;  // even, 2^bits >= n_rows, < 4 n_rows
-    hipLaunchKernelGGL(r2l_pool_pick_kernel, dim3(grid_for(n_out)), dim3(256), 0, (hipStream_t)stream, idx_out, n_out, n_rows, bits / 2,
-                       (unsigned long long)key);
+    hipLaunchKernelGGL(r2l_pool_pick_kernel, dim3(grid_for(n_out)), dim3(256), 0, (hipStream_t)stream, idx_out, n_out, n_rows,
+                       perm_half_bits(n_rows), (unsigned long long)key);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

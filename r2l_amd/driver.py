@@ -638,13 +638,12 @@ def main(argv=None):
         return {"ms_per_frame": per * 1e3, "logger": logger}
 
     # ---------------- distillation training (data_mode rays) ----------------
-    if args.data_mode != "rays" or not args.datadir_kd:
+    if not args.r2l_online_kd and (args.data_mode != "rays" or not args.datadir_kd):
         raise NotImplementedError("training on the accelerated path needs --data_mode rays --datadir_kd <dir of "
-                                  "[4096,9] .npy ray shards> (README step 3/5)")
+                                  "[4096,9] .npy ray shards> (README step 3/5), or --r2l_online_kd (the teacher renders into a "
+                                  "device-resident ray store)")
     if device.type != "cuda":
         raise RuntimeError("R2L training runs on the HIP path and needs a ROCm GPU")
-    datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
-    files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
     # --N_rand is the GLOBAL batch in shard files per step, as in the reference (its DataLoader builds one batch that
     # nn.DataParallel then splits over the GPUs, main.py:794-806,1374): each rank loads N_rand / world shards, so the
     # README command keeps its optimisation schedule (lrate, N_iters, hard-ray pool size) at any GPU count
@@ -655,8 +654,55 @@ def main(argv=None):
         shards = split_shards(args.N_rand, world)
     except ValueError as e:
         raise SystemExit(str(e))
-    loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
-                              threads=max(1, min(args.num_workers, 16)))
+    filler = None  # --r2l_online_kd: the teacher fill of the store (online_kd.TeacherFill), while poses are pending
+    if args.r2l_online_kd:
+        # no shard files: the teacher renders this rank's poses into a device-resident store (r2l_amd/online_kd.py), all of
+        # them before iteration 1 or — --r2l_kd_every K — the first flush group now and one more every K iterations (the
+        # reference's data arriving during training, --i_update_data, main.py:1218-1259, without the files).  The sampler
+        # draws with the shard count of the moment.
+        from .online_kd import TeacherFill, shards_needed
+        from .options import parse_teacher_config
+        from .raystore import RayStore
+        targs = parse_teacher_config(args.r2l_teacher_config, teacher_ckpt=args.teacher_ckpt)
+        targs.r2l_precision = args.r2l_precision  # one arithmetic switch per run: the teacher kernels follow the command line
+        n_pose = args.n_pose_kd if isinstance(args.n_pose_kd, int) else int(args.n_pose_kd[0])
+        cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
+        if cap < 1:
+            raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
+        loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
+        filler = TeacherFill(loader, targs, H, W, float(hwf[2]), near, far, n_pose, args.create_data_chunk, rank, world, device, logger)
+        # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
+        # number, so these are the same rows bit for bit
+        n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
+        while not filler.done and (n_groups is None or filler.groups < n_groups):
+            filler.fill_group()
+        files = loader.files
+        if filler.done:
+            filler = None
+    elif args.r2l_device_store:
+        # the shard files are read ONCE into device memory; no reader threads, no per-step host-to-device copy
+        from .raystore import RayStore
+        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
+        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
+        mine = D.shard_for_rank(files, rank, world)
+        if not mine:
+            raise ValueError("rank %d got no ray shards (have %d files, world %d)" % (rank, len(files), world))
+        rows, cols = ctypes.c_int64(), ctypes.c_int64()
+        from . import _lib
+        _lib.check(_lib.load().r2l_npy_shape(mine[0].encode(), ctypes.byref(rows), ctypes.byref(cols)), "r2l_npy_shape")
+        loader = RayStore(len(mine), device, rays_per_shard=rows.value, seed=9973 * rank, logger=logger)
+        loader.append_files(mine, threads=max(1, min(args.num_workers, 16)))
+    else:
+        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
+        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
+        loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
+                                  threads=max(1, min(args.num_workers, 16)))
+    if args.r2l_online_kd or args.r2l_device_store:
+        loader.n_files = shards[rank]
+        logger.info("ray store: %s" % loader.describe())
+        if start > 0:  # --resume: the sampler is a pure function of (seed, shard count, draw): only the counter is restored
+            loader.seek(start * shards[rank])
+            logger.info("ray store: resuming at draw %d (start iteration %d x %d shards per step)" % (loader.draw, start, shards[rank]))
     uneven = len(set(shards)) > 1
     if uneven:
         logger.info("--N_rand %d over %d ranks: %s shard files per rank and step; gradients weighted by ray share" %
@@ -672,7 +718,12 @@ def main(argv=None):
     for i in range(start + 1, args.N_iters + 1):
         t0 = time.time()
         lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
-        batch = loader.next()  # device tensor; its H2D copy (36 B/ray) ran on the loader's stream during the last step
+        if filler is not None and i % args.r2l_kd_every == 0:  # --r2l_kd_every: one more flush group of teacher frames
+            filler.fill_group()
+            logger.info("Iter %d ray store grew to %d shards (%d poses pending)" % (i, loader.n_shards, filler.pending))
+            if filler.done:
+                filler = None
+        batch = loader.next()  # device tensor (shard reader: its H2D copy ran on the loader's stream during the last step)
         rays_o, rays_d, target = batch[:, :3], batch[:, 3:6], batch[:, 6:9]
         batch_size = rays_o.shape[0]
         if pool is not None:
@@ -739,4 +790,4 @@ def main(argv=None):
         logger.info("replicas in sync after %d iterations: %s (skipped steps: %d)" % (args.N_iters, ok, trainer.drain()))
         if not ok:
             raise RuntimeError("data-parallel replicas diverged")
-    return {"trainer": trainer, "logger": logger, "model": model, "r2l_config": r2l_config}
+    return {"trainer": trainer, "logger": logger, "model": model, "r2l_config": r2l_config, "loader": loader}

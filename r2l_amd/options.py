@@ -54,6 +54,12 @@ FLAGS = {
     # teacher frames (create_data, the teacher's test render) through ONE library call per group of poses
     # (r2l_teacher_frames_cfg: rays, draws and all stages behind the C ABI) instead of render()'s per-pose assembly; opt-in
     "r2l_fused_frames": ("flag", False),
+    # device-resident ray store (r2l_amd/raystore.py): training draws its shards from HBM with one launch per step.
+    # r2l_device_store: the shard files of --datadir_kd are read once into the store.  r2l_online_kd: no files at all, the
+    # teacher (--teacher_ckpt, described by the config file --r2l_teacher_config) renders --n_pose_kd poses into the store, all
+    # before iteration 1 (r2l_kd_every 0) or one flush group of --create_data_chunk poses every r2l_kd_every iterations
+    "r2l_device_store": ("flag", False), "r2l_online_kd": ("flag", False), "r2l_teacher_config": (str, ""),
+    "r2l_kd_every": (int, 0),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),
@@ -158,3 +164,33 @@ def validate_accelerated(args):
             raise NotImplementedError("--%s is a reference variant outside the accelerated R2L path" % name)
     if args.dataset_type != "blender":
         raise NotImplementedError("only --dataset_type blender is on the accelerated path (got %s)" % args.dataset_type)
+    validate_ray_store(args)
+
+
+def validate_ray_store(args):
+    """The ray-store flags name what they need: fail before anything is loaded."""
+    if args.r2l_kd_every < 0:
+        raise ValueError("--r2l_kd_every must be >= 0")
+    if args.r2l_online_kd:
+        for name in ("teacher_ckpt", "n_pose_kd", "r2l_teacher_config"):
+            if not getattr(args, name):
+                raise ValueError("--r2l_online_kd needs --%s" % name)
+        if args.r2l_device_store:
+            raise ValueError("--r2l_online_kd fills the store from the teacher, --r2l_device_store from files: give one of them")
+    elif args.r2l_kd_every:
+        raise ValueError("--r2l_kd_every needs --r2l_online_kd")
+    if args.r2l_device_store and (args.data_mode != "rays" or not args.datadir_kd):
+        raise ValueError("--r2l_device_store needs --data_mode rays and --datadir_kd")
+
+
+def parse_teacher_config(path, teacher_ckpt=None):
+    """--r2l_teacher_config: the teacher's own config file (e.g. configs/lego.txt) as a second namespace — the student's config
+    does not describe the teacher (use_viewdirs, N_samples, N_importance, perturb, white_bkgd).  The refusals of the fused
+    frames path apply: lindisp, raw_noise_std > 0 and a teacher without view directions raise NotImplementedError."""
+    targs = parse_args(["--config", path])
+    if targs.lindisp or targs.raw_noise_std or not targs.use_viewdirs:
+        raise NotImplementedError("%s: the ray store is filled through the fused frames path: lindisp, raw_noise_std > 0 and "
+                                  "use_viewdirs=False are outside it" % path)
+    if teacher_ckpt is not None:
+        targs.teacher_ckpt = teacher_ckpt
+    return targs

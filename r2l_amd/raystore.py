@@ -1,0 +1,244 @@
+"""Device-resident ray store: the [o, d, rgb] rows of distillation live in HBM between the teacher's rendering and the
+student's steps, instead of going through [4096,9] `.npy` shards (include/r2l_hip.h r2l_store_append / r2l_store_batch).
+
+perm() and shard_ids() restate in numpy what the device computes — the keyed bijection of csrc/r2l_perm.h (the one the hard-ray
+pool's row choice uses) and the sampler built on it; they are the specification the tests hold the kernels to.
+
+Sampler: draw t takes shard  perm(epoch_key(seed, t // n_shards), n_shards)[t % n_shards]  — a fresh permutation of the shards
+per epoch, without replacement inside an epoch (the InfiniteSampler of main.py:759-767), a pure function of (seed, n_shards, t).
+A store that grows while it is trained from (driver --r2l_kd_every) is sampled with the shard count of the moment.
+"""
+import ctypes
+import time
+
+import numpy as np
+
+M64 = (1 << 64) - 1
+
+
+def _mix(x):
+    """murmur3 finalizer on uint32 arrays (wrapping arithmetic)."""
+    x = x.astype(np.uint32, copy=True)
+    x ^= x >> np.uint32(16)
+    x *= np.uint32(0x85ebca6b)
+    x ^= x >> np.uint32(13)
+    x *= np.uint32(0xc2b2ae35)
+    x ^= x >> np.uint32(16)
+    return x
+
+
+def _mix1(x):
+    return int(_mix(np.array([x & 0xffffffff], dtype=np.uint32))[0])
+
+
+def round_keys(key):
+    key = int(key) & M64
+    lo, hi = key & 0xffffffff, key >> 32
+    return [_mix1(lo), _mix1(hi ^ 0x9e3779b9), _mix1(lo ^ 0x7f4a7c15), _mix1((hi + 0x6a09e667) & 0xffffffff)]
+
+
+def half_bits(n):
+    bits = 2
+    while (1 << bits) < n:
+        bits += 2
+    return bits // 2
+
+
+def _feistel(x, hb, k):
+    mask = np.uint32((1 << hb) - 1)
+    l = (x >> np.uint64(hb)).astype(np.uint32) & mask
+    r = x.astype(np.uint32) & mask
+    for i in range(4):
+        f = _mix(r ^ np.uint32(k[i])) & mask
+        l, r = r, l ^ f
+    return (l.astype(np.uint64) << np.uint64(hb)) | r.astype(np.uint64)
+
+
+def perm_at(key, n, idx):
+    """pi(key, n) evaluated at the indices idx (each < n): int64 array."""
+    hb, k = half_bits(n), round_keys(key)
+    x = _feistel(np.asarray(idx, dtype=np.uint64), hb, k)
+    while True:
+        out = np.nonzero(x >= np.uint64(n))[0]
+        if out.size == 0:
+            return x.astype(np.int64)
+        x[out] = _feistel(x[out], hb, k)  # cycle walking
+
+
+def perm(key, n):
+    """The bijection of [0, n) that r2l_pool_pick(n, n, key) writes and r2l_store_append shuffles by: int64[n]."""
+    return perm_at(key, n, np.arange(n, dtype=np.uint64))
+
+
+def epoch_key(seed, epoch):
+    """splitmix64 finalizer of seed + (epoch + 1) * 0x9E3779B97F4A7C15 (mod 2^64)."""
+    z = (int(seed) + (int(epoch) + 1) * 0x9E3779B97F4A7C15) & M64
+    z = ((z ^ (z >> 30)) * 0xBF58476D1CE4E5B9) & M64
+    z = ((z ^ (z >> 27)) * 0x94D049BB133111EB) & M64
+    return z ^ (z >> 31)
+
+
+def shard_ids(seed, n_shards, draw0, n_draw):
+    """Shard ids of the draws draw0 .. draw0 + n_draw - 1 (what r2l_store_batch copies and writes to ids_out): int64[n_draw]."""
+    out = np.empty(n_draw, dtype=np.int64)
+    t, j = int(draw0), 0
+    while j < n_draw:
+        e, r = divmod(t, n_shards)
+        n = min(n_shards - r, n_draw - j)
+        out[j:j + n] = perm_at(epoch_key(seed, e), n_shards, np.arange(r, r + n, dtype=np.uint64))
+        t, j = t + n, j + n
+    return out
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class RayStore:
+    """capacity_shards x rays_per_shard rows [o, d, rgb] in device memory, filled by append() (device rows, e.g. the teacher's
+    frames) or append_files() (existing shard files, read once) and drawn from by next(): one launch per batch, no host work.
+
+    next(n_files) has RayShardLoader.next's contract — the returned [n_files * rays_per_shard, 9] tensor stays valid until the
+    second-next call (two buffers) — and everything is ordered on the CURRENT stream: the copy into a buffer is enqueued behind
+    whatever read it two calls ago on that stream, so there is no host sync and no side stream.  `rows_per_file`, `files`
+    (one name per filled shard) and close() make it a drop-in for the driver's loader."""
+
+    def __init__(self, capacity_shards, device, rays_per_shard=4096, seed=0, logger=None):
+        import torch
+        from . import _lib
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("RayStore lives in GPU memory: it needs a ROCm device (got %s)" % self.device)
+        if self.device.index is None:  # "cuda" -> the current device, so that tensors' devices compare equal to it
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity, self.rows_per_file, self.seed = int(capacity_shards), int(rays_per_shard), int(seed) & M64
+        if self.capacity < 1 or self.rows_per_file < 1 or self.rows_per_file % 4:
+            raise ValueError("RayStore: capacity_shards >= 1 and rays_per_shard a positive multiple of 4 (got %d, %d)" %
+                             (self.capacity, self.rows_per_file))
+        need = self.capacity * self.rows_per_file * 36
+        free, _total = torch.cuda.mem_get_info(self.device)
+        if need > 0.8 * free:
+            raise MemoryError("RayStore: %d shards of %d rays need %.2f GB, more than 80 %% of the %.2f GB free on %s" %
+                              (self.capacity, self.rows_per_file, need / 1e9, free / 1e9, self.device))
+        self._lib, self._L = _lib, _lib.load()
+        self.data = torch.empty(self.capacity * self.rows_per_file, 9, dtype=torch.float32, device=self.device)
+        self.nbytes = need
+        self.n_shards = 0
+        self.files = []  # one name per filled shard (source file, or "store:<k>" for appended rows)
+        self.n_files = None  # default of next()
+        self.draw = 0
+        self.last_ids = None
+        self._buf, self._ids, self._k = [None, None], [None, None], 0
+        self.logger = logger
+
+    def _stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def append(self, rows, key, shuffle=True):
+        """Append a device [n, 9] fp32 tensor as floor(n / rays_per_shard) shards, rows shuffled by perm(key, n) (the tail of
+        the shuffled sequence is dropped, as create_data drops it).  Returns the number of shards written."""
+        import torch
+        if rows.device != self.device or rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 9:
+            raise ValueError("RayStore.append: need a [n, 9] fp32 tensor on %s" % self.device)
+        rows = rows.contiguous()
+        m = ctypes.c_int64()
+        self._lib.check(self._L.r2l_store_append(_p(rows), rows.shape[0], _p(self.data), self.capacity, self.n_shards,
+                                                 self.rows_per_file, int(key) & M64, int(bool(shuffle)), ctypes.byref(m),
+                                                 self._stream()), "r2l_store_append")
+        self.files += ["store:%d" % k for k in range(self.n_shards, self.n_shards + m.value)]
+        self.n_shards += m.value
+        return m.value
+
+    def append_files(self, files, threads=4):
+        """Read every listed [rays_per_shard, 9] .npy shard ONCE, in list order, through two pinned group buffers into the
+        store (no shuffle: the files are shuffled already).  Host threads fill one group while the other one is copied."""
+        import torch
+        from concurrent.futures import ThreadPoolExecutor
+        files = list(files)
+        if self.n_shards + len(files) > self.capacity:
+            raise ValueError("RayStore.append_files: %d files do not fit behind %d shards in a store of %d" %
+                             (len(files), self.n_shards, self.capacity))
+        threads = max(1, int(threads))
+        group = max(1, min(len(files), 4 * threads))
+        rps = self.rows_per_file
+        pinned = [torch.empty(group, rps, 9, dtype=torch.float32).pin_memory() for _ in range(2)]
+        views = [p.numpy() for p in pinned]
+        done = [None, None]
+        want = (rps, 9)
+
+        def read(path, dst):
+            with open(path, "rb") as f:
+                major, _minor = np.lib.format.read_magic(f)
+                shape, fortran, dtype = (np.lib.format.read_array_header_1_0 if major == 1 else np.lib.format.read_array_header_2_0)(f)
+                if tuple(shape) != want or fortran or dtype != np.dtype("<f4"):
+                    raise ValueError("%s: need a C-order float32 %s array, got %s %s" % (path, want, dtype, tuple(shape)))
+                buf = memoryview(dst).cast("B")
+                got = f.readinto(buf)
+                if got != len(buf):
+                    raise ValueError("%s: short read (%d of %d bytes)" % (path, got, len(buf)))
+
+        t0 = time.perf_counter()
+        view = self.data.view(self.capacity, rps, 9)
+        with ThreadPoolExecutor(max_workers=threads) as ex:
+            for g, a in enumerate(range(0, len(files), group)):
+                part, k = files[a:a + group], g & 1
+                if done[k] is not None:
+                    done[k].synchronize()  # the copy that last read this pinned buffer
+                list(ex.map(read, part, [views[k][i] for i in range(len(part))]))
+                view[self.n_shards:self.n_shards + len(part)].copy_(pinned[k][:len(part)], non_blocking=True)
+                done[k] = torch.cuda.Event()
+                done[k].record()
+                self.n_shards += len(part)
+        for ev in done:
+            if ev is not None:
+                ev.synchronize()
+        self.files += files
+        dt = time.perf_counter() - t0
+        gb = len(files) * rps * 36 / 1e9
+        msg = "ray store: read %d files, %.3f GB in %.2fs = %.2f GB/s (%d threads)" % (len(files), gb, dt, gb / max(dt, 1e-9), threads)
+        if self.logger is not None:
+            self.logger.info(msg)
+        return {"files": len(files), "GB": gb, "GB/s": gb / max(dt, 1e-9), "message": msg}
+
+    def next(self, n_files=None):
+        """[n_files * rays_per_shard, 9] device tensor of the next n_files draws; valid until the second-next call."""
+        import torch
+        n = int(self.n_files if n_files is None else n_files)
+        if self.data is None:
+            raise RuntimeError("RayStore is closed")
+        if self.n_shards < 1:
+            raise RuntimeError("RayStore.next: the store is empty")
+        k = self._k
+        if self._buf[k] is None or self._buf[k].shape[0] != n * self.rows_per_file:
+            # (a new tensor: the one handed out two calls ago stays the caller's; the allocator is stream-ordered)
+            self._buf[k] = torch.empty(n * self.rows_per_file, 9, dtype=torch.float32, device=self.device)
+            self._ids[k] = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._lib.check(self._L.r2l_store_batch(_p(self.data), self.n_shards, self.rows_per_file, self.draw, n, self.seed,
+                                                _p(self._buf[k]), _p(self._ids[k]), self._stream()), "r2l_store_batch")
+        self.draw += n
+        self.last_ids = self._ids[k]
+        self._k ^= 1
+        return self._buf[k]
+
+    __next__ = next
+
+    def __iter__(self):
+        return self
+
+    def seek(self, draw):
+        if draw < 0:
+            raise ValueError("RayStore.seek: negative draw")
+        self.draw = int(draw)
+
+    def shards(self):
+        """The filled part of the store as a [n_shards, rays_per_shard, 9] view."""
+        return self.data[:self.n_shards * self.rows_per_file].view(self.n_shards, self.rows_per_file, 9)
+
+    def describe(self):
+        return "%d / %d shards of %d rays, %.3f GB of %.3f GB allocated in device memory" % (
+            self.n_shards, self.capacity, self.rows_per_file, self.n_shards * self.rows_per_file * 36 / 1e9, self.nbytes / 1e9)
+
+    def close(self):
+        self.data = None
+        self._buf, self._ids, self.last_ids = [None, None], [None, None], None
