@@ -335,6 +335,18 @@ int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t stream_id, v
 int r2l_frame_rays(const float* c2w_dev /*[K][3][4]*/, const float* focal_dev, float focal, int K, int H, int W,
                    float* rays_o, float* rays_d, float* viewdirs, float* rows, void* stream);
 
+/* ndc_rays (helpers:260-279) of n explicit rays [n,3]: the rays of a forward-facing (LLFF) scene in normalised device
+ * coordinates.  Separately rounded fp32, in this order (extent W for cw, H for ch):
+ *   r = 1/(2*focal);  cw = -(1/(r*W));  ch = -(1/(r*H))     (-1 / (W / (2 focal)) as torch evaluates it for an fp32 tensor focal:
+ *                                                            number / tensor is reciprocal(tensor) * number)
+ *   t  = (-(near + o_z)) / d_z;   s_i = o_i + t*d_i
+ *   o' = ((cw*s_x)/s_z, (ch*s_y)/s_z, 1 + (2*near)/s_z)
+ *   d' = (cw*(d_x/d_z - s_x/s_z), ch*(d_y/d_z - s_y/s_z), (-2*near)/s_z)
+ * d_z == 0 gives the reference's inf / NaN.  In place is allowed (ndc_o == rays_o, ndc_d == rays_d).  n == 0 is a successful no-op;
+ * n < 0, H < 1, W < 1, focal <= 0 or a NULL pointer is hipErrorInvalidValue before any launch. */
+int r2l_ndc_rays(const float* rays_o, const float* rays_d, int64_t n, int H, int W, float focal, float near,
+                 float* ndc_o, float* ndc_d, void* stream);
+
 typedef struct r2l_teacher_frame_desc {
     int H, W; float focal; float near, far;
     int N_samples, N_importance;   /* N_importance 0: coarse pass only; with N_importance > 0: 3 <= N_samples <= 64,
@@ -343,7 +355,8 @@ typedef struct r2l_teacher_frame_desc {
     int white_bkgd; float raw_noise_std;   /* raw_noise_std must be 0 */
     int chunk_rays;                /* 0: a whole frame per pass */
     uint64_t seed, frame_id0;      /* draws of frame k: t_rand stream_id = 2*(frame_id0+k), u stream_id = 2*(frame_id0+k)+1 */
-    int reserved[4];               /* must be 0 */
+    int ndc;                       /* 0 | 1: 1 = forward-facing scenes, the stages run on the NDC image of the rays (below) */
+    int reserved[3];               /* must be 0 */
 } r2l_teacher_frame_desc;
 
 /* Frame k = render(H, W, focal_k, c2w = c2w_k, ndc = False, near, far, use_viewdirs = True, ...) of create_data.py:97-176:
@@ -354,7 +367,13 @@ typedef struct r2l_teacher_frame_desc {
  * perturb == 1: t_rand[r, s] and u[r, i] are r2l_draw_uniform elements r*N_samples + s and r*N_importance + i (r: ray within
  * its frame) of the frame's two streams, so the outputs do not depend on the grouping into calls or on chunk_rays.
  * perturb == 0: no t_rand; u_det is the one shared row of uniforms (u_stride 0).  rows[:, 6:9] receives rgb.  rgb0 (the coarse
- * pass's rgb) is written only when N_importance > 0.  K == 0 is a successful no-op. */
+ * pass's rgb) is written only when N_importance > 0.  K == 0 is a successful no-op.
+ * ndc == 1: frame k = render(H, W, focal, rays = get_rays(H, W, focal_k, c2w_k), ndc = True, ...) (create_data.py:138-152): the ray
+ * kernel writes the WORLD o, d to rows[:, 0:6] and takes viewdirs from the world d, and hands r2l_ndc_rays(o, d; near plane 1) to
+ * the stages, which are the same kernels; near / far are then NDC depths (0, 1).  The NDC coefficients cw / ch take desc.focal,
+ * NOT focal_dev[k]: desc.focal must be > 0 even when focal_dev is given.  That is the reference under use_rand_focal, which
+ * draws rays with the scaled focal_ but calls render(H, W, focal, rays=...) with the scene's (create_data.py:816-831).  The work
+ * buffer is the same size.  ndc == 0 enqueues what it always did. */
 int64_t r2l_teacher_frames_work_floats(const r2l_teacher_frame_desc* d);
 int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
                            const float* ttab /*dev [2*N_samples], as r2l_stratified_z*/,

@@ -32,7 +32,7 @@ class TeacherFrameDesc(ctypes.Structure):
     """r2l_teacher_frame_desc of include/r2l_hip.h (r2l_teacher_frames_cfg)."""
     _fields_ = [("H", _i), ("W", _i), ("focal", _f), ("near", _f), ("far", _f), ("N_samples", _i), ("N_importance", _i),
                 ("perturb", _i), ("white_bkgd", _i), ("raw_noise_std", _f), ("chunk_rays", _i), ("seed", ctypes.c_uint64),
-                ("frame_id0", ctypes.c_uint64), ("reserved", _i * 4)]
+                ("frame_id0", ctypes.c_uint64), ("ndc", _i), ("reserved", _i * 3)]
 
 
 _descp = ctypes.POINTER(TeacherFrameDesc)
@@ -104,6 +104,7 @@ SIGNATURES = {
     "r2l_raw2outputs": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_sample_pdf_sort": (_i, [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _p]),
     "r2l_draw_uniform": (_i, [_p, _l, ctypes.c_uint64, ctypes.c_uint64, _p]),
+    "r2l_ndc_rays": (_i, [_p, _p, _l, _i, _i, _f, _f, _p, _p, _p]),
     "r2l_frame_rays": (_i, [_p, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p]),
     "r2l_teacher_frames_work_floats": (_l, [_descp]),
     "r2l_teacher_frames_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 14 + [_cfgp]),

@@ -42,7 +42,7 @@ def create_teacher(args, device):
     return nets
 
 
-def teacher_render_kwargs(args, coarse, fine):
+def teacher_render_kwargs(args, coarse, fine, ndc=False):
     """render_kwargs_train of create_data.py:302-318 with the teacher pair plugged in (create_data.py:802-808)."""
     embed_fn, _ = get_embedder(args.multires, args.i_embed)
     embeddirs_fn, _ = get_embedder(args.multires_views, args.i_embed)
@@ -50,14 +50,15 @@ def teacher_render_kwargs(args, coarse, fine):
                                                    netchunk=args.netchunk)
     return dict(network_query_fn=qfn, perturb=args.perturb, N_importance=args.N_importance, network_fine=fine,
                 N_samples=args.N_samples, network_fn=coarse, use_viewdirs=args.use_viewdirs, white_bkgd=args.white_bkgd,
-                raw_noise_std=args.raw_noise_std, ndc=False, lindisp=args.lindisp)
+                raw_noise_std=args.raw_noise_std, ndc=ndc, lindisp=args.lindisp)
 
 
-def render_pose_rows(pose, H, W, focal, near, far, chunk, render_kwargs):
-    """[H*W, 9] rows [o, d, rgb] of one teacher-rendered pose (create_data.py:819-840)."""
+def render_pose_rows(pose, H, W, focal, near, far, chunk, render_kwargs, render_focal=None):
+    """[H*W, 9] rows [o, d, rgb] of one teacher-rendered pose (create_data.py:819-840).  render_focal: the focal render() gets
+    (it matters with ndc=True only: the reference draws the rays with the scaled focal_ but passes the scene's, :816-831)."""
     rays_o, rays_d = get_rays(H, W, focal, pose[:3, :4])
     with torch.no_grad():
-        rgb, *_ = render(H, W, focal, chunk=chunk, rays=torch.stack([rays_o, rays_d], 0), near=near, far=far,
+        rgb, *_ = render(H, W, focal if render_focal is None else render_focal, chunk=chunk, rays=torch.stack([rays_o, rays_d], 0), near=near, far=far,
                          **render_kwargs)
     return torch.cat([rays_o.reshape(-1, 3), rays_d.reshape(-1, 3), rgb.reshape(-1, 3)], dim=-1)
 
@@ -92,24 +93,25 @@ def main(argv=None):
     rng = np.random.RandomState(1000003 * rank)  # per-rank pose / focal / shuffle stream
 
     scene = None
-    if os.path.exists(os.path.join(args.datadir, "transforms_train.json")):
-        scene = D.load_blender_data(args.datadir, args.half_res, args.testskip)
-        hwf = scene[3]
+    if args.dataset_type == "llff" or os.path.exists(os.path.join(args.datadir, "transforms_train.json")):
+        scene = D.load_scene(args)
+        hwf = scene.hwf
         H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
     else:  # intrinsics of the 400x400 lego setting when no scene directory is present (main.py:927 comment)
         H, W, focal = 400, 400, 555.5555155968841
-    near, far = 2., 6.
+    near, far = (scene.near, scene.far) if scene is not None else (2., 6.)
+    ndc = scene is not None and scene.ndc
+    rand_pose = scene.rand_pose if scene is not None else D.get_rand_pose
     coarse, fine = create_teacher(args, device)
     apply_arithmetic(args, device, logger, teachers=(coarse, fine))  # --r2l_precision: the teacher kernels' arithmetic
-    kwargs = teacher_render_kwargs(args, coarse, fine)
+    kwargs = teacher_render_kwargs(args, coarse, fine, ndc=ndc)
     if args.test_teacher:
         # "Testing teacher..." (create_data.py:723-741): the test views through render_path with render_kwargs_test (perturb =
         # --perturb_test, raw_noise_std = 0), Loss / PSNR logged before any data is generated; frames sharded over the ranks
         from .driver import render_path
         if not args.teacher_ckpt or scene is None:
             raise SystemExit("--test_teacher needs --teacher_ckpt and a scene directory (--datadir) with test views")
-        images, poses, _, _, i_split = scene
-        images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:]) if args.white_bkgd else images[..., :3]
+        images, poses, i_split = scene.rgb_images(args.white_bkgd), scene.poses, (scene.i_train, scene.i_val, scene.i_test)
         kw_test = dict(kwargs, perturb=args.perturb_test, raw_noise_std=0., near=near, far=far)
         _, misc = render_path(poses[i_split[2]], coarse, None, device, logger, gt_imgs=images[i_split[2]], rank=rank, world=world,
                               teacher=dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kw_test, render_factor=args.render_factor,
@@ -180,12 +182,13 @@ def main(argv=None):
     if fused and device.type != "cuda":
         raise NotImplementedError("--r2l_fused_frames renders through libr2l_hip.so: it needs a GPU")
     if fused and (args.lindisp or args.raw_noise_std or not args.use_viewdirs):
-        raise NotImplementedError("--r2l_fused_frames: lindisp, raw_noise_std > 0 and use_viewdirs=False are outside the fused path")
+        raise NotImplementedError("--r2l_fused_frames: lindisp, raw_noise_std > 0 and use_viewdirs=False are outside the fused path "
+                                  "(pass --raw_noise_std 0 or drop --r2l_fused_frames)")
     logger.info("teacher frames: " + ("fused, one library call per flush group of %d poses (render_frames)" % chunk_poses if fused
                                       else "render() per pose"))
     group = []  # fused: (pose number, pose, focal) of the flush group being collected
     for j, i in enumerate(mine, 1):
-        pose = D.get_rand_pose(rng)
+        pose = rand_pose(rng)
         focal_ = focal * (1 + rng.rand()) if args.use_rand_focal else focal  # focal x U[1,2) (create_data.py:816)
         if fused:
             # same draws in the same order as below (pose, focal scale, ..., then the flush seed); the frames of the group are
@@ -199,7 +202,7 @@ def main(argv=None):
                 with torch.no_grad():
                     parts = [render_frames(c2ws[a:a + n], H, W, focals[a:a + n], near, far, coarse, fine, args.N_samples,
                                            args.N_importance, args.perturb, args.white_bkgd, seed=1000003 * rank,
-                                           frame_id0=ids[a], rows=True)["rows"]  # (a whole frame per pass, as below)
+                                           frame_id0=ids[a], rows=True, ndc=ndc, ndc_focal=focal)["rows"]  # (a whole frame per pass)
                              for a, n in _runs(ids)]
                 filled = len(group) * H * W
                 free[k].wait()  # the flush that last used this buffer has been written
@@ -211,7 +214,7 @@ def main(argv=None):
         # whole frame per launch on the GPU: --chunk (32 768 rays in the reference's configs) is a memory work-around of
         # the op-by-op path; the fused kernels need 0.5 GB of scratch for a 400x400 frame at 192 samples
         chunk = max(args.chunk, H * W) if device.type == "cuda" else args.chunk
-        rows = render_pose_rows(pose, H, W, focal_, near, far, chunk, kwargs)
+        rows = render_pose_rows(pose, H, W, focal_, near, far, chunk, kwargs, render_focal=focal)
         if filled == 0:
             free[k].wait()  # the flush that last used this buffer has been written
         stage[k][filled:filled + H * W].copy_(rows, non_blocking=True)

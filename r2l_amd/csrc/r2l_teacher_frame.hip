@@ -1,6 +1,7 @@
 // r2l_teacher_frame.hip — teacher frames from camera poses in one library call (include/r2l_hip.h "teacher frames").
 //   r2l_frame_rays        : get_rays (utils/run_nerf_raybased_helpers.py:231-257) + the viewdirs of
 //                           create_data.py:138-147 for K whole frames, one launch
+//   r2l_ndc_rays          : ndc_rays (helpers:260-279) of explicit rays; the same arithmetic inside the frames' ray kernel
 //   r2l_draw_uniform      : counter-based uniforms (Philox4x32-10), a pure function of (seed, stream_id, element index): every
 //                           host of the C ABI draws the same t_rand / u, whatever its grouping of frames or chunks of rays
 //   r2l_teacher_frames_cfg: rays -> stratified z -> coarse MLP -> raw2outputs -> sample_pdf + sort -> fine MLP -> raw2outputs,
@@ -40,12 +41,25 @@ __global__ void r2l_draw_uniform_kernel(float* __restrict__ out, int64_t n, int6
     }
 }
 
+// ndc_rays (utils/run_nerf_raybased_helpers.py:260-279) of one ray, separately rounded fp32 in the order of include/r2l_hip.h.
+// o2 / d2 may alias o / d: everything is read before anything is written.
+__device__ __forceinline__ void ndc_one(const float (&o)[3], const float (&d)[3], float cw, float ch, float near, float (&o2)[3],
+                                        float (&d2)[3]) {
+    const float t = (-(near + o[2])) / d[2];
+    const float sx = o[0] + t * d[0], sy = o[1] + t * d[1], sz = o[2] + t * d[2];
+    const float qx = sx / sz, qy = sy / sz, dx = d[0] / d[2], dy = d[1] / d[2];
+    o2[0] = (cw * sx) / sz; o2[1] = (ch * sy) / sz; o2[2] = 1.f + (2.f * near) / sz;
+    d2[0] = cw * (dx - qx); d2[1] = ch * (dy - qy); d2[2] = (-2.f * near) / sz;
+}
+
 // Rays first .. first + n of the K*H*W rays of K frames (ray r = (k*H + row)*W + col); outputs are indexed by r - first.
 // Separately rounded fp32 in the order of include/r2l_hip.h (the build passes -ffp-contract=off).
-__global__ void r2l_frame_rays_kernel(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H, int W,
-                                      int64_t first, int64_t n, float* __restrict__ rays_o, float* __restrict__ rays_d,
-                                      float* __restrict__ viewdirs, float* __restrict__ rows, float* __restrict__ nearfar, float near,
-                                      float far) {
+// NDC: rows and viewdirs take the world ray, rays_o / rays_d its ndc_rays image at near plane 1 (create_data.py:138-152).
+template <bool NDC>
+__device__ __forceinline__ void frame_rays_body(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H,
+                                                int W, int64_t first, int64_t n, float* __restrict__ rays_o,
+                                                float* __restrict__ rays_d, float* __restrict__ viewdirs, float* __restrict__ rows,
+                                                float* __restrict__ nearfar, float near, float far, float cw, float ch) {
     const int64_t hw = (int64_t)H * W;
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = first + j, k = r / hw, pix = r - k * hw;
@@ -59,10 +73,12 @@ __global__ void r2l_frame_rays_kernel(const float* __restrict__ c2w, const float
             d[i] = (dx * c[i * 4 + 0] + dy * c[i * 4 + 1]) + dz * c[i * 4 + 2];
             o[i] = c[i * 4 + 3];
         }
+        float on[3], dn[3];
+        if (NDC) ndc_one(o, d, cw, ch, 1.f, on, dn);
 #pragma unroll
         for (int i = 0; i < 3; ++i) {
-            if (rays_o != nullptr) rays_o[j * 3 + i] = o[i];
-            if (rays_d != nullptr) rays_d[j * 3 + i] = d[i];
+            if (rays_o != nullptr) rays_o[j * 3 + i] = NDC ? on[i] : o[i];
+            if (rays_d != nullptr) rays_d[j * 3 + i] = NDC ? dn[i] : d[i];
             if (rows != nullptr) { rows[j * 9 + i] = o[i]; rows[j * 9 + 3 + i] = d[i]; }
         }
         if (viewdirs != nullptr) {
@@ -74,6 +90,41 @@ __global__ void r2l_frame_rays_kernel(const float* __restrict__ c2w, const float
         }
         if (nearfar != nullptr && j == 0) { nearfar[0] = near; nearfar[1] = far; }
     }
+}
+
+__global__ void r2l_frame_rays_kernel(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H, int W,
+                                      int64_t first, int64_t n, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                      float* __restrict__ viewdirs, float* __restrict__ rows, float* __restrict__ nearfar, float near,
+                                      float far) {
+    frame_rays_body<false>(c2w, focal_dev, focal, H, W, first, n, rays_o, rays_d, viewdirs, rows, nearfar, near, far, 0.f, 0.f);
+}
+
+__global__ void r2l_frame_rays_ndc_kernel(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H,
+                                          int W, int64_t first, int64_t n, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                          float* __restrict__ viewdirs, float* __restrict__ rows, float* __restrict__ nearfar,
+                                          float near, float far, float cw, float ch) {
+    frame_rays_body<true>(c2w, focal_dev, focal, H, W, first, n, rays_o, rays_d, viewdirs, rows, nearfar, near, far, cw, ch);
+}
+
+// ndc_o / ndc_d [n,3] = ndc_rays of rays_o / rays_d [n,3]; the outputs may be the inputs (a thread reads its ray first).
+// No __restrict__: the pointers may alias.
+__global__ void r2l_ndc_rays_kernel(const float* rays_o, const float* rays_d, int64_t n, float cw, float ch, float near, float* ndc_o,
+                                    float* ndc_d) {
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
+        float o[3], d[3];
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { o[i] = rays_o[j * 3 + i]; d[i] = rays_d[j * 3 + i]; }
+        ndc_one(o, d, cw, ch, near, o, d);
+#pragma unroll
+        for (int i = 0; i < 3; ++i) { ndc_o[j * 3 + i] = o[i]; ndc_d[j * 3 + i] = d[i]; }
+    }
+}
+
+// cw (extent = W) / ch (extent = H) of ndc_rays: -1 / (extent / (2 focal)) as torch evaluates it for an fp32 tensor focal,
+// where number / tensor is reciprocal(tensor) * number:  r = 1 / (2 focal);  c = -(1 / (r * extent))
+float ndc_coef(int extent, float focal) {
+    const float r = 1.f / (2.f * focal);
+    return -(1.f / (r * (float)extent));
 }
 
 // rows[r, 6:9] = rgb[r, :]
@@ -97,9 +148,14 @@ int launch_draw(float* out, int64_t n, int64_t i0, uint64_t seed, uint64_t strea
 }
 
 int launch_rays(const float* c2w, const float* focal_dev, float focal, int H, int W, int64_t first, int64_t n, float* rays_o,
-                float* rays_d, float* viewdirs, float* rows, float* nearfar, float near, float far, hipStream_t stream) {
-    hipLaunchKernelGGL(r2l_frame_rays_kernel, dim3(grid_for(n)), dim3(256), 0, stream, c2w, focal_dev, focal, H, W, first, n, rays_o,
-                       rays_d, viewdirs, rows, nearfar, near, far);
+                float* rays_d, float* viewdirs, float* rows, float* nearfar, float near, float far, hipStream_t stream,
+                bool ndc = false, float ndc_focal = 0.f) {
+    if (ndc)
+        hipLaunchKernelGGL(r2l_frame_rays_ndc_kernel, dim3(grid_for(n)), dim3(256), 0, stream, c2w, focal_dev, focal, H, W, first, n,
+                           rays_o, rays_d, viewdirs, rows, nearfar, near, far, ndc_coef(W, ndc_focal), ndc_coef(H, ndc_focal));
+    else
+        hipLaunchKernelGGL(r2l_frame_rays_kernel, dim3(grid_for(n)), dim3(256), 0, stream, c2w, focal_dev, focal, H, W, first, n,
+                           rays_o, rays_d, viewdirs, rows, nearfar, near, far);
     R2L_CHECK(hipGetLastError());
     return 0;
 }
@@ -118,7 +174,9 @@ const char* desc_check(const r2l_teacher_frame_desc* d) {
     if (d->perturb != 0 && d->perturb != 1) return "r2l_teacher_frame_desc.perturb: 0 or 1";
     if (d->raw_noise_std != 0.f) return "r2l_teacher_frame_desc.raw_noise_std: must be 0";
     if (d->chunk_rays < 0) return "r2l_teacher_frame_desc.chunk_rays: need chunk_rays >= 0";
-    if (d->reserved[0] || d->reserved[1] || d->reserved[2] || d->reserved[3]) return "r2l_teacher_frame_desc.reserved: must be 0";
+    if (d->ndc != 0 && d->ndc != 1) return "r2l_teacher_frame_desc.ndc: 0 or 1";
+    if (d->ndc == 1 && !(d->focal > 0.f)) return "r2l_teacher_frame_desc.focal: need focal > 0 with .ndc = 1 (also with focal_dev)";
+    if (d->reserved[0] || d->reserved[1] || d->reserved[2]) return "r2l_teacher_frame_desc.reserved: must be 0";
     return nullptr;
 }
 
@@ -170,6 +228,19 @@ extern "C" int r2l_frame_rays(const float* c2w_dev, const float* focal_dev, floa
                        (hipStream_t)stream);
 }
 
+extern "C" int r2l_ndc_rays(const float* rays_o, const float* rays_d, int64_t n, int H, int W, float focal, float near, float* ndc_o,
+                            float* ndc_d, void* stream) {
+    R2L_REQUIRE(n >= 0, "r2l_ndc_rays: n is negative");
+    R2L_REQUIRE(H >= 1 && W >= 1, "r2l_ndc_rays: need H >= 1 and W >= 1");
+    R2L_REQUIRE(focal > 0.f, "r2l_ndc_rays: need focal > 0");
+    if (n == 0) return 0;
+    R2L_REQUIRE(rays_o && rays_d && ndc_o && ndc_d, "r2l_ndc_rays: a pointer is NULL (rays_o, rays_d, ndc_o, ndc_d)");
+    hipLaunchKernelGGL(r2l_ndc_rays_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, n, ndc_coef(W, focal),
+                       ndc_coef(H, focal), near, ndc_o, ndc_d);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int64_t r2l_teacher_frames_work_floats(const r2l_teacher_frame_desc* d) {
     if (const char* why = desc_check(d)) {
         r2l_set_error_msg(why);
@@ -218,7 +289,7 @@ extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_d
             float* f_acc = acc ? acc + g : work + w.s_f + r4(cr_max);
             float* f_depth = depth ? depth + g : work + w.s_f + 2 * r4(cr_max);
             if ((rc = launch_rays(c2w_dev, focal_dev, d->focal, d->H, d->W, g, cr, o, dd, v, rows ? rows + g * 9 : nullptr, nf, d->near,
-                                  d->far, st)))
+                                  d->far, st, d->ndc == 1, d->focal)))
                 return rc;
             float* t_rand = nullptr;
             if (d->perturb) {

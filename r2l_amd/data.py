@@ -1,5 +1,6 @@
-"""Data layer on the R2L path: Blender-format scenes, pose generators and the [4096,9] `.npy` ray-shard format
-(mirror of /root/reference/dataset/load_blender.py:22-28, 31-120, 257-368; PIL replaces imageio/cv2).
+"""Data layer on the R2L path: Blender-format and forward-facing LLFF scenes, pose generators and the [4096,9] `.npy` ray-shard
+format (mirror of /root/reference/dataset/load_blender.py:22-28, 31-120, 257-368 and dataset/load_llff.py; PIL replaces
+imageio/cv2).
 
 Ray shards: NumPy v1 `.npy`, float32 C-order [n_ray, 9] rows [o(3), d(3), rgb(3)], named data_<k>.npy (teacher
 pseudo data, utils/create_data.py:854-872) or train_<k>.npy (real images).  RayShardLoader streams them through the
@@ -106,6 +107,185 @@ def load_blender_data(basedir, half_res=False, testskip=1, n_pose=40):
         imgs = imgs[:, :2 * H, :2 * W].reshape(imgs.shape[0], H, 2, W, 2, imgs.shape[-1]).mean(axis=(2, 4))
     return torch.from_numpy(np.ascontiguousarray(imgs, dtype=np.float32)), torch.from_numpy(poses), render_poses, [
         H, W, focal], i_split
+
+
+# ---- forward-facing LLFF scenes --------------------------------------------------------------------------------------
+# Restatement of the reference's dataset/load_llff.py:68-132, 135-183, 187-261, 336-456 (itself a lightly modified copy of
+# https://github.com/Fyusion/LLFF).  Not carried over: _minify (the reference shells out to ImageMagick to create images_<factor>/;
+# here a missing directory is an error), spherify_poses, the visualize_3d PDFs.
+
+
+def _normalize(x):
+    return x / np.linalg.norm(x)
+
+
+def _viewmatrix(z, up, pos):
+    vec2 = _normalize(z)
+    vec0 = _normalize(np.cross(up, vec2))
+    vec1 = _normalize(np.cross(vec2, vec0))
+    return np.stack([vec0, vec1, vec2, pos], 1)
+
+
+def poses_avg(poses):
+    """[3,5] average camera of poses [N,3,5]: mean centre, summed z and up axes, hwf of pose 0 (load_llff.py:155-161)."""
+    hwf = poses[0, :3, -1:]
+    center = poses[:, :3, 3].mean(0)
+    vec2 = _normalize(poses[:, :3, 2].sum(0))
+    up = poses[:, :3, 1].sum(0)
+    return np.concatenate([_viewmatrix(vec2, up, center), hwf], 1)
+
+
+def recenter_poses(poses):
+    """poses [N,3,5] expressed in the frame of their average camera; the hwf column is kept (load_llff.py:239-261)."""
+    out = poses + 0
+    bottom = np.reshape([0, 0, 0, 1.], [1, 4])
+    c2w = np.concatenate([poses_avg(poses)[:3, :4], bottom], -2)
+    p44 = np.concatenate([poses[:, :3, :4], np.tile(np.reshape(bottom, [1, 1, 4]), [poses.shape[0], 1, 1])], -2)
+    out[:, :3, :4] = (np.linalg.inv(c2w) @ p44)[:, :3, :4]
+    return out
+
+
+def render_path_spiral(c2w, up, rads, focal, zdelta, zrate, rots, N):
+    """N poses [3,5] on a spiral around c2w looking at the point `focal` in front of it (load_llff.py:164-183)."""
+    out = []
+    rads = np.array(list(rads) + [1.])
+    hwf = c2w[:, 4:5]
+    for theta in np.linspace(0., 2. * np.pi * rots, N + 1)[:-1]:
+        c = np.dot(c2w[:3, :4], np.array([np.cos(theta), -np.sin(theta), -np.sin(theta * zrate), 1.]) * rads)
+        z = _normalize(c - np.dot(c2w[:3, :4], np.array([0, 0, -focal, 1.])))
+        out.append(np.concatenate([_viewmatrix(z, up, c), hwf], 1))
+    return out
+
+
+class LLFFScene:
+    """What load_llff_data returns: images [N,H,W,3], poses [N,3,5] (column 4 = H, W, focal), bds [N,2], render_poses [n,3,5]
+    (all float32 tensors), i_test (the view nearest the average pose) — and the state the reference keeps in a module global for
+    get_rand_pose_v2: c2w (average pose), up.  Unpacks as the reference's 5-tuple."""
+
+    def __init__(self, images, poses, bds, render_poses, i_test, c2w, up):
+        self.images, self.poses, self.bds, self.render_poses, self.i_test = images, poses, bds, render_poses, i_test
+        self.c2w, self.up = c2w, up
+
+    def __iter__(self):
+        return iter((self.images, self.poses, self.bds, self.render_poses, self.i_test))
+
+
+def _llff_image_dir(basedir, factor):
+    imgdir = os.path.join(basedir, "images" if factor in (None, 1) else "images_%d" % factor)
+    if not os.path.isdir(imgdir):
+        raise FileNotFoundError("%s does not exist: images are not resized here (the published LLFF scenes ship images_4 and "
+                                "images_8; --factor 1 reads images/)" % imgdir)
+    return imgdir
+
+
+def load_llff_data(basedir, factor=8, recenter=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120):
+    """A forward-facing LLFF scene (load_llff.py:68-132, 336-456): poses_bounds.npy + images_<factor>/ -> LLFFScene."""
+    if spherify:
+        raise NotImplementedError("--spherify (360-degree LLFF captures) is outside the accelerated path")
+    from PIL import Image
+    poses_arr = np.load(os.path.join(basedir, "poses_bounds.npy"))
+    poses = poses_arr[:, :-2].reshape([-1, 3, 5]).transpose([1, 2, 0])  # [3,5,N]
+    bds = poses_arr[:, -2:].transpose([1, 0])
+    imgdir = _llff_image_dir(basedir, factor)
+    files = [os.path.join(imgdir, f) for f in sorted(os.listdir(imgdir)) if f.endswith(("JPG", "jpg", "png"))]
+    if poses.shape[-1] != len(files):
+        raise ValueError("%s holds %d images, poses_bounds.npy %d poses" % (imgdir, len(files), poses.shape[-1]))
+    imgs = np.stack([np.asarray(Image.open(f))[..., :3] / 255. for f in files], -1)  # [H,W,3,N]
+    poses[:2, 4, :] = np.array(imgs.shape[:2]).reshape([2, 1])
+    poses[2, 4, :] = poses[2, 4, :] * 1. / (1 if factor is None else factor)
+    # rotation columns of the LLFF convention [down, right, back] -> [right, up, back]; the view index moves to axis 0
+    poses = np.concatenate([poses[:, 1:2, :], -poses[:, 0:1, :], poses[:, 2:, :]], 1)
+    poses = np.moveaxis(poses, -1, 0).astype(np.float32)
+    images = np.moveaxis(imgs, -1, 0).astype(np.float32)
+    bds = np.moveaxis(bds, -1, 0).astype(np.float32)
+    sc = 1. if bd_factor is None else 1. / (bds.min() * bd_factor)
+    poses[:, :3, 3] *= sc
+    bds *= sc
+    if recenter:
+        poses = recenter_poses(poses)
+    c2w = poses_avg(poses)
+    # the spiral: a focus depth between the scene's bounds, radii = the 90th percentile of the camera positions
+    close_depth, inf_depth = bds.min() * .9, bds.max() * 5.
+    dt = .75
+    focal = 1. / ((1. - dt) / close_depth + dt / inf_depth)
+    zdelta = close_depth * .2
+    rads = np.percentile(np.abs(poses[:, :3, 3]), 90, 0)
+    c2w_path, n_views, n_rots = c2w, n_pose_video, 2
+    if path_zflat:
+        zloc = -close_depth * .1
+        c2w_path[:3, 3] = c2w_path[:3, 3] + zloc * c2w_path[:3, 2]
+        rads[2] = 0.
+        n_rots, n_views = 1, n_views // 2
+    up = _normalize(poses[:, :3, 1].sum(0))
+    render_poses = np.array(render_path_spiral(c2w_path, up, rads, focal, zdelta, zrate=.5, rots=n_rots, N=n_views))
+    render_poses = render_poses.astype(np.float32)
+    i_test = int(np.argmin(np.sum(np.square(poses_avg(poses)[:3, 3] - poses[:, :3, 3]), -1)))
+    t = lambda a: torch.from_numpy(np.ascontiguousarray(a, dtype=np.float32))
+    return LLFFScene(t(images), t(poses), t(bds), t(render_poses), i_test, c2w, up)
+
+
+def _rand_uniform(rng, left, right, scale=1):
+    assert right > left
+    middle = (left + right) * 0.5
+    left = middle - (right - left) * scale * 0.5
+    right = 2 * middle - left
+    return rng.rand() * (right - left) + left
+
+
+def get_rand_pose_llff(state, rng=np.random):
+    """A random pose [3,5] inside (1.1 x) the bounding boxes of the scene's camera centres and viewing axes
+    (get_rand_pose_v2, load_llff.py:187-236): six rng.rand() draws in the reference's order.  state: an LLFFScene."""
+    c2w, up, poses = state.c2w, state.up, state.poses.numpy()
+    hwf = c2w[:, 4:5]
+    box = lambda a: (np.min(a, axis=0), np.max(a, axis=0))
+    (lo_o, hi_o), (lo_d, hi_d) = box(poses[:, :3, 3]), box(poses[:, :3, 2])
+    c = np.dot(c2w[:3, :4], np.array([_rand_uniform(rng, lo_o[i], hi_o[i], 1.1) for i in range(3)] + [1]))
+    z = np.dot(c2w[:3, :4], np.array([_rand_uniform(rng, lo_d[i], hi_d[i], 1.1) for i in range(3)] + [1]))
+    pose = np.concatenate([_viewmatrix(_normalize(z), up, c), hwf], 1)
+    return torch.from_numpy(pose.astype(np.float32))
+
+
+# ---- one scene for the four drivers --------------------------------------------------------------------------------
+
+
+class Scene:
+    """What driver.main, create_data.main, train_nerf.main and online_kd.TeacherFill need of a data set: images [N,H,W,3|4],
+    poses [N,3|4,4], render_poses, video_poses, hwf = [H, W, focal], i_train / i_val / i_test, near, far, ndc, and
+    rand_pose(rng) -> a random pose [3|4, 4+] for pseudo data."""
+
+    def __init__(self, **kw):
+        self.__dict__.update(kw)
+
+    def rgb_images(self, white_bkgd):
+        """images [N,H,W,3]: blender RGBA composited on white with --white_bkgd (main.py:933-937); LLFF images have no alpha."""
+        im = self.images
+        if self.kind == "blender" and white_bkgd:
+            return im[..., :3] * im[..., -1:] + (1. - im[..., -1:])
+        return im[..., :3]
+
+
+def load_scene(args):
+    """The scene of --dataset_type: blender (main.py:922-937, 1007-1009) or llff (main.py:890-920, 1010-1011;
+    create_data.py:608-642).  near / far are the data set's: --trial.near / .far are applied by the callers, as before."""
+    if args.dataset_type == "llff":
+        sc = load_llff_data(args.datadir, args.factor, recenter=True, bd_factor=.75, spherify=args.spherify,
+                            n_pose_video=args.n_pose_video if isinstance(args.n_pose_video, int) else 120)
+        hwf = sc.poses[0, :3, -1]
+        n = sc.images.shape[0]
+        i_test = np.arange(n)[::args.llffhold] if args.llffhold > 0 else np.array([sc.i_test])
+        i_train = np.array([i for i in np.arange(n) if i not in i_test])
+        if args.no_ndc:
+            near, far = float(sc.bds.min()) * .9, float(sc.bds.max()) * 1.
+        else:
+            near, far = 0., 1.
+        return Scene(kind="llff", images=sc.images, poses=sc.poses[:, :3, :4], render_poses=sc.render_poses,
+                     video_poses=sc.render_poses, hwf=[int(hwf[0]), int(hwf[1]), float(hwf[2])], i_train=i_train, i_val=i_test,
+                     i_test=i_test, near=near, far=far, ndc=not args.no_ndc,
+                     rand_pose=lambda rng=np.random: get_rand_pose_llff(sc, rng))
+    images, poses, render_poses, hwf, i_split = load_blender_data(args.datadir, args.half_res, args.testskip)
+    return Scene(kind="blender", images=images, poses=poses, render_poses=render_poses,
+                 video_poses=get_novel_poses(args, n_pose=args.n_pose_video), hwf=hwf, i_train=i_split[0], i_val=i_split[1],
+                 i_test=i_split[2], near=2., far=6., ndc=False, rand_pose=get_rand_pose)
 
 
 # ---- ray shards -------------------------------------------------------------------------------------------------------
@@ -310,6 +490,33 @@ def convert_images_to_ray_shards(datadir, splits=("train",), suffix="", ignore=(
         rows.append(np.concatenate([ro.reshape(-1, 3).numpy(), rd.reshape(-1, 3).numpy(), im.reshape(-1, 3)], -1))
     rows = np.concatenate(rows, 0).astype(np.float32)
     rows = rows[rng.permutation(rows.shape[0])][rng.permutation(rows.shape[0])]  # shuffled twice, as the reference
+    n_files = rows.shape[0] // rays_per_file
+    for k in range(n_files):
+        np.save(os.path.join(savedir, "%s_%d.npy" % (prefix, k + 1)), rows[k * rays_per_file:(k + 1) * rays_per_file])
+    return savedir, n_files
+
+
+def convert_llff_to_ray_shards(datadir, splits=("train",), suffix="", factor=8, llffhold=8, rays_per_file=4096, rng=np.random):
+    """Real images of an LLFF scene -> shuffled [4096,9] ray shards `<splits>_<k>.npy` in `<datadir>_real_<splits><suffix>/`
+    (reference utils/convert_original_data_to_rays_llff.py:79-136: factor 8, every llffhold-th view held out, WORLD rays of
+    get_rays, two permutations).  Returns (savedir, n_files)."""
+    from .render import get_rays
+    prefix = "".join(splits)
+    savedir = "%s_real_%s%s" % (os.path.normpath(datadir), prefix, suffix)
+    os.makedirs(savedir, exist_ok=True)
+    sc = load_llff_data(datadir, factor=factor, recenter=True, bd_factor=.75, spherify=False, path_zflat=False, n_pose_video=120)
+    H, W, focal = sc.poses[0, :3, -1]
+    H, W = int(H), int(W)
+    n = sc.images.shape[0]
+    i_test = np.arange(n)[::llffhold] if llffhold > 0 else np.array([sc.i_test])
+    i_train = np.array([i for i in np.arange(n) if i not in i_test])
+    views = (list(i_train) if "train" in splits else []) + (list(i_test) if ("val" in splits or "test" in splits) else [])
+    rows = []
+    for i in views:
+        ro, rd = get_rays(H, W, focal, sc.poses[i, :3, :4])
+        rows.append(torch.cat([ro, rd, sc.images[i]], -1).reshape(H * W, 9))
+    rows = torch.cat(rows, 0).numpy().astype(np.float32)
+    rows = rows[rng.permutation(rows.shape[0])][rng.permutation(rows.shape[0])]
     n_files = rows.shape[0] // rays_per_file
     for k in range(n_files):
         np.save(os.path.join(savedir, "%s_%d.npy" % (prefix, k + 1)), rows[k * rays_per_file:(k + 1) * rays_per_file])

@@ -180,11 +180,11 @@ def create_r2l(args, device, logger):
     return model, embedder, history, ckpt
 
 
-def create_nerf_teacher(args, device, logger, near, far):
+def create_nerf_teacher(args, device, logger, near, far, ndc=False):
     """The `model_name in ['nerf']` branch of create_nerf (main.py:407-453, 481-509, 511-541) for rendering: coarse NeRF (+ the
     fine one when N_importance > 0) built from --netdepth/--netwidth(/_fine), weights from --pretrained_ckpt through
     load_weights_v2 ('network_fn_state_dict' / 'network_fine_state_dict'; a checkpoint that carries pickled modules replaces the
-    constructed ones), and render_kwargs_test: perturb = --perturb_test, raw_noise_std = 0, near / far of the blender scenes.
+    constructed ones), and render_kwargs_test: perturb = --perturb_test, raw_noise_std = 0, near / far / ndc of the scene.
     Teacher TRAINING is out of scope: no optimizer, parameters frozen."""
     from .nerf_raybased import NeRF
     from .render import get_embedder, run_network
@@ -222,7 +222,7 @@ def create_nerf_teacher(args, device, logger, near, far):
     # render_kwargs_test (main.py:511-541) + bds_dict (main.py:977-982)
     return dict(network_query_fn=qfn, perturb=args.perturb_test, N_importance=args.N_importance, network_fine=model_fine,
                 N_samples=args.N_samples, network_fn=model, use_viewdirs=args.use_viewdirs, white_bkgd=args.white_bkgd,
-                raw_noise_std=0., ndc=False, lindisp=args.lindisp, near=near, far=far)
+                raw_noise_std=0., ndc=ndc, lindisp=args.lindisp, near=near, far=far)
 
 
 def apply_arithmetic(args, device, logger, student=None, teachers=()):
@@ -470,7 +470,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
                 with torch.no_grad():  # (draws of --perturb_test > 0: stream pair of frame i = its pose number, whatever the ranks)
                     outs = [render_frames(c2ws[k:k + n], H, W, focal, kw["near"], kw["far"], kw["network_fn"], kw.get("network_fine"),
                                           kw["N_samples"], kw.get("N_importance", 0), kw.get("perturb", 0.), kw.get("white_bkgd", False),
-                                          seed=int(teacher.get("seed", 0)), frame_id0=idx[k])["rgb"] for k, n in _runs(idx)]
+                                          seed=int(teacher.get("seed", 0)), frame_id0=idx[k], ndc=bool(kw.get("ndc")))["rgb"]
+                            for k, n in _runs(idx)]
                 frames = (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).view(len(idx), H, W, 3)
                 e1.record()
                 events.append((idx, e0, e1))
@@ -560,21 +561,22 @@ def main(argv=None):
     torch.manual_seed(int(os.environ.get("R2L_SEED", "0")))
     logger = Logger(args, rank)
 
-    images, poses, render_poses, hwf, i_split = D.load_blender_data(args.datadir, args.half_res, args.testskip)
-    logger.info("Loaded blender", tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
-    i_train, i_val, i_test = i_split
-    near, far = 2., 6.
+    scene = D.load_scene(args)
+    images, poses, hwf = scene.images, scene.poses, scene.hwf
+    logger.info("Loaded %s" % scene.kind, tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
+    i_train, i_val, i_test = scene.i_train, scene.i_val, scene.i_test
+    near, far = scene.near, scene.far
     if hasattr(args, "trial") and args.trial.near > 0:
         assert args.trial.far > args.trial.near
         near, far = args.trial.near, args.trial.far
-    images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:]) if args.white_bkgd else images[..., :3]
+    images = scene.rgb_images(args.white_bkgd)
     H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
     if args.focal_scale > 0:
         focal *= args.focal_scale
 
     teacher = None
     if is_teacher:
-        kwargs_test = create_nerf_teacher(args, device, logger, near, far)
+        kwargs_test = create_nerf_teacher(args, device, logger, near, far, ndc=scene.ndc)
         model, point_sampler = kwargs_test["network_fn"], None
         teacher = dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kwargs_test, render_factor=args.render_factor,
                        fused=args.r2l_fused_frames)
@@ -588,7 +590,7 @@ def main(argv=None):
             was = ckpt["r2l_config"]
             logger.info("checkpoint was trained with r2l_config: precision %s, dw_mode %s" % (was.get("precision"), was.get("dw_mode")))
     test_poses, test_images = poses[i_test], images[i_test]
-    video_poses = D.get_novel_poses(args, n_pose=args.n_pose_video)
+    video_poses = scene.video_poses
     start, best_psnr, best_psnr_step = history["start"], history["best_psnr"], history["best_psnr_step"]
 
     if args.test_pretrained:
@@ -670,7 +672,8 @@ def main(argv=None):
         if cap < 1:
             raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
         loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
-        filler = TeacherFill(loader, targs, H, W, float(hwf[2]), near, far, n_pose, args.create_data_chunk, rank, world, device, logger)
+        filler = TeacherFill(loader, targs, H, W, float(hwf[2]), near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
+                             rand_pose=scene.rand_pose, ndc=scene.ndc)
         # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
         # number, so these are the same rows bit for bit
         n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every

@@ -19,7 +19,7 @@ def check_teacher_args(targs, device=None):
     """The refusals of the fused frames path (create_data.main, driver.render_path)."""
     if targs.lindisp or targs.raw_noise_std or not targs.use_viewdirs:
         raise NotImplementedError("teacher fill of the ray store renders through the fused frames path: lindisp, raw_noise_std > 0 "
-                                  "and use_viewdirs=False are outside it")
+                                  "and use_viewdirs=False are outside it (pass --raw_noise_std 0)")
     if device is not None and torch.device(device).type != "cuda":
         raise NotImplementedError("teacher fill of the ray store renders through libr2l_hip.so: it needs a GPU")
 
@@ -38,13 +38,16 @@ def shards_needed(n_pose, chunk_poses, H, W, rank=0, world=1, rays_per_shard=RAY
 class TeacherFill:
     """State of an incremental fill: the rank's pose list, its RandomState, the teacher pair and what is still pending."""
 
-    def __init__(self, store, targs, H, W, focal, near, far, n_pose, chunk_poses, rank, world, device, logger=None):
+    def __init__(self, store, targs, H, W, focal, near, far, n_pose, chunk_poses, rank, world, device, logger=None,
+                 rand_pose=None, ndc=False):
         from .create_data import create_teacher
         from .driver import apply_arithmetic
         check_teacher_args(targs, device)
         self.store, self.targs, self.logger = store, targs, logger
         self.H, self.W, self.focal, self.near, self.far = int(H), int(W), float(focal), float(near), float(far)
         self.rank, self.world, self.device = rank, world, torch.device(device)
+        # the scene's pose generator and ray convention (data.load_scene): blender's by default
+        self.rand_pose, self.ndc = rand_pose or D.get_rand_pose, bool(ndc)
         self.chunk = max(int(chunk_poses), 1)
         self.mine = rank_poses(int(n_pose), rank, world)
         self.rng = np.random.RandomState(1000003 * rank)  # per-rank pose / focal / shuffle stream, as create_data.main
@@ -76,7 +79,7 @@ class TeacherFill:
         a = self.targs
         group = []
         for i in self.mine[self.at:self.at + self.chunk]:
-            pose = D.get_rand_pose(self.rng)
+            pose = self.rand_pose(self.rng)
             focal_ = self.focal * (1 + self.rng.rand()) if a.use_rand_focal else self.focal  # focal x U[1,2) (create_data.py:816)
             group.append((i, pose[:3, :4], focal_))
         ids = [g[0] for g in group]
@@ -87,7 +90,7 @@ class TeacherFill:
         with torch.no_grad():
             parts = [render_frames(c2ws[s:s + n], self.H, self.W, focals[s:s + n], self.near, self.far, self.coarse, self.fine,
                                    a.N_samples, a.N_importance, a.perturb, a.white_bkgd, seed=1000003 * self.rank,
-                                   frame_id0=ids[s], rows=True)["rows"] for s, n in _runs(ids)]
+                                   frame_id0=ids[s], rows=True, ndc=self.ndc, ndc_focal=self.focal)["rows"] for s, n in _runs(ids)]
         rows = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         key = int(self.rng.randint(0, 2**31 - 1))  # the flush seed: drawn where create_data.main's flush() draws it
         e[1].record()

@@ -21,7 +21,7 @@ FLAGS = {
     "resume_TimeID": (str, ""),
     # data
     "expname": (str, None), "basedir": (str, "./logs/"), "datadir": (str, "./data/nerf_synthetic/lego"),
-    "dataset_type": (str, "blender"), "testskip": (int, 8), "white_bkgd": ("flag", False), "half_res": ("flag", False),
+    "dataset_type": (str, "blender"), "testskip": (int, 8), "factor": (int, 8), "llffhold": (int, 8), "white_bkgd": ("flag", False), "half_res": ("flag", False),
     "datadir_kd": (str, ""), "data_mode": (str, "images"), "num_workers": (int, 8), "pseudo_ratio": (float, -1.),
     "pseudo_data_hold_ratio": (float, 0.), "i_update_data": (int, 1000000000), "focal_scale": (float, 1.),
     # networks
@@ -60,6 +60,9 @@ FLAGS = {
     # before iteration 1 (r2l_kd_every 0) or one flush group of --create_data_chunk poses every r2l_kd_every iterations
     "r2l_device_store": ("flag", False), "r2l_online_kd": ("flag", False), "r2l_teacher_config": (str, ""),
     "r2l_kd_every": (int, 0),
+    # forward-facing LLFF scenes (--dataset_type llff: --factor, --llffhold, --no_ndc; NDC rays through r2l_ndc_rays); opt-in —
+    # without the switch --dataset_type llff is refused as it always was.  configs/fern.txt and its kin carry it
+    "r2l_llff": ("flag", False),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),
@@ -72,8 +75,8 @@ CHOICES = {"r2l_precision": ["auto", "fp16x2", "bf16x3", "fp32_mfma"], "r2l_dw_m
 # flags of reference variants outside the accelerated path: accepted so old command lines / configs still parse
 IGNORED = {"plucker": ("flag", False), "learn_depth": (str, ""), "shuffle_input": ("flag", False),
            "given_render_path_rays": (str, ""), "convert_to_onnx": ("flag", False), "lpips_net": (str, "alex"),
-           "trans_origin": (str, ""), "select_pixel_mode": (str, "rand_pixel"), "factor": (int, 8),
-           "spherify": ("flag", False), "llffhold": (int, 8), "shape": (str, "greek"), "lw_depth": (float, 0.1),
+           "trans_origin": (str, ""), "select_pixel_mode": (str, "rand_pixel"),
+           "spherify": ("flag", False), "shape": (str, "greek"), "lw_depth": (float, 0.1),
            "no_cache": ("flag", False), "no_scp": ("flag", False), "cache_code": (str, ""), "skips": (str, "4")}
 
 
@@ -162,8 +165,14 @@ def validate_accelerated(args):
     for name in ("plucker", "learn_depth", "shuffle_input", "given_render_path_rays", "convert_to_onnx"):
         if getattr(args, name):
             raise NotImplementedError("--%s is a reference variant outside the accelerated R2L path" % name)
-    if args.dataset_type != "blender":
-        raise NotImplementedError("only --dataset_type blender is on the accelerated path (got %s)" % args.dataset_type)
+    if args.dataset_type == "llff" and args.r2l_llff:
+        if args.spherify:
+            raise NotImplementedError("--spherify (360-degree LLFF captures) is outside the accelerated path")
+        if args.lindisp:
+            raise NotImplementedError("--lindisp is outside the accelerated path")
+    elif args.dataset_type != "blender":
+        raise NotImplementedError("only --dataset_type blender is on the accelerated path (got %s); --dataset_type llff needs "
+                                  "the switch --r2l_llff (config key r2l_llff = True)" % args.dataset_type)
     validate_ray_store(args)
 
 
@@ -190,7 +199,8 @@ def parse_teacher_config(path, teacher_ckpt=None):
     targs = parse_args(["--config", path])
     if targs.lindisp or targs.raw_noise_std or not targs.use_viewdirs:
         raise NotImplementedError("%s: the ray store is filled through the fused frames path: lindisp, raw_noise_std > 0 and "
-                                  "use_viewdirs=False are outside it" % path)
+                                  "use_viewdirs=False are outside it (a config with raw_noise_std > 0, such as the LLFF ones: "
+                                  "copy it with raw_noise_std = 0)" % path)
     if teacher_ckpt is not None:
         targs.teacher_ckpt = teacher_ckpt
     return targs

@@ -42,6 +42,30 @@ def get_rays_np(H, W, focal, c2w):
     return o.numpy(), d.numpy()
 
 
+def ndc_rays(H, W, focal, near, rays_o, rays_d):
+    """Rays [...,3] of a forward-facing scene in normalised device coordinates (helpers:260-279).  CPU tensors: the reference's
+    torch expressions in its order, focal as an fp32 tensor; ROCm tensors: r2l_ndc_rays (include/r2l_hip.h states the order)."""
+    if rays_o.is_cuda:
+        sh = rays_d.shape
+        o = rays_o.expand(sh).reshape(-1, 3).float().contiguous()
+        d = rays_d.reshape(-1, 3).float().contiguous()
+        o2, d2 = torch.empty_like(o), torch.empty_like(d)
+        with torch.cuda.device(o.device):
+            _lib.check(_lib.load().r2l_ndc_rays(_ptr(o), _ptr(d), o.shape[0], int(H), int(W), float(focal), float(near), _ptr(o2),
+                                                _ptr(d2), _stream()), "r2l_ndc_rays")
+        return o2.reshape(sh), d2.reshape(sh)
+    focal = torch.as_tensor(focal, dtype=torch.float32)
+    t = -(near + rays_o[..., 2]) / rays_d[..., 2]
+    rays_o = rays_o + t[..., None] * rays_d
+    o0 = -1. / (W / (2. * focal)) * rays_o[..., 0] / rays_o[..., 2]
+    o1 = -1. / (H / (2. * focal)) * rays_o[..., 1] / rays_o[..., 2]
+    o2 = 1. + 2. * near / rays_o[..., 2]
+    d0 = -1. / (W / (2. * focal)) * (rays_d[..., 0] / rays_d[..., 2] - rays_o[..., 0] / rays_o[..., 2])
+    d1 = -1. / (H / (2. * focal)) * (rays_d[..., 1] / rays_d[..., 2] - rays_o[..., 1] / rays_o[..., 2])
+    d2 = -2. * near / rays_o[..., 2]
+    return torch.stack([o0, o1, o2], -1), torch.stack([d0, d1, d2], -1)
+
+
 class Embedder:
     """NeRF positional encoding [x, sin(2^0 x), cos(2^0 x), ..., sin(2^(L-1) x), cos(2^(L-1) x)] (helpers:24-56)."""
 
@@ -347,9 +371,8 @@ def batchify_rays(rays_flat, chunk=1024 * 32, **kwargs):
 def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0., far=1., use_viewdirs=False,
            c2w_staticcam=None, **kwargs):
     """[rgb_map, disp_map, acc_map, extras] for explicit rays [2,...,3] or a full frame from c2w
-    (create_data.py:97-176).  NDC (forward-facing LLFF scenes) is out of scope."""
-    if ndc:
-        raise NotImplementedError("ndc rays (LLFF) are not part of the accelerated blender path; pass ndc=False")
+    (create_data.py:97-176).  ndc=True (forward-facing LLFF scenes): view directions are taken from the world rays, then the
+    rays go through ndc_rays at near plane 1 (create_data.py:138-152) and near / far are NDC depths."""
     if c2w is not None:
         rays_o, rays_d = get_rays(H, W, focal, c2w)
     else:
@@ -361,6 +384,8 @@ def render(H, W, focal, chunk=1024 * 32, rays=None, c2w=None, ndc=True, near=0.,
             rays_o, rays_d = get_rays(H, W, focal, c2w_staticcam)
         viewdirs = (viewdirs / torch.norm(viewdirs, dim=-1, keepdim=True)).reshape(-1, 3).float()
     sh = rays_d.shape
+    if ndc:
+        rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
     rays_o = rays_o.reshape(-1, 3).float()
     rays_d = rays_d.reshape(-1, 3).float()
     ones = torch.ones_like(rays_d[..., :1])
@@ -427,13 +452,16 @@ def draw_uniform(n, seed, stream_id, device):
 
 
 def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samples, N_importance, perturb, white_bkgd, seed,
-                  frame_id0=0, chunk=0, rows=False):
+                  frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None):
     """K teacher frames from K poses in ONE library call (r2l_teacher_frames_cfg): what render(H, W, focal_k, c2w=c2ws[k],
     ndc=False, near=, far=, use_viewdirs=True, ...) computes per pose, with the random draws of perturb > 0 made on the device
     by draw_uniform (frame k: t_rand = stream 2*(frame_id0+k), u = stream 2*(frame_id0+k)+1 of `seed`).  GPU only.
     focal: a number or K per-frame values; chunk: rays per pass (0: a whole frame); network_fine None: the coarse net serves
     both passes.  Returns {'rgb' [K*H*W,3], 'disp', 'acc', 'depth' [K*H*W], 'rgb0' (None when N_importance == 0),
-    'rows' ([K*H*W,9] = [o, d, rgb] when rows=True, else None)}."""
+    'rows' ([K*H*W,9] = [o, d, rgb] when rows=True, else None)}.
+    ndc=True: render(..., ndc=True) per pose instead (desc.ndc): rows keep the world rays, the stages see their ndc_rays image.  The
+    NDC coefficients take ONE focal, ndc_focal (default: `focal`, which must then be a number) — with per-frame focals that is the
+    reference's use_rand_focal: rays from focal_k, render(H, W, focal, rays=...) with the scene's."""
     c2ws = _pose_table(c2ws, next(network_fn.parameters()).device)
     _need_gpu(c2ws, "render_frames")
     dev = c2ws.device
@@ -445,7 +473,11 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
         if e is not None:
             e.ensure_packed()
     fdev, f = _focals(focal, K, dev)
-    desc = _lib.TeacherFrameDesc(H=H, W=W, focal=f, near=near, far=far, N_samples=N_samples, N_importance=N_importance,
+    if ndc:
+        if ndc_focal is None and fdev is not None:
+            raise ValueError("render_frames(ndc=True) with per-frame focals needs ndc_focal (the focal of the NDC coefficients)")
+        f = float(f if ndc_focal is None else ndc_focal)
+    desc = _lib.TeacherFrameDesc(ndc=int(bool(ndc)), H=H, W=W, focal=f, near=near, far=far, N_samples=N_samples, N_importance=N_importance,
                                  perturb=int(perturb > 0), white_bkgd=int(bool(white_bkgd)), raw_noise_std=0.,
                                  chunk_rays=int(chunk), seed=int(seed) & (2**64 - 1), frame_id0=int(frame_id0) & (2**64 - 1))
     n_work = lib.r2l_teacher_frames_work_floats(ctypes.byref(desc))

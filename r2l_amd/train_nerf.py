@@ -19,7 +19,7 @@ from .checkpoint import load_ckpt, save_ckpt
 from .driver import apply_arithmetic, create_nerf_teacher, init_distributed, render_path
 from .logger import Logger
 from .options import parse_args, validate_accelerated
-from .render import get_rays
+from .render import get_rays, ndc_rays
 from .teacher_train import MAX_SAMPLES, TeacherTrainer
 from .train_step import lr_schedule
 
@@ -74,6 +74,15 @@ def sample_batch(i, args, images, poses, i_train, H, W, focal):
     return rays_o, rays_d, viewdirs, target
 
 
+def device_rays(rays_o, rays_d, H, W, focal, ndc, device):
+    """The selected rays on `device` as the step takes them: NDC scenes (main.py:1303-1306 -> render(ndc=True)) put them through
+    ndc_rays at near plane 1 there; the view directions stay those of the world rays."""
+    rays_o, rays_d = rays_o.to(device), rays_d.to(device)
+    if ndc:
+        rays_o, rays_d = ndc_rays(H, W, focal, 1., rays_o, rays_d)
+    return rays_o, rays_d
+
+
 def _seed(i):
     s = (int(os.environ.get("R2L_SEED", "0")) * 1000003 + i) % (2**32)
     np.random.seed(s)
@@ -87,14 +96,15 @@ def main(argv=None):
     rank, world, device = init_distributed()
     _seed(0)
     logger = Logger(args, rank)
-    images, poses, _, hwf, i_split = D.load_blender_data(args.datadir, args.half_res, args.testskip)
-    logger.info("Loaded blender", tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
-    i_train, _, i_test = i_split
-    near, far = 2., 6.
-    images = images[..., :3] * images[..., -1:] + (1. - images[..., -1:]) if args.white_bkgd else images[..., :3]
+    scene = D.load_scene(args)
+    images, poses, hwf = scene.images, scene.poses, scene.hwf
+    logger.info("Loaded %s" % scene.kind, tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
+    i_train, i_test = scene.i_train, scene.i_test
+    near, far = scene.near, scene.far
+    images = scene.rgb_images(args.white_bkgd)
     H, W, focal = int(hwf[0]), int(hwf[1]), float(hwf[2])
 
-    kwargs_test = create_nerf_teacher(args, device, logger, near, far)
+    kwargs_test = create_nerf_teacher(args, device, logger, near, far, ndc=scene.ndc)
     coarse, fine = kwargs_test["network_fn"], kwargs_test["network_fine"]
     for net in (coarse, fine):
         if net is not None:
@@ -126,7 +136,8 @@ def main(argv=None):
             dH, dW = int(H // 2 * args.precrop_frac), int(W // 2 * args.precrop_frac)
             logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (2 * dH, 2 * dW, args.precrop_iters))
         lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
-        loss, psnr = trainer.step(rays_o.to(device), rays_d.to(device), viewdirs.to(device), near, far, target.to(device), lr)
+        rays_o, rays_d = device_rays(rays_o, rays_d, H, W, focal, scene.ndc, device)
+        loss, psnr = trainer.step(rays_o, rays_d, viewdirs.to(device), near, far, target.to(device), lr)
         history.append((loss, psnr))
         if i % args.i_print == 0:
             logger.info("[TRAIN] Iter %d Loss %.4f PSNR %.4f LR %.8f Time %.1fs" % (i, loss, psnr, lr, time.time() - t0))
