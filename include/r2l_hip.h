@@ -300,12 +300,19 @@ int r2l_teacher_backward(const float* rays_o, const float* rays_d, const float* 
                          int S, void* stream);
 
 /* z_out[R,S] = near*(1-t)+far*t, with stratified jitter when t_rand[R,S] != NULL (create_data.py:457-482).
- * near/far: per-ray values read at near[r*nf_stride], far[r*nf_stride]; ttab[2S] = t_vals ++ (1 - t_vals). */
+ * near/far: per-ray values read at near[r*nf_stride], far[r*nf_stride]; ttab[2S] = t_vals ++ (1 - t_vals).
+ * nf_stride = 1: two [R] arrays; nf_stride = 11 (8): columns 6 and 7 of [R,11] ([R,8]) ray rows, passed as rows + 6 and rows + 7;
+ * nf_stride = 0: every ray reads near[0], far[0] — ONE pair shared by all rays (the frames call).  S >= 1; S = 1 gives z = near
+ * (t_vals = [0]), jitter or not.  Every product and sum is rounded to fp32 on its own (no FMA), as torch's expressions are:
+ * the result equals theirs bit for bit.  R == 0 is a successful no-op. */
 int r2l_stratified_z(const float* near, const float* far, int nf_stride, const float* ttab, const float* t_rand,
                      float* z_out, int64_t R, int S, void* stream);
 
 /* raw2outputs (create_data.py:335-402 == main.py:556-621 == model/nerf_raybased.py:226-295).  noise[R,S] (already
- * scaled by raw_noise_std) and weights[R,S] are optional (NULL).  1 <= S <= 256. */
+ * scaled by raw_noise_std) and weights[R,S] are optional (NULL).  1 <= S <= 256.
+ * The last sample of a ray gets the interval 1e10 * |d|; S = 1 means exactly that for the one sample (alpha = 1 - exp(-relu(sigma)
+ * * 1e10 |d|), weights = alpha) — the reference's own expression is degenerate there (1e10 expanded over an empty slice: no
+ * sample at all) — as in r2l_raw2outputs_backward.  A ray without opacity (acc = 0) has disp = NaN (0 / 0), as the reference. */
 int r2l_raw2outputs(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
                     float* rgb_map, float* disp_map, float* acc_map, float* weights, float* depth_map, int64_t R, int S,
                     void* stream);
