@@ -5,51 +5,14 @@
 // control": layer 0, the two embedding column blocks and every bias divided by s, the alpha / rgb heads multiplied by s: exact),
 // so the launches after it run here again: the teacher's weights do not change, a sticky guard would be for good.
 #include "r2l_f2.h"
+#include "r2l_teacher_net.h"
 
-#define T2_W 256
-#define T2_XYZ 63
-#define T2_DIR 27
-// 145 stages of the 256-wide layers + the views layer (128 outputs = four of a stage's eight tile slots): its bias stage and
-// nine DOUBLE stages, each holding TWO k-blocks (tile slots 0-3: tiles 0-3 of k-block 2j, slots 4-7: tiles 0-3 of k-block
+// the 145 common stages (r2l_teacher_net.h) + the views layer (128 outputs = four of a stage's eight tile slots): its bias stage
+// and nine DOUBLE stages, each holding TWO k-blocks (tile slots 0-3: tiles 0-3 of k-block 2j, slots 4-7: tiles 0-3 of k-block
 // 2j + 1; eight feature pairs, then the two direction blocks) — both halves of such a stage accumulate into tiles 0-3, the
 // second with its own B operand.  (Round 2 ran the layer as 19 ordinary stages whose slots 4-7 held zeros: 5.5 % of the
 // launch's matrix work.)
 #define T2_STAGES 155
-
-struct T2Off {
-    int64_t w[8], b[8], views_w, views_b, feat_w, feat_b, alpha_w, alpha_b, rgb_w, rgb_b, total;
-};
-__host__ __device__ static inline T2Off t2_offsets() {  // state_dict order of NeRF(D=8, W=256, 63, 27, use_viewdirs)
-    T2Off o;
-    int64_t p = 0;
-    for (int i = 0; i < 8; ++i) {
-        const int fin = i == 0 ? T2_XYZ : (i == 5 ? T2_W + T2_XYZ : T2_W);
-        o.w[i] = p; p += (int64_t)T2_W * fin;
-        o.b[i] = p; p += T2_W;
-    }
-    o.views_w = p; p += (int64_t)128 * (T2_W + T2_DIR);
-    o.views_b = p; p += 128;
-    o.feat_w = p; p += (int64_t)T2_W * T2_W;
-    o.feat_b = p; p += T2_W;
-    o.alpha_w = p; p += T2_W;
-    o.alpha_b = p; p += 1;
-    o.rgb_w = p; p += 3 * 128;
-    o.rgb_b = p; p += 3;
-    o.total = p;
-    return o;
-}
-
-// embedding column of value v of half h (or -1 = zero padding); `nfreq_half` frequencies per half (5 xyz / 2 direction)
-__host__ __device__ static inline int t2_emb_col(int v, int h, int nfreq_half) {
-    const int ntrig = 6 * nfreq_half;
-    if (v < ntrig) {
-        const int q = v >> 1, fl = q / 3, ax = q % 3;
-        return 3 + (nfreq_half * h + fl) * 6 + ((v & 1) ? 3 + ax : ax);
-    }
-    if (v == ntrig) return h ? 2 : 0;
-    if (v == ntrig + 1) return h ? -1 : 1;
-    return -1;
-}
 
 // =================================================================================================================
 // pack
@@ -62,39 +25,21 @@ __host__ __device__ static inline int t2_emb_col(int v, int h, int nfreq_half) {
 // their terms are O(|W| |pe|) / s against hidden terms of O(amax / s) >= 2^10 whenever s > 1 — what they lose below 2^-25
 // absolute is below 2^-35 of the layer's output.)
 __device__ __forceinline__ void t2_pack_elements(const float* __restrict__ params, unsigned short* __restrict__ out, float inv_s) {
-    const T2Off off = t2_offsets();
+    const TOff off = t_offsets();
     const int64_t total = (int64_t)(T2_STAGES + R2L_F3_PAD_STAGES) * 8 * 64 * 8;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int s = (int)(idx & 7), lane = (int)((idx >> 3) & 63), tile = (int)((idx >> 9) & 7);
         const int g = (int)(idx >> 12);
         const int i = lane & 31, h = lane >> 5, o = 32 * tile + i;
         unsigned short* st = out + (int64_t)g * (F2_STAGE_BYTES / 2);
-        // decode the stage: kind 0 bias (offset boff), 1 xyz block (layer 0 or 5), 2 256->256 block, 3 views feature block,
-        // 4 views direction block
-        int kind = -1, layer = 0, kb = 0;
-        int64_t boff = 0;
+        // the stage: 0..144 as r2l_teacher_net.h has them, then the views layer (kind 3 feature block, 4 direction block);
+        // kind -1: stream padding
+        const T16Stage d = t16_body_stage(g, off);
+        int kind = d.kind, layer = d.layer, kb = d.kb;
+        int64_t boff = d.boff;
         bool views = false;
-        if (g == 0) { kind = 0; boff = off.b[0]; }
-        else if (g < 5) { kind = 1; layer = 0; kb = g - 1; }
-        else if (g < 145) {
-            int r = g - 5, k = 0;
-            const int psz[4] = {34, 34, 38, 34};
-            while (r >= psz[k]) { r -= psz[k]; ++k; }
-            const int lt = 1 + 2 * k, lx = 2 + 2 * k;  // lx == 8: feature_linear
-            const int tl = (k == 2) ? 21 : 17;        // stages of the t-layer
-            if (r < tl) {
-                layer = lt;
-                if (r == 0) { kind = 0; boff = off.b[lt]; }
-                else if (k == 2 && r <= 4) { kind = 1; kb = r - 1; }
-                else { kind = 2; kb = r - 1 - (k == 2 ? 4 : 0); }
-            } else {
-                r -= tl;
-                layer = lx;
-                if (r == 0) { kind = 0; boff = lx == 8 ? off.feat_b : off.b[lx]; }
-                else { kind = 2; kb = r - 1; }
-            }
-        } else if (g < T2_STAGES) {
-            const int r = g - 145;
+        if (g >= T16_BODY_STAGES && g < T2_STAGES) {
+            const int r = g - T16_BODY_STAGES;
             views = true;
             if (r == 0) { kind = 0; boff = off.views_b; }
             else if (r <= 8) { kind = 3; kb = 2 * (r - 1) + (tile >> 2); }  // double stage: k-blocks 2j (slots 0-3), 2j+1 (4-7)
@@ -106,23 +51,23 @@ __device__ __forceinline__ void t2_pack_elements(const float* __restrict__ param
         if (kind == 0) {
             if (!views || tile < 4) { w = params[boff + o]; have = true; }
         } else if (kind == 1) {
-            const int col = t2_emb_col(8 * kb + s, h, 5);
-            if (col >= 0) { w = layer == 5 ? params[off.w[5] + (int64_t)o * (T2_W + T2_XYZ) + col] : params[off.w[0] + (int64_t)o * T2_XYZ + col]; have = true; }
+            const int col = t16_emb_col(8 * kb + s, h, 5);
+            if (col >= 0) { w = layer == 5 ? params[off.w[5] + (int64_t)o * (T_W + T_XYZ) + col] : params[off.w[0] + (int64_t)o * T_XYZ + col]; have = true; }
         } else if (kind == 2) {
             const int T = kb >> 1, r = kb & 1;
             const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-            if (layer == 8) w = params[off.feat_w + (int64_t)o * T2_W + in];
-            else if (layer == 5) w = params[off.w[5] + (int64_t)o * (T2_W + T2_XYZ) + T2_XYZ + in];
-            else w = params[off.w[layer] + (int64_t)o * T2_W + in];
+            if (layer == 8) w = params[off.feat_w + (int64_t)o * T_W + in];
+            else if (layer == 5) w = params[off.w[5] + (int64_t)o * (T_W + T_XYZ) + T_XYZ + in];
+            else w = params[off.w[layer] + (int64_t)o * T_W + in];
             have = true;
         } else if (kind == 3) {
             const int T = kb >> 1, r = kb & 1;
             const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-            w = params[off.views_w + (int64_t)ov * (T2_W + T2_DIR) + in];
+            w = params[off.views_w + (int64_t)ov * (T_W + T_DIR) + in];
             have = true;
         } else if (kind == 4) {
-            const int col = t2_emb_col(8 * kb + s, h, 2);
-            if (col >= 0) { w = params[off.views_w + (int64_t)ov * (T2_W + T2_DIR) + T2_W + col]; have = true; }
+            const int col = t16_emb_col(8 * kb + s, h, 2);
+            if (col >= 0) { w = params[off.views_w + (int64_t)ov * (T_W + T_DIR) + T_W + col]; have = true; }
         }
         unsigned short v0 = 0, v1 = 0;
         if (have) {
@@ -168,47 +113,6 @@ __global__ void r2l_teacher2_rescale_kernel(const float* __restrict__ params, un
 // =================================================================================================================
 // kernel
 // =================================================================================================================
-struct T2Args {
-    const float* rays_o;
-    const float* rays_d;
-    const float* viewdirs;
-    const float* z;
-    const unsigned char* stream;
-    unsigned* status;  // range-guard word behind the stream: != 0 -> this launch is left to the bf16x3 kernel
-    const float* params;
-    float* raw;
-    int64_t n_pts;
-    int S;
-};
-
-// four embedding values v0 .. v0+3 of this half-wave: (sin, cos) pairs of c[axis] * 2^(nf*h + fl), then the identity
-template <int NF>
-struct T2Emb4 {
-    const float (&c)[3];
-    int h;
-    int v0;
-    __device__ __forceinline__ void operator()(float (&out)[4]) const {
-        const float base = h ? (float)(1 << NF) : 1.0f;
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            const int v = v0 + j;
-            if (v < 6 * NF) {
-                const int q = v >> 1, fl = q / 3, ax = q % 3;
-#ifdef T2_TIME_NOSINCOS  // (timing experiment only: results are wrong)
-                out[j] = c[ax] * (base * (float)(1 << fl)); out[j + 1] = out[j] + 1.0f;
-#else
-                r2l_sincos(c[ax] * (base * (float)(1 << fl)), out[j], out[j + 1]);
-#endif
-            } else if (v == 6 * NF) {
-                out[j] = h ? c[2] : c[0];
-                out[j + 1] = h ? 0.f : c[1];
-            } else {
-                out[j] = 0.f;
-                out[j + 1] = 0.f;
-            }
-        }
-    }
-};
 // relu(frag[c0 .. c0+3]) as B values (F3Take4<true>), and — riding along — four terms of a dot product with them: the alpha head
 // (alpha_linear on relu(layer 7)) is accumulated by the 32 gathers of the feature layer's GEMM, in the shadow of its MFMAs, from
 // the values they produce anyway; as a VALU burst after the layer it cost 1043 instructions per tile with the matrix pipe idle
@@ -322,20 +226,20 @@ __device__ __forceinline__ void t2_vstage(f32x16 (&acc)[R2L_NT], F2Pipe& P, F2Sp
     }
 }
 
-__global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T2Args a) {
+__global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[F2_NBUF][F2_STAGE_BYTES];
     // weights of the two VALU heads (alpha_linear [256], rgb_linear [3][128]): staged in LDS once per workgroup.  Read from global
     // inside the tile — 80 16-byte loads per lane with no registers left to keep them in flight — the heads cost 7 % of the frame
     // (timing build without them: 117.8 -> 109.7 ms, profiles/r04_teacher_heads_ab.txt); as broadcast LDS reads they cost ~2 %.
-    __shared__ __attribute__((aligned(16))) float head_a[2][T2_W];  // [0]: zeros, [1]: alpha_linear.weight
-    __shared__ __attribute__((aligned(16))) float head_rgb[3 * 128];
+    __shared__ __attribute__((aligned(16))) float head_a[2][T_W];  // [0]: zeros, [1]: alpha_linear.weight
+    __shared__ __attribute__((aligned(16))) float head_rgb[3 * T_VIEWS];
     // the heads' four biases as well: a VMEM load at the end of a tile makes hipcc wait for vmcnt(0), i.e. for the twenty weight-DMA
     // loads the pipeline has in flight for the stages behind the tile (1 - 2 us per 60 us tile: most of what the heads "cost")
     __shared__ __attribute__((aligned(16))) float head_b[4];  // rgb_linear.bias[0..2], alpha_linear.bias
     if (__builtin_nontemporal_load(a.status) != 0u) return;
-    const T2Off off = t2_offsets();
-    for (int i = threadIdx.x; i < T2_W; i += 256) { head_a[0][i] = 0.f; head_a[1][i] = a.params[off.alpha_w + i]; }
-    for (int i = threadIdx.x; i < 3 * 128; i += 256) head_rgb[i] = a.params[off.rgb_w + i];  // (published by the prologue's barrier)
+    const TOff off = t_offsets();
+    for (int i = threadIdx.x; i < T_W; i += 256) { head_a[0][i] = 0.f; head_a[1][i] = a.params[off.alpha_w + i]; }
+    for (int i = threadIdx.x; i < 3 * T_VIEWS; i += 256) head_rgb[i] = a.params[off.rgb_w + i];  // (published by the prologue's barrier)
     if (threadIdx.x < 4) head_b[threadIdx.x] = threadIdx.x < 3 ? a.params[off.rgb_b + threadIdx.x] : a.params[off.alpha_b];
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
@@ -391,8 +295,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T2Args a) {
     }
     P.sb = P.ones;
 
-    typedef T2Emb4<5> Xyz4;
-    typedef T2Emb4<2> Dir4;
+    typedef T16Emb4<5> Xyz4;
+    typedef T16Emb4<2> Dir4;
     typedef F3Take4<true> Relu4;
     // ---- layer 0: x = W0 pe + b0 (pre-activation; every consumer applies the ReLU to its B values) ---------------------
     f2_stage<true, true, false>(x, P, Xyz4{p, h, 0}, Xyz4{p, h, 4});
@@ -475,7 +379,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T2Args a) {
             for (int q = 0; q < 4; ++q) {
                 f32x4 wv[3];
 #pragma unroll
-                for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(wr + c * 128 + 32 * T + 8 * q);
+                for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(wr + c * T_VIEWS + 32 * T + 8 * q);
                 float y[4];
 #pragma unroll
                 for (int j = 0; j < 4; ++j) asm("v_max_f32_e32 %0, 0, %1" : "=v"(y[j]) : "v"(t[T][4 * q + j]));
@@ -518,13 +422,12 @@ int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream)
 
 int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream) {
-    T2Args a{};
+    T16Args a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
     // the status word lives in the caller's stream buffer (library-private contents): written through, hence the cast
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + t2_status_offset());
-    const int64_t tiles = (n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-    hipLaunchKernelGGL(r2l_teacher2_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(r2l_teacher2_kernel, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());
     hipLaunchKernelGGL(r2l_teacher2_rescale_kernel, dim3(512), dim3(256), 0, stream, tparams,
                        reinterpret_cast<unsigned short*>(const_cast<float*>(wstream2)), a.status);

@@ -12,84 +12,29 @@
 // Embedding k order per half-wave h: xyz: 15 (sin, cos) pairs (frequency 5h + q/3, axis q%3), then the identity (h = 0: x,
 // y; h = 1: z, pad);  direction: 6 pairs (frequency 2h + q/3), identity (x, y | z, pad), 2 pads.
 #include "r2l_f3.h"
+#include "r2l_teacher_net.h"
 
-#define T3_W 256
-#define T3_XYZ 63
-#define T3_DIR 27
 #define T3_STAGES 164
-
-struct T3Off {
-    int64_t w[8], b[8], views_w, views_b, feat_w, feat_b, alpha_w, alpha_b, rgb_w, rgb_b, total;
-};
-__host__ __device__ static inline T3Off t3_offsets() {  // state_dict order of NeRF(D=8, W=256, 63, 27, use_viewdirs)
-    T3Off o;
-    int64_t p = 0;
-    for (int i = 0; i < 8; ++i) {
-        const int fin = i == 0 ? T3_XYZ : (i == 5 ? T3_W + T3_XYZ : T3_W);
-        o.w[i] = p; p += (int64_t)T3_W * fin;
-        o.b[i] = p; p += T3_W;
-    }
-    o.views_w = p; p += (int64_t)128 * (T3_W + T3_DIR);
-    o.views_b = p; p += 128;
-    o.feat_w = p; p += (int64_t)T3_W * T3_W;
-    o.feat_b = p; p += T3_W;
-    o.alpha_w = p; p += T3_W;
-    o.alpha_b = p; p += 1;
-    o.rgb_w = p; p += 3 * 128;
-    o.rgb_b = p; p += 3;
-    o.total = p;
-    return o;
-}
-
-// embedding column of value v of half h (or -1 = zero padding); `nfreq_half` frequencies per half (5 xyz / 2 direction)
-__host__ __device__ static inline int t3_emb_col(int v, int h, int nfreq_half) {
-    const int ntrig = 6 * nfreq_half;
-    if (v < ntrig) {
-        const int q = v >> 1, fl = q / 3, ax = q % 3;
-        return 3 + (nfreq_half * h + fl) * 6 + ((v & 1) ? 3 + ax : ax);
-    }
-    if (v == ntrig) return h ? 2 : 0;
-    if (v == ntrig + 1) return h ? -1 : 1;
-    return -1;
-}
 
 // =================================================================================================================
 // pack
 // =================================================================================================================
 __global__ void r2l_pack_teacher3_kernel(const float* __restrict__ params, unsigned short* __restrict__ out) {
-    const T3Off off = t3_offsets();
+    const TOff off = t_offsets();
     const int64_t total = (int64_t)(T3_STAGES + R2L_F3_PAD_STAGES) * 8 * 64 * 8;
     for (int64_t idx = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * blockDim.x) {
         const int s = (int)(idx & 7), lane = (int)((idx >> 3) & 63), tile = (int)((idx >> 9) & 7);
         const int g = (int)(idx >> 12);
         const int i = lane & 31, h = lane >> 5, o = 32 * tile + i;
         unsigned short* st = out + (int64_t)g * (F3_STAGE_BYTES / 2);
-        // decode the stage: kind 0 bias (offset boff), 1 xyz block (layer 0 or 5), 2 256->256 block, 3 views feature block,
-        // 4 views direction block
-        int kind = -1, layer = 0, kb = 0;
-        int64_t boff = 0;
+        // the stage: 0..144 as r2l_teacher_net.h has them, then the views layer (kind 3 feature block, 4 direction block);
+        // kind -1: stream padding
+        const T16Stage d = t16_body_stage(g, off);
+        int kind = d.kind, layer = d.layer, kb = d.kb;
+        int64_t boff = d.boff;
         bool views = false;
-        if (g == 0) { kind = 0; boff = off.b[0]; }
-        else if (g < 5) { kind = 1; layer = 0; kb = g - 1; }
-        else if (g < 145) {
-            int r = g - 5, k = 0;
-            const int psz[4] = {34, 34, 38, 34};
-            while (r >= psz[k]) { r -= psz[k]; ++k; }
-            const int lt = 1 + 2 * k, lx = 2 + 2 * k;  // lx == 8: feature_linear
-            const int tl = (k == 2) ? 21 : 17;        // stages of the t-layer
-            if (r < tl) {
-                layer = lt;
-                if (r == 0) { kind = 0; boff = off.b[lt]; }
-                else if (k == 2 && r <= 4) { kind = 1; kb = r - 1; }
-                else { kind = 2; kb = r - 1 - (k == 2 ? 4 : 0); }
-            } else {
-                r -= tl;
-                layer = lx;
-                if (r == 0) { kind = 0; boff = lx == 8 ? off.feat_b : off.b[lx]; }
-                else { kind = 2; kb = r - 1; }
-            }
-        } else if (g < T3_STAGES) {
-            const int r = g - 145;
+        if (g >= T16_BODY_STAGES && g < T3_STAGES) {
+            const int r = g - T16_BODY_STAGES;
             views = true;
             if (r == 0) { kind = 0; boff = off.views_b; }
             else if (r <= 16) { kind = 3; kb = r - 1; }
@@ -100,22 +45,22 @@ __global__ void r2l_pack_teacher3_kernel(const float* __restrict__ params, unsig
         if (kind == 0) {
             if (!views || tile < 4) { w = params[boff + o]; have = true; }
         } else if (kind == 1) {
-            const int col = t3_emb_col(8 * kb + s, h, 5);
-            if (col >= 0) { w = layer == 5 ? params[off.w[5] + (int64_t)o * (T3_W + T3_XYZ) + col] : params[off.w[0] + (int64_t)o * T3_XYZ + col]; have = true; }
+            const int col = t16_emb_col(8 * kb + s, h, 5);
+            if (col >= 0) { w = layer == 5 ? params[off.w[5] + (int64_t)o * (T_W + T_XYZ) + col] : params[off.w[0] + (int64_t)o * T_XYZ + col]; have = true; }
         } else if (kind == 2) {
             const int T = kb >> 1, r = kb & 1;
             const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-            if (layer == 8) w = params[off.feat_w + (int64_t)o * T3_W + in];
-            else if (layer == 5) w = params[off.w[5] + (int64_t)o * (T3_W + T3_XYZ) + T3_XYZ + in];
-            else w = params[off.w[layer] + (int64_t)o * T3_W + in];
+            if (layer == 8) w = params[off.feat_w + (int64_t)o * T_W + in];
+            else if (layer == 5) w = params[off.w[5] + (int64_t)o * (T_W + T_XYZ) + T_XYZ + in];
+            else w = params[off.w[layer] + (int64_t)o * T_W + in];
             have = true;
         } else if (kind == 3) {
             const int T = kb >> 1, r = kb & 1;
             const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-            if (tile < 4) { w = params[off.views_w + (int64_t)o * (T3_W + T3_DIR) + in]; have = true; }
+            if (tile < 4) { w = params[off.views_w + (int64_t)o * (T_W + T_DIR) + in]; have = true; }
         } else if (kind == 4) {
-            const int col = t3_emb_col(8 * kb + s, h, 2);
-            if (tile < 4 && col >= 0) { w = params[off.views_w + (int64_t)o * (T3_W + T3_DIR) + T3_W + col]; have = true; }
+            const int col = t16_emb_col(8 * kb + s, h, 2);
+            if (tile < 4 && col >= 0) { w = params[off.views_w + (int64_t)o * (T_W + T_DIR) + T_W + col]; have = true; }
         }
         unsigned short v0 = 0, v1 = 0, v2 = 0;
         if (have) {
@@ -139,43 +84,6 @@ __global__ void r2l_pack_teacher3_kernel(const float* __restrict__ params, unsig
 // =================================================================================================================
 // kernel
 // =================================================================================================================
-struct T3Args {
-    const float* rays_o;
-    const float* rays_d;
-    const float* viewdirs;
-    const float* z;
-    const unsigned char* stream;
-    const unsigned* run_if;  // nullptr, or: return at once while this word is 0 (range-guard fallback of r2l_teacher2.hip)
-    const float* params;
-    float* raw;
-    int64_t n_pts;
-    int S;
-};
-
-// four embedding values v0 .. v0+3 of this half-wave: (sin, cos) pairs of c[axis] * 2^(nf*h + fl), then the identity
-template <int NF>
-struct T3Emb4 {
-    const float (&c)[3];
-    int h;
-    int v0;
-    __device__ __forceinline__ void operator()(float (&out)[4]) const {
-        const float base = h ? (float)(1 << NF) : 1.0f;
-#pragma unroll
-        for (int j = 0; j < 4; j += 2) {
-            const int v = v0 + j;
-            if (v < 6 * NF) {
-                const int q = v >> 1, fl = q / 3, ax = q % 3;
-                r2l_sincos(c[ax] * (base * (float)(1 << fl)), out[j], out[j + 1]);
-            } else if (v == 6 * NF) {
-                out[j] = h ? c[2] : c[0];
-                out[j + 1] = h ? 0.f : c[1];
-            } else {
-                out[j] = 0.f;
-                out[j + 1] = 0.f;
-            }
-        }
-    }
-};
 // either of two gatherers, chosen at run time (the stage in front of a conditionally inserted group of stages)
 template <class GA, class GB>
 struct T3Select {
@@ -191,10 +99,10 @@ struct T3Select {
     }
 };
 
-__global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T3Args a) {
+__global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T16Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[F3_NBUF][F3_STAGE_BYTES];
     if (a.run_if != nullptr && __builtin_nontemporal_load(a.run_if) == 0u) return;
-    const T3Off off = t3_offsets();
+    const TOff off = t_offsets();
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
@@ -246,8 +154,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T3Args a) {
     }
     P.sb = P.ones;
 
-    typedef T3Emb4<5> Xyz4;
-    typedef T3Emb4<2> Dir4;
+    typedef T16Emb4<5> Xyz4;
+    typedef T16Emb4<2> Dir4;
     typedef F3Take4<true> Relu4;
     // ---- layer 0: x = W0 pe + b0 (pre-activation; every consumer applies the ReLU to its B values) ---------------------
     f3_stage<true, true, false>(x, P, Xyz4{p, h, 0}, Xyz4{p, h, 4});
@@ -319,7 +227,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T3Args a) {
         for (int q = 0; q < 4; ++q) {
             f32x4 wv[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(P0 + off.rgb_w + c * 128 + 32 * T + 8 * q + 4 * h);
+            for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(P0 + off.rgb_w + c * T_VIEWS + 32 * T + 8 * q + 4 * h);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float y = fmaxf(t[T][4 * q + j], 0.f);
@@ -350,12 +258,11 @@ int r2l_teacher3_pack(const float* tparams, float* wstream3, hipStream_t stream)
 int r2l_teacher3_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream3, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
                      const unsigned* run_if) {
-    T3Args a{};
+    T16Args a{};
     a.run_if = run_if;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream3); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
-    const int64_t tiles = (n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-    hipLaunchKernelGGL(r2l_teacher3_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
+    hipLaunchKernelGGL(r2l_teacher3_kernel, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

@@ -6,37 +6,11 @@
 // Same register-resident chain as the student (r2l_common.h): one wavefront = 32 consecutive sample points, exact-fp32
 // MFMA, weights pre-packed into ONE stream in consumption order (r2l_pack_teacher below).
 #include "r2l_dispatch.h"
+#include "r2l_teacher_net.h"
 
-#define T_W 256
-#define T_XYZ 63
-#define T_DIR 27
 #define T_PE_STEPS 36   // xyz embedding k-steps per half-wave (30 trig + 3 identity + 3 pad)  -> 9 groups
 #define T_PE_GROUPS 9
 #define T_DIR_STEPS 16  // dir embedding k-steps per half-wave (12 trig + 3 identity + 1 pad)  -> 4 groups of 4 tiles
-
-// ---- flat parameter offsets, state_dict order of NeRF(D=8,W=256,63,27,use_viewdirs=True) ------------------------------
-struct TOff {
-    int64_t w[8], b[8], views_w, views_b, feat_w, feat_b, alpha_w, alpha_b, rgb_w, rgb_b, total;
-};
-__host__ __device__ static inline TOff t_offsets() {
-    TOff o;
-    int64_t p = 0;
-    for (int i = 0; i < 8; ++i) {
-        const int fin = i == 0 ? T_XYZ : (i == 5 ? T_W + T_XYZ : T_W);
-        o.w[i] = p; p += (int64_t)T_W * fin;
-        o.b[i] = p; p += T_W;
-    }
-    o.views_w = p; p += (int64_t)128 * (T_W + T_DIR);
-    o.views_b = p; p += 128;
-    o.feat_w = p; p += (int64_t)T_W * T_W;
-    o.feat_b = p; p += T_W;
-    o.alpha_w = p; p += T_W;
-    o.alpha_b = p; p += 1;
-    o.rgb_w = p; p += 3 * 128;
-    o.rgb_b = p; p += 3;
-    o.total = p;
-    return o;
-}
 
 // xyz-embedding column fed by k-step s of half-wave h (or -1 = zero padding).  The k order is ours to choose (the pack
 // kernel follows it): (sin, cos) PAIRS, so that a group of 4 k-steps needs exactly two sincos evaluations and the
@@ -140,14 +114,8 @@ struct TeacherArgs {
     float* raw;             // [R,S,4]
     int64_t n_pts;          // R*S
     int S;
-    float* stash;           // training only (r2l_teacher_mlp_train): the layer outputs of every point, T_STASH_* below
+    float* stash;           // training only (r2l_teacher_mlp_train): the layer outputs of every point (r2l_teacher_net.h)
 };
-
-// Stash of the forward with stash (teacher training, r2l_teacher_train.hip reads it): slot l of [P,256] floats for l = 0..7
-// holds relu(layer l), slot 8 the feature (no ReLU), slot 9 relu(views layer) as [P,128].  ReLU masks follow from the values.
-#define T_STASH_FEAT 8
-#define T_STASH_VIEWS 9
-#define T_STASH_PER_POINT (9 * T_W + 128)
 
 // one wave's NT 32-feature tiles of a layer output (accumulator layout: point = lane & 31, feature 32T + 8q + 4h + j)
 template <int NT>
@@ -240,7 +208,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         mfma_bias_group<true, 0>(x, ws, one_h0);
         t_pe_gemm<1, T_PE_GROUPS>(x, p, h, ws);  // 1 + 9 groups: the loop below starts at an even group index
     }
-    float* const st = STASH ? a.stash + pc * T_W : nullptr;  // slot l of this point: st + l * n_pts * T_W
+    float* const st = STASH ? a.stash + pc * T_W : nullptr;  // this point's row in slot 0
     if constexpr (STASH)
         if (valid) t_stash_store(st, x, h, true);
     // (L1,L2) (L3,L4) (L5,L6) (L7,feature): t = W_odd relu(x) [+ W5pe pe] + b ; x = W_even relu(t) + b
@@ -259,7 +227,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         }
         gemm256x<true, T_SLOT(1)>(t, x, ws, nh);
         if constexpr (STASH)
-            if (valid) t_stash_store(st + (2 * k + 1) * a.n_pts * T_W, t, h, true);
+            if (valid) t_stash_store(T_STASH_SLOT(st, 2 * k + 1, a.n_pts), t, h, true);
         if (k == 3) {  // alpha_linear on relu(layer 7)
             float acc = 0.f;
 #pragma unroll
@@ -276,7 +244,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         mfma_bias_group<true, T_SLOT(1)>(x, ws, one_h0);
         gemm256x<true, 0>(x, t, ws, nh);  // k == 3: x = feature_linear(relu(layer 7)), consumed WITHOUT a ReLU below
         if constexpr (STASH)
-            if (valid) t_stash_store(st + (2 * k + 2) * a.n_pts * T_W, x, h, k < 3);
+            if (valid) t_stash_store(T_STASH_SLOT(st, 2 * k + 2, a.n_pts), x, h, k < 3);
     }
     // views layer: v[128] = Wv [feature, dir-embedding] + bv   (4 output tiles; ReLU applied by the rgb head)
     f32x16 v[4];
@@ -321,7 +289,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         }
     }
     if constexpr (STASH)
-        if (valid) t_stash_store(a.stash + T_STASH_VIEWS * a.n_pts * T_W + pc * 128, v, h, true);
+        if (valid) t_stash_store(T_STASH_SLOT(a.stash, T_STASH_VIEWS, a.n_pts) + pc * T_VIEWS, v, h, true);
     // rgb = Wrgb relu(v) + b
     float acc3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -330,7 +298,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         for (int q = 0; q < 4; ++q) {
             f32x4 wv[3];
 #pragma unroll
-            for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(P + off.rgb_w + c * 128 + 32 * T + 8 * q + 4 * h);
+            for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(P + off.rgb_w + c * T_VIEWS + 32 * T + 8 * q + 4 * h);
 #pragma unroll
             for (int j = 0; j < 4; ++j) {
                 const float y = fmaxf(v[T][4 * q + j], 0.f);
@@ -350,18 +318,6 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
 // C ABI
 // ------------------------------------------------------------------------------------------------------------------
 extern "C" int64_t r2l_teacher_param_count(void) { return t_offsets().total; }
-// r2l_teacher3.hip: the same network on the bf16 matrix pipe (fp32-accurate); its stage stream follows the fp32 one
-int64_t r2l_teacher3_stream_floats(void);
-int r2l_teacher3_pack(const float* tparams, float* wstream3, hipStream_t stream);
-int r2l_teacher3_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
-                     const float* wstream3, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const unsigned* run_if);
-// r2l_teacher2.hip: three fp16 products per fp32 product (default), range-guarded; its stream follows the bf16x3 one
-int64_t r2l_teacher2_stream_floats(void);
-const unsigned* r2l_teacher2_status(const float* wstream2);
-int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream);
-int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
-                     const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream);
 static inline int64_t t_stream32_floats() { return (int64_t)TG_TOTAL * R2L_GROUP_FLOATS + R2L_STREAM_PAD; }
 // a teacher stream buffer = [fp32 groups | bf16x3 stages | fp16x2 stages + status words]
 static inline float* t_w3(const float* wstream) { return const_cast<float*>(wstream) + t_stream32_floats(); }
@@ -410,8 +366,7 @@ extern "C" int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, con
     }
     if (arith == R2L_ARITH_BF16X3)  // R2L_NO_FWD2=1: fp32-exact products on the bf16 matrix pipe (R2L_NO_FWD3=1: fp32 MFMA)
         return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, a.n_pts, S, (hipStream_t)stream, nullptr);
-    const int64_t tiles = (a.n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<false>, dim3(t_workgroups(a.n_pts)), dim3(256), 0, (hipStream_t)stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }
@@ -429,8 +384,7 @@ extern "C" int r2l_teacher_mlp_train(const float* rays_o, const float* rays_d, c
     TeacherArgs a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
     a.raw = raw; a.n_pts = R * (int64_t)S; a.S = S; a.stash = stash;
-    const int64_t tiles = (a.n_pts + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
-    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, (hipStream_t)stream, a);
+    hipLaunchKernelGGL(r2l_teacher_mlp_kernel<true>, dim3(t_workgroups(a.n_pts)), dim3(256), 0, (hipStream_t)stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

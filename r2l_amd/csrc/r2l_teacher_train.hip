@@ -8,39 +8,12 @@
 // products dW_l = G_l^T A_l reduced over the points in fixed-size chunks into partial slabs, summed in a fixed order by a second
 // kernel (no atomics: a step is bit-reproducible).  The positional encodings (A of layer 0, of layer 5's first 63 columns and
 // of the views layer's last 27) are not stored: the GEMM's loader recomputes them from (o, d, z) / viewdirs.
-#include "r2l_common.h"
+#include "r2l_teacher_net.h"
 
-#define TT_W 256
-#define TT_XYZ 63
-#define TT_DIR 27
 #define TT_BM 128
 #define TT_BN 128
 #define TT_BK 16
 #define TT_KCHUNK 2048  // points per partial slab of a weight gradient: fixed, so the reduction order never changes
-
-// ---- flat parameter offsets (state_dict order; same census as t_offsets of r2l_teacher_mlp.hip) ------------------------
-struct TTOff {
-    int64_t w[8], b[8], views_w, views_b, feat_w, feat_b, alpha_w, alpha_b, rgb_w, rgb_b, total;
-};
-static TTOff tt_offsets() {
-    TTOff o;
-    int64_t p = 0;
-    for (int i = 0; i < 8; ++i) {
-        const int fin = i == 0 ? TT_XYZ : (i == 5 ? TT_W + TT_XYZ : TT_W);
-        o.w[i] = p; p += (int64_t)TT_W * fin;
-        o.b[i] = p; p += TT_W;
-    }
-    o.views_w = p; p += (int64_t)128 * (TT_W + TT_DIR);
-    o.views_b = p; p += 128;
-    o.feat_w = p; p += (int64_t)TT_W * TT_W;
-    o.feat_b = p; p += TT_W;
-    o.alpha_w = p; p += TT_W;
-    o.alpha_b = p; p += 1;
-    o.rgb_w = p; p += 3 * 128;
-    o.rgb_b = p; p += 3;
-    o.total = p;
-    return o;
-}
 
 // ------------------------------------------------------------------------------------------------------------------
 // raw2outputs backward (one wave per ray, S <= 256 samples staged in LDS)
@@ -336,18 +309,18 @@ static int tt_dx(const float* G, int ldg, int Kout, const float* w, int ldw, int
     return tt_gemm(LdRowA{G, ldg}, LdWeightB{w, ldw, col0}, ep, P, N, Kout, Kout, nullptr, st);
 }
 
-static int64_t tt_slab_floats(int64_t P) { return ((P + TT_KCHUNK - 1) / TT_KCHUNK) * (int64_t)TT_W * (TT_W + TT_XYZ + 1); }
+static int64_t tt_slab_floats(int64_t P) { return ((P + TT_KCHUNK - 1) / TT_KCHUNK) * (int64_t)T_W * (T_W + T_XYZ + 1); }
 
 extern "C" int64_t r2l_teacher_train_work_floats(int64_t P) {
     if (P < 0) return -1;
-    return 2 * P * TT_W + P * 128 + tt_slab_floats(P);
+    return 2 * P * T_W + P * T_VIEWS + tt_slab_floats(P);  // G ping, G pong, G of the views layer, slabs
 }
 
 extern "C" int r2l_teacher_backward(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                                     const float* tparams, const float* stash, const float* draw, float* grads, float* work,
                                     int64_t R, int S, void* stream) {
     R2L_REQUIRE(R >= 0 && S >= 0, "r2l_teacher_backward: negative R / S");
-    const TTOff off = tt_offsets();
+    const TOff off = t_offsets();
     const int64_t P = R * (int64_t)S;
     if (P == 0) {  // no points: every gradient is zero
         R2L_REQUIRE(grads, "r2l_teacher_backward: grads is NULL");
@@ -359,40 +332,40 @@ extern "C" int r2l_teacher_backward(const float* rays_o, const float* rays_d, co
     const hipStream_t st = (hipStream_t)stream;
     const float* W = tparams;
     float* ga = work;
-    float* gb = ga + P * TT_W;
-    float* gv = gb + P * TT_W;
-    float* slab = gv + P * 128;
-    auto slot = [&](int l) { return stash + (int64_t)l * P * TT_W; };
-    const float* vst = slot(9);  // relu(views layer), [P,128]
+    float* gb = ga + P * T_W;
+    float* gv = gb + P * T_W;
+    float* slab = gv + P * T_VIEWS;
+    auto slot = [&](int l) { return T_STASH_SLOT(stash, (int64_t)l, P); };
+    const float* vst = slot(T_STASH_VIEWS);  // relu(views layer), [P,128]
     auto act = [&](const float* a, int nx, int w1, int nd) { return LdActB{a, rays_o, rays_d, viewdirs, z, S, nx, w1, nd}; };
     int rc;
     // heads: rgb_linear (128 -> 3) and alpha_linear (256 -> 1) weight gradients; G of the views layer
-    if ((rc = tt_weight_grad(draw, 4, 3, act(vst, 0, 128, 0), 128, P, slab, grads, off.rgb_w, off.rgb_b, st))) return rc;
-    if ((rc = tt_weight_grad(draw + 3, 4, 1, act(slot(7), 0, TT_W, 0), TT_W, P, slab, grads, off.alpha_w, off.alpha_b, st)))
+    if ((rc = tt_weight_grad(draw, 4, 3, act(vst, 0, T_VIEWS, 0), T_VIEWS, P, slab, grads, off.rgb_w, off.rgb_b, st))) return rc;
+    if ((rc = tt_weight_grad(draw + 3, 4, 1, act(slot(7), 0, T_W, 0), T_W, P, slab, grads, off.alpha_w, off.alpha_b, st)))
         return rc;
-    hipLaunchKernelGGL(tt_rgb_head_dx_kernel, dim3((unsigned)((P * 128 + 255) / 256 < 65536 ? (P * 128 + 255) / 256 : 65536)),
+    hipLaunchKernelGGL(tt_rgb_head_dx_kernel, dim3((unsigned)((P * T_VIEWS + 255) / 256 < 65536 ? (P * T_VIEWS + 255) / 256 : 65536)),
                        dim3(256), 0, st, draw, W + off.rgb_w, vst, gv, P);
     R2L_CHECK(hipGetLastError());
     // views layer: dW over [feature, PE(dir)]; dX to the feature (the direction encoding is a constant)
-    if ((rc = tt_weight_grad(gv, 128, 128, act(slot(8), 0, TT_W, TT_DIR), TT_W + TT_DIR, P, slab, grads, off.views_w,
+    if ((rc = tt_weight_grad(gv, T_VIEWS, T_VIEWS, act(slot(T_STASH_FEAT), 0, T_W, T_DIR), T_W + T_DIR, P, slab, grads, off.views_w,
                              off.views_b, st)))
         return rc;
-    if ((rc = tt_dx(gv, 128, 128, W + off.views_w, TT_W + TT_DIR, 0, TT_W, ga, nullptr, nullptr, nullptr, P, st))) return rc;
+    if ((rc = tt_dx(gv, T_VIEWS, T_VIEWS, W + off.views_w, T_W + T_DIR, 0, T_W, ga, nullptr, nullptr, nullptr, P, st))) return rc;
     // feature_linear: dW over h7; dX into h7 plus the alpha head's d sigma (x) w_alpha, then relu'(h7)
-    if ((rc = tt_weight_grad(ga, TT_W, TT_W, act(slot(7), 0, TT_W, 0), TT_W, P, slab, grads, off.feat_w, off.feat_b, st)))
+    if ((rc = tt_weight_grad(ga, T_W, T_W, act(slot(7), 0, T_W, 0), T_W, P, slab, grads, off.feat_w, off.feat_b, st)))
         return rc;
-    if ((rc = tt_dx(ga, TT_W, TT_W, W + off.feat_w, TT_W, 0, TT_W, gb, slot(7), draw + 3, W + off.alpha_w, P, st))) return rc;
+    if ((rc = tt_dx(ga, T_W, T_W, W + off.feat_w, T_W, 0, T_W, gb, slot(7), draw + 3, W + off.alpha_w, P, st))) return rc;
     // layers 7 .. 1: G (pre-activation gradient of layer l) in `cur`; layer 5's input is [PE(xyz), h4]
     float* cur = gb;
     float* nxt = ga;
     for (int l = 7; l >= 1; --l) {
-        const int nx = l == 5 ? TT_XYZ : 0;
-        const int fin = nx + TT_W;
-        if ((rc = tt_weight_grad(cur, TT_W, TT_W, act(slot(l - 1), nx, TT_W, 0), fin, P, slab, grads, off.w[l], off.b[l], st)))
+        const int nx = l == 5 ? T_XYZ : 0;
+        const int fin = nx + T_W;
+        if ((rc = tt_weight_grad(cur, T_W, T_W, act(slot(l - 1), nx, T_W, 0), fin, P, slab, grads, off.w[l], off.b[l], st)))
             return rc;
-        if ((rc = tt_dx(cur, TT_W, TT_W, W + off.w[l], fin, nx, TT_W, nxt, slot(l - 1), nullptr, nullptr, P, st))) return rc;
+        if ((rc = tt_dx(cur, T_W, T_W, W + off.w[l], fin, nx, T_W, nxt, slot(l - 1), nullptr, nullptr, P, st))) return rc;
         float* t = cur; cur = nxt; nxt = t;
     }
     // layer 0: dW over PE(xyz)
-    return tt_weight_grad(cur, TT_W, TT_W, act(nullptr, TT_XYZ, 0, 0), TT_XYZ, P, slab, grads, off.w[0], off.b[0], st);
+    return tt_weight_grad(cur, T_W, T_W, act(nullptr, T_XYZ, 0, 0), T_XYZ, P, slab, grads, off.w[0], off.b[0], st);
 }

@@ -82,7 +82,7 @@ def scene_rays(R, seed, H=181, W=181, focal=250.):
 
 
 # ---- fp64 yardstick of the teacher's network backward (r2l_teacher_backward) ----------------------------------------------
-STASH_SLOT = 256  # floats per point of one stash slot (r2l_teacher_mlp.hip: slots 0-7 relu(h0..h7), 8 the feature, 9 relu(views))
+STASH_SLOT = 256  # floats per point of one stash slot (r2l_teacher_net.h: slots 0-7 relu(h0..h7), 8 the feature, 9 relu(views))
 
 
 def stash_slots(stash, P):

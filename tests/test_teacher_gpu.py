@@ -218,23 +218,38 @@ def test_sample_pdf_sort_shapes_vs_oracle(S, NI, R):
     np.testing.assert_allclose(z_std.cpu().numpy(), torch.std(zs.cpu(), dim=-1, unbiased=False).numpy(), rtol=1e-4, atol=1e-6)
 
 
-def test_teacher_mlp_vs_oracle():
+# units of the point network's tiling: 32 points per wave, 128 per workgroup
+@pytest.mark.parametrize("R,S", [(37, 64), (1, 1), (1, 31), (1, 33), (3, 43), (43, 3)])
+def test_teacher_mlp_vs_oracle(R, S):
+    """raw of the three forwards against the oracle, down to the smallest shapes at which tiling can go wrong: one point, one
+    under / over a wave, (3, 43) a partial last tile with ray boundaries inside tiles, (43, 3) one point over a workgroup with
+    ray boundaries inside every tile.  raw is the front of a larger buffer: nothing behind R*S*4 floats may be written."""
+    import ctypes
+    from r2l_amd import _lib, engine as _engine
+    from r2l_amd.engine import _ptr, _stream
     from r2l_amd.render import teacher_engine
     coarse, _ = O.make_teacher_state_dicts(11, 2, alpha_bias=0.5)
     m = make_teacher(coarse)
     g = torch.Generator().manual_seed(0)
-    R, S = 37, 64
     o = torch.randn(R, 3, generator=g)
     d = torch.randn(R, 3, generator=g)
     vd = d / d.norm(dim=-1, keepdim=True)
     z = torch.sort(torch.rand(R, S, generator=g) * 4 + 2, -1)[0]
     pts = o[:, None, :] + d[:, None, :] * z[:, :, None]
+    eng = teacher_engine(m)
+    eng.ensure_packed()
+    n, tail, sentinel = R * S * 4, 4096, 0x7FA5C3E1  # (a NaN pattern no kernel writes)
+    buf = torch.full((n + tail,), sentinel, dtype=torch.int32, device="cuda")
+    dev = [t.cuda().contiguous() for t in (o, d, vd, z)]
     with torch.no_grad():
         ref = O.run_network(coarse, pts, vd)
-        raw = teacher_engine(m).mlp(o.cuda(), d.cuda(), vd.cuda(), z.cuda()).cpu()
+        _lib.check(eng.lib.r2l_teacher_mlp_cfg(*[_ptr(t) for t in dev], _ptr(eng.wstream), _ptr(eng.flat), _ptr(buf), R, S,
+                                               _stream(), ctypes.byref(_engine.merged_config(eng.cfg))), "r2l_teacher_mlp")
+    raw = buf[:n].view(torch.float32).view(R, S, 4).cpu()
     err = (raw - ref).abs().max().item()
-    print("teacher raw max err", err, "ref scale", ref.abs().max().item())
+    print("teacher raw (%d, %d) max err" % (R, S), err, "ref scale", ref.abs().max().item())
     assert err < 2e-5
+    assert (buf[n:] == sentinel).all().item()  # the tail: untouched bit for bit
 
 
 def test_render_rays_golden(golden_dir):
