@@ -465,6 +465,25 @@ int r2l_store_append(const float* rows_in, int64_t n_rows, float* store, int64_t
 int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
                     float* batch, int32_t* ids_out, void* stream);
 
+/* ---- pixel sampler of teacher training (batching mode without a bank of rays) ----------------------------------------------
+ * The reference's use_batching mode (main.py:1137-1162, 1199-1210) builds the rays of every pixel of every training image,
+ * shuffles that bank and hands out N_rand rows per step.  Here one draw is one pixel and its ray is computed when it is drawn:
+ * with M = n_img*H*W, draw t = draw0 + j, j < n_draw, takes pixel
+ *   g = pi(epoch_key(seed, t / M), M)(t % M)            (pi and epoch_key exactly as specified for r2l_store_batch above)
+ * — a fresh permutation of all pixels per epoch, without replacement inside an epoch, a pure function of (seed, M, t) — and
+ * g = (img*H + row)*W + col.  Outputs, each [n_draw,3]:
+ *   target[j]   = images[img,row,col,:]
+ *   the world ray (o, d) of pixel (row, col) under c2w[img], separately rounded fp32 in the order given for r2l_frame_rays
+ *   viewdirs[j] = d / sqrt((d_x^2 + d_z^2) + d_y^2)      (always of the WORLD d)
+ *   rays_o[j], rays_d[j] = (o, d) with ndc == 0; with ndc == 1 their r2l_ndc_rays image at near plane 1, cw / ch from focal
+ *   ids_out[j]  = g                                      (device int64[n_draw], or NULL)
+ * Stateless: the arguments are checked before any launch, one kernel is enqueued on `stream`, nothing synchronises.  n_draw == 0
+ * is a successful no-op.  hipErrorInvalidValue (with r2l_last_error): a NULL required pointer (all but ids_out), n_img / H / W < 1,
+ * focal <= 0, draw0 < 0, n_draw < 0, ndc not 0 or 1, M > 2^31 - 1.  r2l_amd/pixel_batch.py (pixel_ids, host_batch) restates it. */
+int r2l_pixel_batch(const float* images /*dev [n_img,H,W,3]*/, const float* c2w /*dev [n_img,3,4]*/, int n_img, int H, int W,
+                    float focal, int ndc, int64_t draw0, int64_t n_draw, uint64_t seed, float* rays_o, float* rays_d,
+                    float* viewdirs, float* target /*each [n_draw,3]*/, int64_t* ids_out /*[n_draw] or NULL*/, void* stream);
+
 /* ---- frame writer (host threads; test-set evaluation) ------------------------------------------------------------------
  * Replaces `imageio.imwrite(filename, to8b(rgb))` of every prediction / ground-truth frame in render_path (main.py:337-344):
  * a pool of encoder threads (zlib, Sub filter; lossless, so the decoded pixels are the bytes handed over).  `pixels`: HOST

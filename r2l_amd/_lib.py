@@ -117,6 +117,7 @@ SIGNATURES = {
     "r2l_pool_store": (_i, [_p, _p, _p, _l, _l, _l, _p, _p, _p, _l, _l, _p]),
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
+    "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
     "r2l_png_writer_open": (_i, [_i, _i, _p]),
     "r2l_png_writer_submit": (_i, [_p, ctypes.c_char_p, _p, _i, _i, _i, _p, _p]),
     "r2l_png_writer_wait": (_i, [_p, _l]),

@@ -7,8 +7,12 @@
 //   r2l_teacher_frames_cfg: rays -> stratified z -> coarse MLP -> raw2outputs -> sample_pdf + sort -> fine MLP -> raw2outputs,
 //                           the EXISTING kernels of those stages enqueued back to back on the caller's stream through one work
 //                           buffer the caller sized once: no allocation, no host synchronisation
-// The three kernels here move 12 - 72 bytes per ray: a thread per ray (per Philox block of four draws), no LDS.
+//   r2l_pixel_batch       : the batching mode of teacher training (main.py:1137-1162, 1199-1210) without its bank of rays:
+//                           draw t takes pixel pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img*H*W training pixels
+//                           (csrc/r2l_perm.h, the ray store's sampler), and its ray is computed on the spot
+// The kernels here move 12 - 72 bytes per ray: a thread per ray (per Philox block of four draws), no LDS.
 #include "r2l_dispatch.h"
+#include "r2l_perm.h"
 #include <math.h>
 
 namespace {
@@ -52,8 +56,23 @@ __device__ __forceinline__ void ndc_one(const float (&o)[3], const float (&d)[3]
     d2[0] = cw * (dx - qx); d2[1] = ch * (dy - qy); d2[2] = (-2.f * near) / sz;
 }
 
+// World ray of pixel (row, col) of an H x W frame with pose c ([3][4]) and focal f: separately rounded fp32 in the order of
+// include/r2l_hip.h (the build passes -ffp-contract=off).  The one definition behind r2l_frame_rays and r2l_pixel_batch.
+__device__ __forceinline__ void pixel_ray(const float* __restrict__ c, float f, int H, int W, int row, int col, float (&o)[3],
+                                          float (&d)[3]) {
+    const float dx = ((float)col - (float)W * .5f) / f, dy = -(((float)row - (float)H * .5f) / f), dz = -1.f;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        d[i] = (dx * c[i * 4 + 0] + dy * c[i * 4 + 1]) + dz * c[i * 4 + 2];
+        o[i] = c[i * 4 + 3];
+    }
+}
+
+// (x^2 + z^2) + y^2: the association of torch.norm's reduction over a 3-vector, so that render()'s own normalisation of
+// these rays_d gives these bits (tests/test_teacher_frames_gpu.py: fused = unfused)
+__device__ __forceinline__ float ray_norm(const float (&d)[3]) { return sqrtf((d[0] * d[0] + d[2] * d[2]) + d[1] * d[1]); }
+
 // Rays first .. first + n of the K*H*W rays of K frames (ray r = (k*H + row)*W + col); outputs are indexed by r - first.
-// Separately rounded fp32 in the order of include/r2l_hip.h (the build passes -ffp-contract=off).
 // NDC: rows and viewdirs take the world ray, rays_o / rays_d its ndc_rays image at near plane 1 (create_data.py:138-152).
 template <bool NDC>
 __device__ __forceinline__ void frame_rays_body(const float* __restrict__ c2w, const float* __restrict__ focal_dev, float focal, int H,
@@ -64,15 +83,8 @@ __device__ __forceinline__ void frame_rays_body(const float* __restrict__ c2w, c
     for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n; j += (int64_t)gridDim.x * blockDim.x) {
         const int64_t r = first + j, k = r / hw, pix = r - k * hw;
         const int row = (int)(pix / W), col = (int)(pix - (int64_t)row * W);
-        const float* c = c2w + k * 12;
-        const float f = focal_dev != nullptr ? focal_dev[k] : focal;
-        const float dx = ((float)col - (float)W * .5f) / f, dy = -(((float)row - (float)H * .5f) / f), dz = -1.f;
         float o[3], d[3];
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            d[i] = (dx * c[i * 4 + 0] + dy * c[i * 4 + 1]) + dz * c[i * 4 + 2];
-            o[i] = c[i * 4 + 3];
-        }
+        pixel_ray(c2w + k * 12, focal_dev != nullptr ? focal_dev[k] : focal, H, W, row, col, o, d);
         float on[3], dn[3];
         if (NDC) ndc_one(o, d, cw, ch, 1.f, on, dn);
 #pragma unroll
@@ -82,9 +94,7 @@ __device__ __forceinline__ void frame_rays_body(const float* __restrict__ c2w, c
             if (rows != nullptr) { rows[j * 9 + i] = o[i]; rows[j * 9 + 3 + i] = d[i]; }
         }
         if (viewdirs != nullptr) {
-            // (x^2 + z^2) + y^2: the association of torch.norm's reduction over a 3-vector, so that render()'s own
-            // normalisation of these rays_d gives these bits (tests/test_teacher_frames_gpu.py: fused = unfused)
-            const float nrm = sqrtf((d[0] * d[0] + d[2] * d[2]) + d[1] * d[1]);
+            const float nrm = ray_norm(d);
 #pragma unroll
             for (int i = 0; i < 3; ++i) viewdirs[j * 3 + i] = d[i] / nrm;
         }
@@ -117,6 +127,40 @@ __global__ void r2l_ndc_rays_kernel(const float* rays_o, const float* rays_d, in
         ndc_one(o, d, cw, ch, near, o, d);
 #pragma unroll
         for (int i = 0; i < 3; ++i) { ndc_o[j * 3 + i] = o[i]; ndc_d[j * 3 + i] = d[i]; }
+    }
+}
+
+// Draw t = draw0 + j of the pixel sampler: pixel g = pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img * hw training pixels,
+// g = (img * H + row) * W + col.  A thread per draw; the cycle walk of perm_at diverges within a wave (~2 trips at worst on
+// average).  Every index is 64-bit.  NDC: viewdirs take the world ray, rays_o / rays_d its ndc_rays image at near plane 1
+// (what train_nerf.device_rays does to the selected rays).
+template <bool NDC>
+__global__ void r2l_pixel_batch_kernel(const float* __restrict__ images, const float* __restrict__ c2w, int H, int W, float focal,
+                                       int64_t M, int half_bits, int64_t draw0, int64_t n_draw, unsigned long long seed,
+                                       float* __restrict__ rays_o, float* __restrict__ rays_d, float* __restrict__ viewdirs,
+                                       float* __restrict__ target, int64_t* __restrict__ ids_out, float cw, float ch) {
+    const int64_t hw = (int64_t)H * W;
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_draw; j += (int64_t)gridDim.x * blockDim.x) {
+        const unsigned long long t = (unsigned long long)(draw0 + j), epoch = t / (unsigned long long)M;
+        unsigned k[4];
+        perm_round_keys(perm_epoch_key(seed, epoch), k);
+        const int64_t g = (int64_t)perm_at(t - epoch * (unsigned long long)M, (unsigned long long)M, half_bits, k);
+        const int64_t img = g / hw, pix = g - img * hw;
+        const int row = (int)(pix / W), col = (int)(pix - (int64_t)row * W);
+        float o[3], d[3];
+        pixel_ray(c2w + img * 12, focal, H, W, row, col, o, d);
+        const float nrm = ray_norm(d);
+        float on[3], dn[3];
+        if (NDC) ndc_one(o, d, cw, ch, 1.f, on, dn);
+        const float* __restrict__ px = images + g * 3;
+#pragma unroll
+        for (int i = 0; i < 3; ++i) {
+            rays_o[j * 3 + i] = NDC ? on[i] : o[i];
+            rays_d[j * 3 + i] = NDC ? dn[i] : d[i];
+            viewdirs[j * 3 + i] = d[i] / nrm;
+            target[j * 3 + i] = px[i];
+        }
+        if (ids_out != nullptr) ids_out[j] = g;
     }
 }
 
@@ -237,6 +281,33 @@ extern "C" int r2l_ndc_rays(const float* rays_o, const float* rays_d, int64_t n,
     R2L_REQUIRE(rays_o && rays_d && ndc_o && ndc_d, "r2l_ndc_rays: a pointer is NULL (rays_o, rays_d, ndc_o, ndc_d)");
     hipLaunchKernelGGL(r2l_ndc_rays_kernel, dim3(grid_for(n)), dim3(256), 0, (hipStream_t)stream, rays_o, rays_d, n, ndc_coef(W, focal),
                        ndc_coef(H, focal), near, ndc_o, ndc_d);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_pixel_batch(const float* images, const float* c2w, int n_img, int H, int W, float focal, int ndc, int64_t draw0,
+                               int64_t n_draw, uint64_t seed, float* rays_o, float* rays_d, float* viewdirs, float* target,
+                               int64_t* ids_out, void* stream) {
+    R2L_REQUIRE(n_img >= 1 && H >= 1 && W >= 1, "r2l_pixel_batch: need n_img >= 1, H >= 1 and W >= 1");
+    R2L_REQUIRE(focal > 0.f, "r2l_pixel_batch: need focal > 0");
+    R2L_REQUIRE(ndc == 0 || ndc == 1, "r2l_pixel_batch: ndc is 0 or 1");
+    R2L_REQUIRE(n_draw >= 0, "r2l_pixel_batch: n_draw is negative");
+    R2L_REQUIRE(draw0 >= 0 && draw0 <= INT64_MAX - n_draw, "r2l_pixel_batch: draw0 is negative (or draw0 + n_draw overflows)");
+    const int64_t nh = (int64_t)n_img * H;  // < 2^62; checked before it is multiplied again
+    R2L_REQUIRE(nh <= 0x7fffffff && nh * W <= 0x7fffffff, "r2l_pixel_batch: need n_img * H * W < 2^31 pixels");
+    const int64_t M = nh * W;
+    R2L_REQUIRE(images && c2w && rays_o && rays_d && viewdirs && target,
+                "r2l_pixel_batch: a required pointer is NULL (images, c2w, rays_o, rays_d, viewdirs, target)");
+    if (n_draw == 0) return 0;
+    const hipStream_t st = (hipStream_t)stream;
+    if (ndc)
+        hipLaunchKernelGGL(r2l_pixel_batch_kernel<true>, dim3(grid_for(n_draw)), dim3(256), 0, st, images, c2w, H, W, focal, M,
+                           perm_half_bits(M), draw0, n_draw, (unsigned long long)seed, rays_o, rays_d, viewdirs, target, ids_out,
+                           ndc_coef(W, focal), ndc_coef(H, focal));
+    else
+        hipLaunchKernelGGL(r2l_pixel_batch_kernel<false>, dim3(grid_for(n_draw)), dim3(256), 0, st, images, c2w, H, W, focal, M,
+                           perm_half_bits(M), draw0, n_draw, (unsigned long long)seed, rays_o, rays_d, viewdirs, target, ids_out, 0.f,
+                           0.f);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

@@ -63,6 +63,10 @@ FLAGS = {
     # forward-facing LLFF scenes (--dataset_type llff: --factor, --llffhold, --no_ndc; NDC rays through r2l_ndc_rays); opt-in —
     # without the switch --dataset_type llff is refused as it always was.  configs/fern.txt and its kin carry it
     "r2l_llff": ("flag", False),
+    # teacher training in the reference's batching mode (no --no_batching: every batch is N_rand pixels drawn without replacement
+    # from all training images) through a pixel sampler on the device (r2l_amd/pixel_batch.py, r2l_pixel_batch); opt-in — without
+    # the switch utils/train_nerf.py refuses a run without --no_batching as it always did.  main.py / create_data.py ignore it
+    "r2l_batching": ("flag", False),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),

@@ -1,0 +1,146 @@
+"""Pixel sampler of teacher training in batching mode (include/r2l_hip.h r2l_pixel_batch; --r2l_batching).
+
+The reference's use_batching mode (main.py:1137-1162, 1199-1210) builds the rays of every pixel of every training image, shuffles
+that [n_img*H*W, 3, 3] bank after each epoch and hands out N_rand rows per step.  Here one draw is one pixel, and its ray is
+computed when it is drawn: with M = n_img*H*W, draw t takes pixel
+
+    g = perm(epoch_key(seed, t // M), M)[t % M],        g = (img*H + row)*W + col
+
+— the ray store's sampler (r2l_amd/raystore.py) on pixels: a fresh permutation per epoch, without replacement inside one, a pure
+function of (seed, M, t).  There is no bank of rays and no sampler state; a resumed run seeks to its draw number.
+
+pixel_ids() and host_batch() restate in numpy / torch what the kernel computes; they are the specification the tests hold it to,
+and the CPU path of the training loop.
+"""
+import ctypes
+
+import numpy as np
+import torch
+
+from . import raystore
+from .raystore import M64
+from .render import get_rays, ndc_rays
+
+M_MAX = 2**31 - 1
+
+
+def pixel_ids(seed, M, draw0, n_draw):
+    """Pixel ids of the draws draw0 .. draw0 + n_draw - 1 (what r2l_pixel_batch writes to ids_out): int64[n_draw]."""
+    out = np.empty(n_draw, dtype=np.int64)
+    t, j = int(draw0), 0
+    while j < n_draw:
+        e, r = divmod(t, M)
+        n = min(M - r, n_draw - j)
+        out[j:j + n] = raystore.perm_at(raystore.epoch_key(seed, e), M, np.arange(r, r + n, dtype=np.uint64))
+        t, j = t + n, j + n
+    return out
+
+
+def _check(images, poses, H, W, focal):
+    images = torch.as_tensor(images, dtype=torch.float32)
+    poses = torch.as_tensor(poses, dtype=torch.float32)
+    if poses.dim() == 2:
+        poses = poses[None]
+    poses = poses[:, :3, :4]
+    H, W, focal = int(H), int(W), float(focal)
+    if images.dim() != 4 or tuple(images.shape[1:]) != (H, W, 3) or images.shape[0] < 1 or poses.shape[0] != images.shape[0]:
+        raise ValueError("pixel batch: need images [n_img, %d, %d, 3] and as many poses, got %s and %s" %
+                         (H, W, tuple(images.shape), tuple(poses.shape)))
+    if not focal > 0:
+        raise ValueError("pixel batch: need focal > 0")
+    if images.shape[0] * H * W > M_MAX:
+        raise ValueError("pixel batch: %d x %d x %d pixels, at most 2^31 - 1" % (images.shape[0], H, W))
+    return images, poses, H, W, focal
+
+
+def host_batch(images, poses, H, W, focal, ndc, seed, draw0, n_draw):
+    """(rays_o, rays_d, viewdirs, target, ids) of the draws draw0 .. draw0 + n_draw - 1 on CPU tensors: get_rays of the frames that
+    are met, a gather at pixel_ids, the view directions of the world d with the kernel's (x^2 + z^2) + y^2 association, and
+    ndc_rays at near plane 1 with ndc.  images [n_img,H,W,3], poses [n_img,3|4,4]."""
+    images, poses, H, W, focal = _check(images, poses, H, W, focal)
+    images, poses = images.cpu(), poses.cpu()
+    hw = H * W
+    ids = torch.from_numpy(pixel_ids(int(seed) & M64, images.shape[0] * hw, draw0, n_draw))
+    img, pix = ids // hw, ids % hw
+    o, d = torch.empty(n_draw, 3), torch.empty(n_draw, 3)
+    for k in torch.unique(img).tolist():
+        at = torch.nonzero(img == k)[:, 0]
+        fo, fd = get_rays(H, W, focal, poses[k])
+        o[at], d[at] = fo.reshape(-1, 3)[pix[at]], fd.reshape(-1, 3)[pix[at]]
+    target = images.reshape(-1, 3)[ids]
+    # the kernel's square root is correctly rounded; torch.sqrt on fp32 CPU tensors is not on every CPU (measured on an AVX512
+    # host: 1 ulp off for a tenth of the rays), so the norm is the fp64 root of the fp32 sum, rounded once
+    s2 = (d[:, 0] * d[:, 0] + d[:, 2] * d[:, 2]) + d[:, 1] * d[:, 1]
+    nrm = torch.from_numpy(np.sqrt(s2.numpy().astype(np.float64)).astype(np.float32))
+    viewdirs = d / nrm[:, None]
+    if ndc:
+        o, d = ndc_rays(H, W, focal, 1., o, d)
+    return o, d, viewdirs, target, ids
+
+
+def _p(t):
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+class PixelBatcher:
+    """The training pixels and poses, and next(n): the (rays_o, rays_d, viewdirs, target) of the next n draws, each [n, 3].
+
+    On a ROCm device the images [n_img,H,W,3] (fp32, after Scene.rgb_images) and poses are uploaded once and a batch is one
+    r2l_pixel_batch launch on the CURRENT stream into one of two alternating sets of output buffers: the tensors handed out stay
+    valid until the second-next call, and nothing synchronises (RayStore.next's contract).  On the CPU next() answers from
+    host_batch.  seek(draw) sets the number of the next draw; last_ids holds the pixel ids of the last batch (int64)."""
+
+    def __init__(self, images, poses, H, W, focal, ndc, device, seed=0):
+        images, poses, self.H, self.W, self.focal = _check(images, poses, H, W, focal)
+        self.device = torch.device(device)
+        self.ndc, self.seed = int(bool(ndc)), int(seed) & M64
+        self.n_img = images.shape[0]
+        self.M = self.n_img * self.H * self.W
+        self.nbytes = self.M * 12 + self.n_img * 48
+        self.draw = 0
+        self.last_ids = None
+        self._buf, self._k = [None, None], 0
+        if self.device.type == "cuda":
+            from . import _lib
+            if self.device.index is None:
+                self.device = torch.device("cuda", torch.cuda.current_device())
+            free, _total = torch.cuda.mem_get_info(self.device)
+            if self.nbytes > 0.8 * free:
+                raise MemoryError("PixelBatcher: %d images of %d x %d need %.2f GB, more than 80 %% of the %.2f GB free on %s" %
+                                  (self.n_img, self.H, self.W, self.nbytes / 1e9, free / 1e9, self.device))
+            self._lib, self._L = _lib, _lib.load()
+        self.images = images.to(self.device).contiguous()
+        self.poses = poses.to(self.device).contiguous()
+
+    def describe(self):
+        return "%d pixels of %d images %d x %d, %.3f GB on %s" % (self.M, self.n_img, self.H, self.W, self.nbytes / 1e9, self.device)
+
+    def epoch(self):
+        """The epoch the next draw belongs to."""
+        return self.draw // self.M
+
+    def seek(self, draw):
+        if draw < 0:
+            raise ValueError("PixelBatcher.seek: negative draw")
+        self.draw = int(draw)
+
+    def next(self, n):
+        n = int(n)
+        if self.device.type != "cuda":
+            o, d, v, t, ids = host_batch(self.images, self.poses, self.H, self.W, self.focal, self.ndc, self.seed, self.draw, n)
+        else:
+            k = self._k
+            if self._buf[k] is None or self._buf[k][0].shape[0] != n:
+                # (new tensors: the ones handed out two calls ago stay the caller's; the allocator is stream-ordered)
+                self._buf[k] = tuple(torch.empty(n, 3, dtype=torch.float32, device=self.device) for _ in range(4)) + (
+                    torch.empty(n, dtype=torch.int64, device=self.device),)
+            o, d, v, t, ids = self._buf[k]
+            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+            with torch.cuda.device(self.device):
+                self._lib.check(self._L.r2l_pixel_batch(_p(self.images), _p(self.poses), self.n_img, self.H, self.W, self.focal,
+                                                        self.ndc, self.draw, n, self.seed, _p(o), _p(d), _p(v), _p(t), _p(ids),
+                                                        stream), "r2l_pixel_batch")
+            self._k ^= 1
+        self.draw += n
+        self.last_ids = ids
+        return o, d, v, t

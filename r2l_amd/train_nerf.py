@@ -5,6 +5,12 @@ Each iteration draws one training image (np.random.choice(i_train)), centre-crop
 pixels without replacement (rand_pixel, helpers:385-392) and runs one TeacherTrainer step (r2l_amd/teacher_train.py) at the
 learning rate of lr_schedule.  The numpy and torch generators are re-seeded from (R2L_SEED, iteration) at every iteration, so a
 run is reproducible and a --resume from a checkpoint of iteration k continues exactly as the uninterrupted run would.
+With --r2l_batching and no --no_batching the run is the reference's batching mode (main.py:1137-1162, 1199-1210) instead:
+iteration i takes draws (i-1)*N_rand .. i*N_rand - 1 of the pixel sampler of r2l_amd/pixel_batch.py, seeded with R2L_SEED — N_rand
+pixels of all training images, without replacement inside an epoch, no centre crop.  Two differences from the reference: every
+batch has N_rand rays (one that reaches the end of an epoch goes on with the first draws of the next; the reference hands out one
+short batch, then reshuffles), and the permutation is the keyed bijection of csrc/r2l_perm.h, not numpy's.  The sampler has no
+state, so --resume seeks to start*N_rand and continues bit for bit.
 Checkpoints are the reference's layout (checkpoint.save_ckpt, model_name='nerf'): utils/create_data.py --teacher_ckpt and
 main.py --model_name nerf --render_only read them unchanged.
 """
@@ -19,6 +25,7 @@ from .checkpoint import load_ckpt, save_ckpt
 from .driver import apply_arithmetic, create_nerf_teacher, init_distributed, render_path
 from .logger import Logger
 from .options import parse_args, validate_accelerated
+from .pixel_batch import PixelBatcher
 from .render import get_rays, ndc_rays
 from .teacher_train import MAX_SAMPLES, TeacherTrainer
 from .train_step import lr_schedule
@@ -29,8 +36,9 @@ def validate_teacher_training(args):
     validate_accelerated(args)
     if int(os.environ.get("WORLD_SIZE", "1")) > 1:
         raise NotImplementedError("teacher training runs on one GPU (WORLD_SIZE > 1 is not supported)")
-    if not args.no_batching:
-        raise NotImplementedError("teacher training implements images mode with --no_batching (use_batching is out of scope)")
+    if not args.no_batching and not args.r2l_batching:
+        raise NotImplementedError("teacher training implements images mode with --no_batching; use_batching, the reference's "
+                                  "default, needs the switch --r2l_batching (config key r2l_batching = True)")
     if args.r2l_precision not in ("auto", "fp32_mfma"):
         raise NotImplementedError("teacher training is exact fp32 (--r2l_precision auto | fp32_mfma), got %s" % args.r2l_precision)
     if not args.use_viewdirs or args.N_importance < 0:
@@ -128,16 +136,33 @@ def main(argv=None):
         return save_ckpt(path, i, coarse, trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, model_name="nerf",
                          model_fine=fine, r2l_config=r2l_config)
 
+    batcher = None
+    if not args.no_batching:  # (validate_teacher_training: only with --r2l_batching)
+        batcher = PixelBatcher(torch.as_tensor(images[i_train]), poses[i_train], H, W, focal, scene.ndc, device,
+                               seed=int(os.environ.get("R2L_SEED", "0")))
+        batcher.seek(start * args.N_rand)
+        logger.info("[Config] Batching mode (--r2l_batching): N_rand %d of M = %s; draw %d, in epoch %d" %
+                    (args.N_rand, batcher.describe(), batcher.draw, batcher.epoch()))
+        if args.precrop_iters > 0:
+            logger.info("[Config] precrop_iters = %d is ignored: batching mode has no centre crop" % args.precrop_iters)
+
     history, lr, t0 = [], args.lrate, time.time()
     for i in range(start + 1, args.N_iters + 1):
         _seed(i)
-        rays_o, rays_d, viewdirs, target = sample_batch(i, args, images, poses, i_train, H, W, focal)
-        if i == start + 1 and i < args.precrop_iters:
-            dH, dW = int(H // 2 * args.precrop_frac), int(W // 2 * args.precrop_frac)
-            logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (2 * dH, 2 * dW, args.precrop_iters))
         lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
-        rays_o, rays_d = device_rays(rays_o, rays_d, H, W, focal, scene.ndc, device)
-        loss, psnr = trainer.step(rays_o, rays_d, viewdirs.to(device), near, far, target.to(device), lr)
+        if batcher is not None:
+            a = batcher.draw
+            rays_o, rays_d, viewdirs, target = batcher.next(args.N_rand)
+            for e in range(-(-a // batcher.M), (batcher.draw - 1) // batcher.M + 1):  # the epochs whose first draw is in this batch
+                logger.info("[TRAIN] Iter %d: epoch %d begins (draw %d)" % (i, e, e * batcher.M))
+        else:
+            rays_o, rays_d, viewdirs, target = sample_batch(i, args, images, poses, i_train, H, W, focal)
+            if i == start + 1 and i < args.precrop_iters:
+                dH, dW = int(H // 2 * args.precrop_frac), int(W // 2 * args.precrop_frac)
+                logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (2 * dH, 2 * dW, args.precrop_iters))
+            rays_o, rays_d = device_rays(rays_o, rays_d, H, W, focal, scene.ndc, device)
+            viewdirs, target = viewdirs.to(device), target.to(device)
+        loss, psnr = trainer.step(rays_o, rays_d, viewdirs, near, far, target, lr)
         history.append((loss, psnr))
         if i % args.i_print == 0:
             logger.info("[TRAIN] Iter %d Loss %.4f PSNR %.4f LR %.8f Time %.1fs" % (i, loss, psnr, lr, time.time() - t0))
@@ -158,4 +183,4 @@ def main(argv=None):
             path = save(os.path.join(logger.weights_path, name), i, lr)
             logger.info('Iter %d Save checkpoint: "%s".' % (i, path))
     return {"trainer": trainer, "logger": logger, "history": history, "coarse": coarse, "fine": fine,
-            "r2l_config": r2l_config}
+            "r2l_config": r2l_config, "batcher": batcher}

@@ -5,12 +5,23 @@ and the same step as torch fp32 autograd of the oracle's functions on the same G
 
 FLOP model (DESIGN.md §teacher training): forward 1.187 MFLOP, dX chain ~1.12 MFLOP, dW 1.187 MFLOP per point; the fraction
 is of the 157.3 TFLOP/s fp32-MFMA peak.  The per-kernel split comes from a separate run of this script under
-`rocprofv3 --kernel-trace --stats -- python tools/teacher_train_time.py`."""
+`rocprofv3 --kernel-trace --stats -- python tools/teacher_train_time.py`.
+
+  python tools/teacher_train_time.py --batching [--steps 20] [--warmup 3] [--out profiles/teacher_batching.txt]
+
+The data path of utils/train_nerf.py per batch, images mode against batching mode (--r2l_batching), on synthetic scenes of the
+lego size (100 views of 400 x 400, N_rand 1024) and the fern size (17 views of 378 x 504, NDC, N_rand 1024 and 4096):
+  host path      : sample_batch + device_rays + the copies of viewdirs and target, synchronised (what images mode does per step)
+  PixelBatcher   : next(N_rand), synchronised per call, and back to back (one synchronisation after all calls)
+  whole step     : either of them followed by TeacherTrainer.step (which reads the loss back, so every step is synchronised)
+Wall-clock ms (time.perf_counter) around synchronised work; one line per scene to stdout and to --out."""
 import argparse
 import json
 import os
 import sys
+import time
 
+import numpy as np
 import torch
 
 sys.path.insert(0, os.path.dirname(os.path.dirname(os.path.abspath(__file__))))
@@ -40,14 +51,93 @@ def timed(fn, steps, warmup):
     return a.elapsed_time(b) / steps
 
 
+def wall(fn, steps, warmup, sync_each=True):
+    """ms per call of fn, wall clock; synchronised after every call, or once after all of them."""
+    for _ in range(warmup):
+        fn()
+    torch.cuda.synchronize()
+    t0 = time.perf_counter()
+    for _ in range(steps):
+        fn()
+        if sync_each:
+            torch.cuda.synchronize()
+    torch.cuda.synchronize()
+    return (time.perf_counter() - t0) / steps * 1e3
+
+
+def forward_facing_poses(n, rng):
+    """[n,3,4]: rotations <= 0.35 rad about a random axis, centres within +-1 (z within +-0.3): every ray goes down -z."""
+    out = []
+    for _ in range(n):
+        axis = rng.randn(3)
+        axis /= np.linalg.norm(axis)
+        ang = rng.uniform(-.35, .35)
+        K = np.array([[0, -axis[2], axis[1]], [axis[2], 0, -axis[0]], [-axis[1], axis[0], 0]])
+        R = np.eye(3) + np.sin(ang) * K + (1 - np.cos(ang)) * (K @ K)
+        out.append(np.concatenate([R, (rng.uniform(-1, 1, 3) * np.array([1., 1., .3]))[:, None]], 1))
+    return np.stack(out).astype(np.float32)
+
+
+def batching(a):
+    from r2l_amd import train_nerf
+    from r2l_amd.pixel_batch import PixelBatcher
+    from r2l_amd.teacher_train import TeacherTrainer
+    dev = torch.device("cuda")
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    rng = np.random.RandomState(0)
+    scenes = [("lego-like", 100, 400, 400, 555.5555155968841, False, 2., 6., 128, (1024,)),
+              ("fern-like", 17, 378, 504, 407.5657, True, 0., 1., 64, (1024, 4096))]
+    lines = ["teacher training, data path per batch: images mode (host) against batching mode (r2l_pixel_batch); %s; steps %d, "
+             "warmup %d; wall-clock ms" % (torch.cuda.get_device_name(0), a.steps, a.warmup)]
+    for name, n, H, W, focal, ndc, near, far, NI, n_rands in scenes:
+        images = rng.rand(n, H, W, 3).astype(np.float32)
+        poses = (forward_facing_poses(n, rng) if ndc else
+                 np.stack([O.pose_spherical(-180. + 360. * k / n, -30., 4.)[:3, :4] for k in range(n)]).astype(np.float32))
+        i_train = np.arange(n)
+        tr = TeacherTrainer(make(csd), make(fsd), N_samples=64, N_importance=NI, perturb=1., white_bkgd=not ndc, raw_noise_std=0.)
+        pb = PixelBatcher(images, poses, H, W, focal, ndc, dev, seed=0)
+        for N_rand in n_rands:
+            args = argparse.Namespace(N_rand=N_rand, precrop_iters=0, precrop_frac=.5)
+            it = [0]
+
+            def host():
+                it[0] += 1
+                train_nerf._seed(it[0])
+                o, d, v, t = train_nerf.sample_batch(it[0], args, images, poses, i_train, H, W, focal)
+                o, d = train_nerf.device_rays(o, d, H, W, focal, ndc, dev)
+                return o, d, v.to(dev), t.to(dev)
+
+            def step(batch):
+                o, d, v, t = batch()
+                tr.step(o, d, v, near, far, t, 5e-4)
+
+            r = {"scene": name, "views": n, "H": H, "W": W, "ndc": int(ndc), "N_rand": N_rand, "bank_MB": round(pb.nbytes / 1e6, 1),
+                 "host_path_ms": round(wall(host, a.steps, a.warmup), 3),
+                 "pixel_batcher_ms": round(wall(lambda: pb.next(N_rand), a.steps, a.warmup), 3),
+                 "pixel_batcher_back_to_back_ms": round(wall(lambda: pb.next(N_rand), 10 * a.steps, a.warmup, sync_each=False), 4),
+                 "step_images_mode_ms": round(wall(lambda: step(host), a.steps, a.warmup), 3),
+                 "step_batching_mode_ms": round(wall(lambda: step(lambda: pb.next(N_rand)), a.steps, a.warmup), 3)}
+            lines.append(json.dumps(r))
+            print(lines[-1], flush=True)
+        del tr, pb
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
     ap.add_argument("--steps", type=int, default=20)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no_baseline", action="store_true")
+    ap.add_argument("--batching", action="store_true", help="time the data path: images mode's host path against PixelBatcher.next")
+    ap.add_argument("--out", default=os.path.join("profiles", "teacher_batching.txt"), help="where --batching writes its lines")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "teacher_train_time needs the GPU"
+    if a.batching:
+        return batching(a)
     from r2l_amd.teacher_train import TeacherTrainer
     csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
     tr = TeacherTrainer(make(csd), make(fsd), perturb=1., white_bkgd=True)
