@@ -332,6 +332,14 @@ int r2l_sample_pdf_sort(const float* z, const float* weights, const float* u, in
  * counter = { lo32(i>>2), hi32(i>>2), lo32(stream_id), hi32(stream_id) },
  * key = { lo32(seed), hi32(seed) }.  Pure function of (seed, stream_id, i). */
 int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream);
+/* out[i] = scale * n_i (one fp32 rounding of the product), n_i standard normal by Box-Muller on the Philox4x32-10 block
+ * b = i >> 2 of stream (seed, stream_id) — counter and key exactly as r2l_draw_uniform; words w0..w3:
+ *   u1 = ((w0 >> 8) + 1) * 2^-24 in (0,1],  u2 = (w1 >> 8) * 2^-24 in [0,1):  r = sqrt(-2 ln u1)
+ *   element 4b+0 = r cos(2 pi u2), 4b+1 = r sin(2 pi u2); elements 4b+2, 4b+3 the same from (w2, w3).
+ * |n_i| <= sqrt(48 ln 2) = 5.77.  Pure function of (seed, stream_id, i).  The angle is evaluated as sincospi(2 u2) (2 u2 is exact);
+ * every element is within 6 * 2^-24 * r of the real-number value (tests/test_teacher_step_gpu.py).  n == 0 is a successful no-op;
+ * n < 0 or a NULL out is hipErrorInvalidValue before any launch. */
+int r2l_draw_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, float scale, void* stream);
 
 /* Rays of K whole frames (helpers:231-257 get_rays + the viewdirs of create_data.py:138-147), one launch.
  * Ray r = (k*H + row)*W + col.  focal_dev: K device floats or NULL (focal for all).
@@ -483,6 +491,61 @@ int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard
 int r2l_pixel_batch(const float* images /*dev [n_img,H,W,3]*/, const float* c2w /*dev [n_img,3,4]*/, int n_img, int H, int W,
                     float focal, int ndc, int64_t draw0, int64_t n_draw, uint64_t seed, float* rays_o, float* rays_d,
                     float* viewdirs, float* target /*each [n_draw,3]*/, int64_t* ids_out /*[n_draw] or NULL*/, void* stream);
+
+/* ---- one teacher training step in one library call ------------------------------------------------------------------------
+ * What r2l_amd/teacher_train.py (TeacherTrainer.forward_backward + adam) assembles per step from the stages above, behind the C
+ * ABI (csrc/r2l_teacher_step.hip): a pure function of (weights, optimizer state, batch, seed, step).  Those very kernels, in this
+ * order, enqueued on `stream` with no allocation and no host synchronisation; the call keeps no state:
+ *   r2l_stratified_z (near / far shared, nf_stride 0) -> coarse r2l_teacher_mlp_train -> r2l_raw2outputs (weights) ->
+ *   r2l_sample_pdf_sort -> fine r2l_teacher_mlp_train -> r2l_raw2outputs_backward + r2l_teacher_backward + r2l_loss_finish of the
+ *   fine net, then of the coarse net -> loss_out -> r2l_adam_step over [coarse | fine] -> r2l_pack_teacher of both nets.
+ * N_importance == 0: the coarse net alone (no sampling, no fine pass); wstream_fine must be NULL exactly then.
+ * params / grads / exp_avg / exp_avg_sq: n_nets * r2l_teacher_param_count() floats, [coarse | fine] (n_nets = 2 with
+ * N_importance > 0, else 1); grads is overwritten.  On entry wstream_coarse / wstream_fine (r2l_teacher_stream_floats() each, zero-
+ * filled once after allocation) must be packed from params (r2l_pack_teacher); on exit they are packed from the UPDATED params: a
+ * test-set render, or the next step, follows directly.  rays_o / rays_d / viewdirs / target: device [N_rand,3].
+ * loss_out (device [2]): loss_out[0] = mse_fine + mse_coarse (one fp32 add, fine first; the coarse mse alone without a fine net),
+ * loss_out[1] = psnr of the fine net (of the coarse net when it is alone), each mse / psnr as r2l_loss_finish with 1/(3 N_rand).
+ * Adam: r2l_adam_step(lr, beta1, beta2, eps, step, grad_scale 1); its bias corrections take min(step, 2^31 - 1).
+ *
+ * Draws: made inside the call, stream_id = 2^62 + 4*step + k of `seed` (the frames call uses stream ids 2*frame_id, far below):
+ *   k = 0  t_rand[r,s]      element r*N_samples + s                    of r2l_draw_uniform        (perturb == 1)
+ *   k = 1  u[r,i]           element r*N_importance + i                 of r2l_draw_uniform        (perturb == 1, N_importance > 0)
+ *   k = 2  coarse noise     element r*N_samples + s                    of r2l_draw_normal, scale = raw_noise_std   (raw_noise_std > 0)
+ *   k = 3  fine noise       element r*(N_samples + N_importance) + j   of r2l_draw_normal, scale = raw_noise_std   (.. and N_importance > 0)
+ * perturb == 0: no t_rand, and u is the one shared row u_det (u_stride 0), required exactly then (with N_importance > 0).
+ * raw_noise_std == 0: no noise buffers, the kernels receive NULL.  The noise of a net is the same in its r2l_raw2outputs and its
+ * r2l_raw2outputs_backward.
+ *
+ * work: 16-byte aligned, r2l_teacher_step_work_floats(d) floats (-1 with r2l_last_error for an invalid descriptor).  With
+ * R = N_rand, S = N_samples, T = S + N_importance, every part rounded up to a multiple of 1024 floats (4 KiB), it holds
+ *   near/far (2), z [R,S], coarse raw [R,S,4], coarse stash (r2l_teacher_stash_floats(R*S)), rgb [R,3] + disp, acc, depth [R] of
+ *   the coarse r2l_raw2outputs, draw [R,T,4], sqerr [R] and mse/psnr (2) per net, the scratch of r2l_teacher_backward
+ *   (r2l_teacher_train_work_floats(R*T)), t_rand [R,S] (perturb), coarse noise [R,S] (raw_noise_std > 0), and with N_importance > 0:
+ *   weights [R,S], z_samples [R,N_importance], z_all [R,T], fine raw [R,T,4], fine stash (r2l_teacher_stash_floats(R*T)),
+ *   u [R,N_importance] (perturb), fine noise [R,T] (raw_noise_std > 0).
+ * hipErrorInvalidValue (with r2l_last_error naming the field or pointer) before any launch: N_rand < 1, the sample limits of
+ * r2l_teacher_frame_desc, perturb / white_bkgd not 0 or 1, raw_noise_std < 0 or not finite, near >= far, step < 1 or >= 2^60,
+ * non-zero reserved, a NULL required pointer, a wstream_fine that does not match N_importance (NULL with N_importance > 0, or
+ * given with N_importance == 0), a missing u_det, an unaligned work.  r2l_amd/teacher_train.py (TeacherTrainer.fused_step) is the worked example. */
+typedef struct r2l_teacher_step_desc {
+    int N_rand;                     /* rays of this step, >= 1 */
+    int N_samples, N_importance;    /* limits as r2l_teacher_frame_desc; N_importance == 0: coarse net only */
+    int perturb, white_bkgd;        /* 0 | 1 */
+    float raw_noise_std;            /* >= 0 */
+    float near, far;                /* near < far; one pair for all rays */
+    float lr, beta1, beta2, eps;
+    int64_t step;                   /* 1-based iteration = Adam's step count; 1 <= step < 2^60 */
+    uint64_t seed;
+    int reserved[4];                /* must be 0 */
+} r2l_teacher_step_desc;
+int64_t r2l_teacher_step_work_floats(const r2l_teacher_step_desc* d);   /* -1: invalid descriptor */
+int r2l_teacher_train_step(const r2l_teacher_step_desc* d,
+        const float* rays_o, const float* rays_d, const float* viewdirs, const float* target, /* dev, each [N_rand,3] */
+        const float* ttab, const float* u_det,      /* as r2l_teacher_frames_cfg; u_det needed iff perturb==0 && N_importance>0 */
+        float* params, float* grads, float* exp_avg, float* exp_avg_sq,   /* [coarse | fine], r2l_teacher_param_count() each */
+        float* wstream_coarse, float* wstream_fine, /* wstream_fine NULL iff N_importance == 0 */
+        float* loss_out /* dev [2]: loss, psnr */, float* work, void* stream);
 
 /* ---- frame writer (host threads; test-set evaluation) ------------------------------------------------------------------
  * Replaces `imageio.imwrite(filename, to8b(rgb))` of every prediction / ground-truth frame in render_path (main.py:337-344):

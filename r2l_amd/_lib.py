@@ -38,6 +38,16 @@ class TeacherFrameDesc(ctypes.Structure):
 _descp = ctypes.POINTER(TeacherFrameDesc)
 
 
+class TeacherStepDesc(ctypes.Structure):
+    """r2l_teacher_step_desc of include/r2l_hip.h (r2l_teacher_train_step)."""
+    _fields_ = [("N_rand", _i), ("N_samples", _i), ("N_importance", _i), ("perturb", _i), ("white_bkgd", _i), ("raw_noise_std", _f),
+                ("near", _f), ("far", _f), ("lr", _f), ("beta1", _f), ("beta2", _f), ("eps", _f), ("step", _l),
+                ("seed", ctypes.c_uint64), ("reserved", _i * 4)]
+
+
+_stepp = ctypes.POINTER(TeacherStepDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -104,6 +114,7 @@ SIGNATURES = {
     "r2l_raw2outputs": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_sample_pdf_sort": (_i, [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _p]),
     "r2l_draw_uniform": (_i, [_p, _l, ctypes.c_uint64, ctypes.c_uint64, _p]),
+    "r2l_draw_normal": (_i, [_p, _l, ctypes.c_uint64, ctypes.c_uint64, _f, _p]),
     "r2l_ndc_rays": (_i, [_p, _p, _l, _i, _i, _f, _f, _p, _p, _p]),
     "r2l_frame_rays": (_i, [_p, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p]),
     "r2l_teacher_frames_work_floats": (_l, [_descp]),
@@ -118,6 +129,8 @@ SIGNATURES = {
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
     "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
+    "r2l_teacher_step_work_floats": (_l, [_stepp]),
+    "r2l_teacher_train_step": (_i, [_stepp] + [_p] * 15),
     "r2l_png_writer_open": (_i, [_i, _i, _p]),
     "r2l_png_writer_submit": (_i, [_p, ctypes.c_char_p, _p, _i, _i, _i, _p, _p]),
     "r2l_png_writer_wait": (_i, [_p, _l]),

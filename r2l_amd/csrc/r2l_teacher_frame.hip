@@ -4,6 +4,8 @@
 //   r2l_ndc_rays          : ndc_rays (helpers:260-279) of explicit rays; the same arithmetic inside the frames' ray kernel
 //   r2l_draw_uniform      : counter-based uniforms (Philox4x32-10), a pure function of (seed, stream_id, element index): every
 //                           host of the C ABI draws the same t_rand / u, whatever its grouping of frames or chunks of rays
+//   r2l_draw_normal       : standard normals by Box-Muller on the same Philox blocks (the sigma noise of teacher training,
+//                           csrc/r2l_teacher_step.hip)
 //   r2l_teacher_frames_cfg: rays -> stratified z -> coarse MLP -> raw2outputs -> sample_pdf + sort -> fine MLP -> raw2outputs,
 //                           the EXISTING kernels of those stages enqueued back to back on the caller's stream through one work
 //                           buffer the caller sized once: no allocation, no host synchronisation
@@ -41,6 +43,37 @@ __global__ void r2l_draw_uniform_kernel(float* __restrict__ out, int64_t n, int6
         for (int w = 0; w < 4; ++w) {
             const int64_t j = (int64_t)(b << 2) + w - i0;
             if (j >= 0 && j < n) out[j] = (float)(c[w] >> 8) * 5.9604644775390625e-08f;  // 2^-24: exact, in [0, 1)
+        }
+    }
+}
+
+// out[i] = scale * n_i, i < n: standard normals by Box-Muller on the same Philox blocks (include/r2l_hip.h).  Thread t owns block t =
+// elements 4 t .. 4 t + 3: two (u1, u2) pairs, each giving r cos, r sin.  The angle is 2 pi u2 with u2 a multiple of 2^-24: 2 u2 is
+// exact and sincospif reduces it exactly, where fp32(2 pi) * u2 would carry the rounding of the product into the angle (up to
+// pi * 2^-24 absolute, which alone is 3 * 2^-24 r in the result; the whole kernel measures 2.4 * 2^-24 r).  logf and sqrtf are the accurate library forms (1 ulp /
+// correctly rounded): a dozen of them per 16 bytes written is nothing beside the step these draws feed, and the fast forms
+// (v_log_f32 is ~1 ulp in log2 only, which the 0.693 factor and the argument near 1 do not preserve) would miss the tail.
+__global__ void r2l_draw_normal_kernel(float* __restrict__ out, int64_t n, unsigned long long seed, unsigned long long stream_id,
+                                       float scale) {
+    const int64_t nb = (n + 3) >> 2;
+    for (int64_t t = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; t < nb; t += (int64_t)gridDim.x * blockDim.x) {
+        unsigned c[4] = {(unsigned)t, (unsigned)((unsigned long long)t >> 32), (unsigned)stream_id, (unsigned)(stream_id >> 32)};
+        philox4x32_10(c, (unsigned)seed, (unsigned)(seed >> 32));
+        float v[4];
+#pragma unroll
+        for (int p = 0; p < 2; ++p) {
+            const float u1 = (float)((c[2 * p] >> 8) + 1u) * 5.9604644775390625e-08f;  // (0, 1]: exact
+            const float a = (float)(c[2 * p + 1] >> 8) * 1.1920928955078125e-07f;      // 2 u2 in [0, 2): exact
+            const float r = sqrtf(-2.f * logf(u1));
+            float sn, cs;
+            sincospif(a, &sn, &cs);
+            v[2 * p] = r * cs;
+            v[2 * p + 1] = r * sn;
+        }
+#pragma unroll
+        for (int w = 0; w < 4; ++w) {
+            const int64_t j = (t << 2) + w;
+            if (j < n) out[j] = scale * v[w];
         }
     }
 }
@@ -258,6 +291,16 @@ extern "C" int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t s
     if (n == 0) return 0;
     R2L_REQUIRE(out != nullptr, "r2l_draw_uniform: out is NULL");
     return launch_draw(out, n, 0, seed, stream_id, (hipStream_t)stream);
+}
+
+extern "C" int r2l_draw_normal(float* out, int64_t n, uint64_t seed, uint64_t stream_id, float scale, void* stream) {
+    R2L_REQUIRE(n >= 0, "r2l_draw_normal: n is negative");
+    if (n == 0) return 0;
+    R2L_REQUIRE(out != nullptr, "r2l_draw_normal: out is NULL");
+    hipLaunchKernelGGL(r2l_draw_normal_kernel, dim3(grid_for((n + 3) / 4)), dim3(256), 0, (hipStream_t)stream, out, n,
+                       (unsigned long long)seed, (unsigned long long)stream_id, scale);
+    R2L_CHECK(hipGetLastError());
+    return 0;
 }
 
 extern "C" int r2l_frame_rays(const float* c2w_dev, const float* focal_dev, float focal, int K, int H, int W, float* rays_o,

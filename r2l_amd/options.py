@@ -67,6 +67,10 @@ FLAGS = {
     # from all training images) through a pixel sampler on the device (r2l_amd/pixel_batch.py, r2l_pixel_batch); opt-in — without
     # the switch utils/train_nerf.py refuses a run without --no_batching as it always did.  main.py / create_data.py ignore it
     "r2l_batching": ("flag", False),
+    # teacher training with one library call per iteration (r2l_teacher_train_step): t_rand, u and the sigma noise are drawn on the
+    # device from Philox streams of (R2L_SEED, iteration) instead of torch's generator, and the loop reads the loss only where it
+    # prints, tests or ends; opt-in, GPU only.  main.py / create_data.py ignore it
+    "r2l_fused_step": ("flag", False),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),

@@ -451,6 +451,18 @@ def draw_uniform(n, seed, stream_id, device):
     return out
 
 
+def draw_normal(n, seed, stream_id, device, scale=1.):
+    """n normals times `scale`: elements 0..n-1 of r2l_draw_normal's Box-Muller on the Philox4x32-10 stream (seed, stream_id)."""
+    device = torch.device(device)
+    if device.type != "cuda":
+        raise NotImplementedError("draw_normal runs on the GPU only (HIP kernels of libr2l_hip.so)")
+    out = torch.empty(int(n), dtype=torch.float32, device=device)
+    with torch.cuda.device(device):
+        _lib.check(_lib.load().r2l_draw_normal(_ptr(out), int(n), int(seed) & (2**64 - 1), int(stream_id) & (2**64 - 1),
+                                               float(scale), _stream()), "r2l_draw_normal")
+    return out
+
+
 def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samples, N_importance, perturb, white_bkgd, seed,
                   frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None):
     """K teacher frames from K poses in ONE library call (r2l_teacher_frames_cfg): what render(H, W, focal_k, c2w=c2ws[k],

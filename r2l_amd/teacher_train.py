@@ -8,6 +8,8 @@ moments.  On ROCm tensors one step is, in libr2l_hip.so (include/r2l_hip.h, "NeR
 On CPU modules the same step is torch autograd over render.render_rays' CPU branch and torch.optim.Adam (plumbing only:
 it lets the host loop be tested without a GPU).
 """
+import ctypes
+
 import torch
 
 from . import _lib
@@ -144,6 +146,47 @@ class TeacherTrainer:
         self.adam(lr)
         loss, psnr = out.tolist()
         return loss, psnr
+
+    def fused_step(self, rays_o, rays_d, viewdirs, near, far, target, lr, step, seed, loss_out=None):
+        """One optimisation step in ONE library call (r2l_teacher_train_step, include/r2l_hip.h): the stages of step() in the same
+        order and by the same kernels, with t_rand, u and the sigma noise drawn on the device from the Philox streams
+        2^62 + 4*step + k of `seed` — a pure function of (weights, optimizer state, batch, seed, step).  near / far: numbers (one pair
+        for all rays).  step: the 1-based iteration, Adam's step count.  Returns the device tensor [loss, psnr] (loss_out, a
+        contiguous fp32 [2], when given) WITHOUT reading it: nothing here synchronises.  GPU only."""
+        if not self.on_gpu:
+            raise NotImplementedError("fused_step runs on the GPU only (r2l_teacher_train_step of libr2l_hip.so)")
+        f32 = dict(dtype=torch.float32, device=self.flat.device)
+        rays_o, rays_d, viewdirs, target = [t.to(**f32).contiguous() for t in (rays_o, rays_d, viewdirs, target)]
+        for eng in self.engines:
+            eng.ensure_packed()
+        fine = len(self.nets) > 1
+        desc = _lib.TeacherStepDesc(N_rand=rays_o.shape[0], N_samples=self.N_samples, N_importance=self.N_importance if fine else 0,
+                                    perturb=int(self.perturb > 0.), white_bkgd=int(self.white_bkgd),
+                                    raw_noise_std=self.raw_noise_std, near=float(near), far=float(far), lr=float(lr),
+                                    beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=int(step),
+                                    seed=int(seed) & (2**64 - 1))
+        n_work = self.lib.r2l_teacher_step_work_floats(ctypes.byref(desc))
+        if n_work < 0:
+            _lib.check(1, "r2l_teacher_step_work_floats")
+        work = self._buf("step_work", n_work)
+        tabs = self._bufs.get("step_tabs")
+        if tabs is None:  # the tables of _coarse_z and sample_pdf_sort, by the same torch expressions
+            t = torch.linspace(0., 1., steps=self.N_samples)
+            u_det = torch.linspace(0., 1., steps=self.N_importance).to(**f32).contiguous() if fine else None
+            tabs = self._bufs["step_tabs"] = (torch.cat([t, 1. - t]).to(**f32), u_det)
+        if loss_out is None:
+            loss_out = self.loss_out
+        if loss_out.dtype != torch.float32 or loss_out.numel() != 2 or not loss_out.is_contiguous() or loss_out.device != self.flat.device:
+            raise ValueError("fused_step: loss_out is a contiguous fp32 tensor of 2 elements on the trainer's device")
+        _lib.check(self.lib.r2l_teacher_train_step(ctypes.byref(desc), _ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(target),
+                                                   _ptr(tabs[0]), _ptr(tabs[1]), _ptr(self.flat), _ptr(self.grads), _ptr(self.exp_avg),
+                                                   _ptr(self.exp_avg_sq), _ptr(self.engines[0].wstream),
+                                                   _ptr(self.engines[1].wstream if fine else None), _ptr(loss_out), _ptr(work),
+                                                   _stream()), "r2l_teacher_train_step")
+        # the call re-packed both streams from the weights it wrote in place: the engines' version stamps (taken by ensure_packed
+        # above; a kernel bumps no tensor version) stay valid, nothing re-packs before the next launch
+        self.step_count = int(step)
+        return loss_out
 
     def _cpu_step(self, rays_o, rays_d, viewdirs, near, far, target, lr, t_rand, u):
         R = rays_o.shape[0]

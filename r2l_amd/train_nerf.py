@@ -11,6 +11,11 @@ pixels of all training images, without replacement inside an epoch, no centre cr
 batch has N_rand rays (one that reaches the end of an epoch goes on with the first draws of the next; the reference hands out one
 short batch, then reshuffles), and the permutation is the keyed bijection of csrc/r2l_perm.h, not numpy's.  The sampler has no
 state, so --resume seeks to start*N_rand and continues bit for bit.
+With --r2l_fused_step (GPU only) an iteration is ONE library call, TeacherTrainer.fused_step: the same kernels in the same order, but
+t_rand, u and the sigma noise of raw_noise_std come from the Philox streams 2^62 + 4*i + k of R2L_SEED (include/r2l_hip.h) instead of
+torch's generator, and the loss stays on the device: the host reads it where it prints, tests and ends, never per iteration.  The
+step has no state, so --resume continues bit for bit; batching mode then skips the per-iteration re-seeding (nothing there draws
+from the host generators), images mode keeps it for its numpy pixel choice.
 Checkpoints are the reference's layout (checkpoint.save_ckpt, model_name='nerf'): utils/create_data.py --teacher_ckpt and
 main.py --model_name nerf --render_only read them unchanged.
 """
@@ -102,6 +107,9 @@ def main(argv=None):
     args.model_name = "nerf"
     validate_teacher_training(args)
     rank, world, device = init_distributed()
+    if args.r2l_fused_step and device.type != "cuda":
+        raise NotImplementedError("--r2l_fused_step runs on the GPU only (r2l_teacher_train_step of libr2l_hip.so); this run is on "
+                                  "device '%s'" % device)
     _seed(0)
     logger = Logger(args, rank)
     scene = D.load_scene(args)
@@ -146,9 +154,21 @@ def main(argv=None):
         if args.precrop_iters > 0:
             logger.info("[Config] precrop_iters = %d is ignored: batching mode has no centre crop" % args.precrop_iters)
 
+    fused = bool(args.r2l_fused_step)
+    if fused:
+        seed = int(os.environ.get("R2L_SEED", "0"))
+        n_left = max(args.N_iters - start, 0)
+        loss_hist = torch.zeros(n_left, 2, dtype=torch.float32, device=device)  # [loss, psnr] per iteration; read where printed
+        logger.info("[Config] Fused step (--r2l_fused_step): one r2l_teacher_train_step call per iteration; t_rand, u and the sigma "
+                    "noise are the Philox streams 2^62 + 4*iter + k of seed %d (r2l_draw_uniform / r2l_draw_normal), not torch's "
+                    "generator; the loss is read at i_print, i_testset and the end" % seed)
+    else:
+        logger.info("[Config] Staged step: TeacherTrainer.step, the draws are torch's generator, re-seeded per iteration")
+
     history, lr, t0 = [], args.lrate, time.time()
     for i in range(start + 1, args.N_iters + 1):
-        _seed(i)
+        if not (fused and batcher is not None):
+            _seed(i)
         lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
         if batcher is not None:
             a = batcher.draw
@@ -162,8 +182,13 @@ def main(argv=None):
                 logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (2 * dH, 2 * dW, args.precrop_iters))
             rays_o, rays_d = device_rays(rays_o, rays_d, H, W, focal, scene.ndc, device)
             viewdirs, target = viewdirs.to(device), target.to(device)
-        loss, psnr = trainer.step(rays_o, rays_d, viewdirs, near, far, target, lr)
-        history.append((loss, psnr))
+        if fused:
+            trainer.fused_step(rays_o, rays_d, viewdirs, near, far, target, lr, step=i, seed=seed, loss_out=loss_hist[i - start - 1])
+            if i % args.i_print == 0 or (i % args.i_testset == 0 and len(i_test)):
+                loss, psnr = loss_hist[i - start - 1].tolist()
+        else:
+            loss, psnr = trainer.step(rays_o, rays_d, viewdirs, near, far, target, lr)
+            history.append((loss, psnr))
         if i % args.i_print == 0:
             logger.info("[TRAIN] Iter %d Loss %.4f PSNR %.4f LR %.8f Time %.1fs" % (i, loss, psnr, lr, time.time() - t0))
         if i % args.i_testset == 0 and len(i_test):
@@ -182,5 +207,7 @@ def main(argv=None):
             name = "ckpt_%d.tar" % i if args.save_intermediate_models else "ckpt.tar"
             path = save(os.path.join(logger.weights_path, name), i, lr)
             logger.info('Iter %d Save checkpoint: "%s".' % (i, path))
+    if fused:
+        history = [tuple(row) for row in loss_hist.tolist()]
     return {"trainer": trainer, "logger": logger, "history": history, "coarse": coarse, "fine": fine,
             "r2l_config": r2l_config, "batcher": batcher}

@@ -14,7 +14,14 @@ lego size (100 views of 400 x 400, N_rand 1024) and the fern size (17 views of 3
   host path      : sample_batch + device_rays + the copies of viewdirs and target, synchronised (what images mode does per step)
   PixelBatcher   : next(N_rand), synchronised per call, and back to back (one synchronisation after all calls)
   whole step     : either of them followed by TeacherTrainer.step (which reads the loss back, so every step is synchronised)
-Wall-clock ms (time.perf_counter) around synchronised work; one line per scene to stdout and to --out."""
+Wall-clock ms (time.perf_counter) around synchronised work; one line per scene to stdout and to --out.
+
+  python tools/teacher_train_time.py --fused [--steps 20] [--warmup 3] [--repeats 3] [--out profiles/teacher_fused_step.txt]
+
+The staged step (TeacherTrainer.step: ~25 library calls and torch ops, the loss read back every step) against the fused step
+(TeacherTrainer.fused_step: one library call, nothing read back until the end) in the same process, on a fixed batch, at 1024 rays
+(kernel-bound) and at 64 rays (where the host's share should show), 64 + 128 samples, perturb 1.  Wall-clock ms per step over
+--steps steps, --repeats times each, alternating: the spread of a path's repeats is what a difference has to exceed."""
 import argparse
 import json
 import os
@@ -126,6 +133,45 @@ def batching(a):
             f.write("\n".join(lines) + "\n")
 
 
+def fused(a):
+    from r2l_amd.teacher_train import TeacherTrainer
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    lines = ["teacher training, staged step (TeacherTrainer.step, loss read back per step) against fused step (fused_step, one "
+             "r2l_teacher_train_step call, loss read once at the end); 64 + 128 samples, perturb 1; %s; steps %d, warmup %d, "
+             "repeats %d; wall-clock ms per step" % (torch.cuda.get_device_name(0), a.steps, a.warmup, a.repeats)]
+    for R in (1024, 64):
+        g = torch.Generator().manual_seed(0)
+        o = (torch.randn(R, 3, generator=g) * .5).cuda()
+        d = torch.randn(R, 3, generator=g).cuda()
+        vd = d / d.norm(dim=-1, keepdim=True)
+        tgt = torch.rand(R, 3, generator=g).cuda()
+        tr = TeacherTrainer(make(csd), make(fsd), perturb=1., white_bkgd=True)
+        hist = torch.zeros(a.warmup + a.steps, 2, device="cuda")
+        it = [0]
+
+        def fused_step():
+            k = it[0] % hist.shape[0]
+            it[0] += 1
+            tr.fused_step(o, d, vd, 2., 6., tgt, 5e-4, step=it[0], seed=0, loss_out=hist[k])
+
+        staged, fus = [], []
+        for _ in range(a.repeats):
+            staged.append(round(wall(lambda: tr.step(o, d, vd, 2., 6., tgt, 5e-4), a.steps, a.warmup, sync_each=False), 3))
+            it[0] = 0
+            fus.append(round(wall(fused_step, a.steps, a.warmup, sync_each=False), 3))
+            hist.tolist()
+        r = {"rays": R, "points": R * 256, "staged_ms": staged, "fused_ms": fus, "staged_median_ms": float(np.median(staged)),
+             "fused_median_ms": float(np.median(fus)), "staged_spread_ms": round(max(staged) - min(staged), 3),
+             "fused_minus_staged_ms": round(float(np.median(fus) - np.median(staged)), 3)}
+        lines.append(json.dumps(r))
+        print(lines[-1], flush=True)
+        del tr
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
@@ -133,9 +179,16 @@ def main():
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--no_baseline", action="store_true")
     ap.add_argument("--batching", action="store_true", help="time the data path: images mode's host path against PixelBatcher.next")
-    ap.add_argument("--out", default=os.path.join("profiles", "teacher_batching.txt"), help="where --batching writes its lines")
+    ap.add_argument("--fused", action="store_true", help="time the staged step against the fused step (r2l_teacher_train_step)")
+    ap.add_argument("--repeats", type=int, default=3, help="--fused: timed runs per path")
+    ap.add_argument("--out", default=None, help="where --batching / --fused write their lines (default: profiles/teacher_batching.txt "
+                    "/ profiles/teacher_fused_step.txt)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "teacher_train_time needs the GPU"
+    if a.out is None:
+        a.out = os.path.join("profiles", "teacher_fused_step.txt" if a.fused else "teacher_batching.txt")
+    if a.fused:
+        return fused(a)
     if a.batching:
         return batching(a)
     from r2l_amd.teacher_train import TeacherTrainer
