@@ -424,6 +424,29 @@ int64_t r2l_flip_partial_count(int H, int W, int K);
 int r2l_flip(const float* img_a, const float* img_b, int K, int H, int W, float pixels_per_degree,
              const float* rescale_dev, float* partial, float* map, float* out, void* stream);
 
+/* out[k] = LPIPS(img_a[k], img_b[k]) with the AlexNet features, version 0.1, eval mode (lpips.LPIPS(net='alex') as
+ * main.py:359-369 calls it): scaling layer (x - shift) / scale, the five feature maps after their ReLUs (conv 3-64 11/4/2,
+ * pool 3/2, conv 64-192 5/1/2, pool 3/2, conv 192-384, 384-256, 256-256 3/1/1; zero padding after the scaling layer), per
+ * position d_l = sum_c lin_l[c] (a[c] / (|a| + 1e-10) - b[c] / (|b| + 1e-10))^2, v_l = its spatial mean, out = v_0 + .. + v_4.
+ * The convolutions are exact-fp32 MFMA implicit GEMMs, the sums run in a fixed order (no float atomics): out is
+ * bit-reproducible and the bits of a pair do not depend on how many pairs share the call.
+ * The weights are the caller's: r2l_lpips_param_floats() = 2470848 flat floats, for l = 0..4 { conv weight [Co,Ci,kh,kw] (torch
+ * order), bias [Co] }, then lin_0 .. lin_4; r2l_lpips_pack turns them once into the library-private stream wpack_dev
+ * (r2l_lpips_pack_floats() floats) that r2l_lpips reads.
+ * img_a/img_b: device [K, H, W, 3] fp32 (the layout render_path holds), values meant to lie in [-1, 1]; H, W >= 31.
+ * rescale_dev: NULL (values used as given) or a device pointer to {min_a, max_a, min_b, max_b} as r2l_flip: each image is first
+ * mapped by 2 / (max - min) * (x - min) - 1 (main.py:361-363).  work: device scratch of r2l_lpips_work_floats(K, H, W) floats
+ * (-1 for K < 1 or H, W < 31).  per_layer: NULL or device [K, 5], receives v_0 .. v_4.  maps: NULL or device
+ * [K, r2l_lpips_map_floats(H, W)], receives d_l(y, x): layer 0's [Ho, Wo] map first.  wpack and work must be 16-byte aligned.
+ * Every argument is checked before the first launch; the call allocates and synchronises nothing and keeps no state. */
+int64_t r2l_lpips_param_floats(void);
+int64_t r2l_lpips_pack_floats(void);
+int r2l_lpips_pack(const float* params_dev, float* wpack_dev, void* stream);
+int64_t r2l_lpips_work_floats(int K, int H, int W);
+int64_t r2l_lpips_map_floats(int H, int W);
+int r2l_lpips(const float* img_a, const float* img_b, int K, int H, int W, const float* rescale_dev, const float* wpack,
+              float* work, float* per_layer, float* maps, float* out, void* stream);
+
 /* ---- hard-ray pool (training data path) ---------------------------------------------------------------------------------
  * The three data movements of main.py:1325-1347 (n_hard_out random pool rows [o, d, rgb] appended to every batch) and
  * main.py:1410-1425 (the hard rays of the step enter the pool, appended until it is full, then replacing the rows that were

@@ -15,7 +15,7 @@ import torch.distributed as dist
 from . import data as D
 from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
-from .metrics import flip, img2mse, mse2psnr, ssim, to8b
+from .metrics import flip, img2mse, lpips, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import parse_args, validate_accelerated
 from .dist_utils import split_shards
@@ -377,12 +377,20 @@ def save_video(rgbs, logger, expid, iter_, tag, rank=0, world=1, device=None):
 FLIP_FRAMES_PER_LAUNCH = 64  # frame pairs per r2l_flip launch (its map is not kept: scratch is one float per 32x8 tile)
 
 
-def _flip_sum(rgbs, gts, device, world):
-    """Sum over this rank's frames of the per-frame FLIP means (fp64, 0-d, on the device), evaluated as main.py:359-379 does:
-    rendered and target stacks are each rescaled to [-1, 1] by their own extrema over ALL frames of the test set, then
-    compute_flip.  The extrema stay on the device (one all_reduce(MAX) makes them global) and go to the kernel as a pointer:
-    no host sync here."""
-    total = torch.zeros((), dtype=torch.float64, device=device)
+LPIPS_WORK_BYTES = 256 << 20  # the work buffer of one r2l_lpips launch may take this much (26 MB per 400x400 pair: 9 pairs)
+
+
+def lpips_frames_per_launch(H, W):
+    """LPIPS_FRAMES_PER_LAUNCH: frame pairs per r2l_lpips launch, from the size of its work buffer (at least 1, at most 64)."""
+    from . import _lib
+    per_pair = 4 * _lib.load().r2l_lpips_work_floats(1, H, W)
+    return max(1, min(64, LPIPS_WORK_BYTES // max(per_pair, 1)))
+
+
+def _stack_extrema(rgbs, gts, device, world):
+    """-> the target stack and {min, max} of the rendered and of the target stack over ALL frames of the test set (main.py:361-363
+    rescales both to [-1, 1] by them before LPIPS and FLIP).  The extrema stay on the device (one all_reduce(MAX) makes them
+    global) and go to the kernels as a pointer: no host sync here."""
     if gts:
         gts = torch.stack(gts, 0)
         ext = torch.stack([rgbs.max(), -rgbs.min(), gts.max(), -gts.min()]).float()
@@ -390,9 +398,26 @@ def _flip_sum(rgbs, gts, device, world):
         ext = torch.full((4,), -torch.finfo(torch.float32).max, device=device)
     if world > 1:
         dist.all_reduce(ext, op=dist.ReduceOp.MAX)
-    extrema = torch.stack([-ext[1], ext[0], -ext[3], ext[2]])
+    return gts, torch.stack([-ext[1], ext[0], -ext[3], ext[2]])
+
+
+def _flip_sum(rgbs, gts, extrema, device):
+    """Sum over this rank's frames of the per-frame FLIP means (fp64, 0-d, on the device), evaluated as main.py:359-379 does:
+    rendered and target stacks (gts, extrema: _stack_extrema) are each rescaled to [-1, 1], then compute_flip."""
+    total = torch.zeros((), dtype=torch.float64, device=device)
     for g0 in range(0, len(gts), FLIP_FRAMES_PER_LAUNCH):
         total += flip(rgbs[g0:g0 + FLIP_FRAMES_PER_LAUNCH], gts[g0:g0 + FLIP_FRAMES_PER_LAUNCH], rescale=extrema).double().sum()
+    return total
+
+
+def _lpips_sum(rgbs, gts, extrema, params, device):
+    """Sum over this rank's frames of LPIPS(AlexNet) on the same rescaled stacks (main.py:359-369), in launch groups sized by
+    the kernels' work buffer."""
+    total = torch.zeros((), dtype=torch.float64, device=device)
+    if len(gts):
+        n = lpips_frames_per_launch(*rgbs.shape[1:3]) if device.type == "cuda" else 8  # (the reference's batches of 8)
+        for g0 in range(0, len(gts), n):
+            total += lpips(rgbs[g0:g0 + n], gts[g0:g0 + n], params, rescale=extrema).double().sum()
     return total
 
 
@@ -406,12 +431,16 @@ def _runs(idx):
     return out
 
 
-def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, savedir=None, rank=0, world=1, teacher=None):
+def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, savedir=None, rank=0, world=1, teacher=None,
+                lpips_params=None):
     """Render poses[rank::world]; returns (rgbs [n,H,W,3], misc with test_loss/test_psnr/test_psnr_v2 over ALL frames)
-    and test_ssim / test_flip — main.py:189-398 (LPIPS needs network weights that are absent: out of scope).  No host
+    and test_ssim / test_flip — main.py:189-398.  No host
     sync inside the loop: metrics stay on the device, frames are written by _FrameWriter, per-frame times come from device
     events and are logged after the loop.  FLIP runs once behind the loop (_flip_sum): the reference rescales both stacks by
     their extrema over ALL frames first (main.py:361-363), so it cannot be accumulated frame by frame.
+    lpips_params = the flat AlexNet + lin weights of metrics.lpips_params (--r2l_lpips_weights: the user's files, none are
+    shipped): misc gains test_lpips (main.py:359-369, 392), evaluated behind the loop on the same rescaled stacks (_lpips_sum);
+    None: no LPIPS work at all and no such key.
     teacher = None: the R2L branch (main.py:284-324), `model` = the student.
     teacher = dict(hwf=(H, W, focal), chunk=, render_kwargs=): the `model_name in ['nerf']` branch (main.py:275-282): every
     frame is render(H, W, focal, chunk, c2w=pose[:3,:4], **render_kwargs) of r2l_amd/render.py (coarse + fine NeRF on the
@@ -512,7 +541,12 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
             logger.info("[#%d] frame, rendering done, time for this frame: %.4fs" % (i, time.time() - t0))
             account(i, rgb)
     rgbs = torch.stack(rgbs, 0) if rgbs else torch.empty(0)
-    flip_sum = _flip_sum(rgbs, gts, device, world) if gt_imgs is not None else None  # (enqueued before the host waits below)
+    flip_sum = lpips_sum = None
+    if gt_imgs is not None:  # (enqueued before the host waits below)
+        gts, extrema = _stack_extrema(rgbs, gts, device, world)
+        flip_sum = _flip_sum(rgbs, gts, extrema, device)
+        if lpips_params is not None:
+            lpips_sum = _lpips_sum(rgbs, gts, extrema, lpips_params, device)
     if writer is not None:
         writer.flush()  # (shared writer: threads and pinned slots stay for the next evaluation)
     if on_gpu:
@@ -529,18 +563,38 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
                 for v in (sq_err, psnrs, ssims)]
         stats = torch.stack([sums[0].reshape(()), sums[1].reshape(()),
                              torch.tensor(float(len(mine)), dtype=torch.float64, device=device),
-                             sums[2].reshape(()), flip_sum.reshape(())]).to(device)
+                             sums[2].reshape(()), flip_sum.reshape(())] +
+                            ([lpips_sum.reshape(())] if lpips_sum is not None else [])).to(device)
         if world > 1:
-            dist.all_reduce(stats)  # host-side metric gather (5 scalars), not on the data path
+            dist.all_reduce(stats)  # host-side metric gather (5 scalars, 6 with LPIPS), not on the data path
         stats = stats.tolist()
         misc["test_loss"] = torch.tensor(stats[0] / max(stats[2], 1))
         misc["test_psnr"] = mse2psnr(misc["test_loss"].float()).squeeze()
         misc["test_psnr_v2"] = torch.tensor(stats[1] / max(stats[2], 1))
         misc["test_ssim"] = torch.tensor(stats[3] / max(stats[2], 1))
         misc["test_flip"] = torch.tensor(stats[4] / max(stats[2], 1))  # (frames of one size: the mean of per-frame means, main.py:393)
+        if lpips_sum is not None:
+            misc["test_lpips"] = torch.tensor(stats[5] / max(stats[2], 1))
         misc["errors"] = torch.stack(errors, 0) if errors else torch.empty(0)
     model.train()
     return rgbs, misc
+
+
+def load_lpips_weights(args, device, logger):
+    """--r2l_lpips_weights -> the flat parameter vector on the device (metrics.lpips_params), or None without the flag."""
+    from .metrics import lpips_params
+    from .options import validate_lpips
+    validate_lpips(args)
+    if not args.r2l_lpips_weights:
+        return None
+    params = lpips_params(args.r2l_lpips_weights).to(device)
+    logger.info("LPIPS (AlexNet, v0.1) in the test-set loop: %d parameters from %s" % (params.numel(), args.r2l_lpips_weights))
+    return params
+
+
+def lpips_field(misc):
+    """' TestLPIPS %.4f' for the test-set log lines (main.py:1080, 1468: between TestSSIM and TestFLIP), '' without the flag."""
+    return " TestLPIPS %.4f" % misc["test_lpips"].item() if "test_lpips" in misc else ""
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -560,6 +614,7 @@ def main(argv=None):
     # flat parameter buffer once, so a checkpoint-less start is identical on all ranks by construction
     torch.manual_seed(int(os.environ.get("R2L_SEED", "0")))
     logger = Logger(args, rank)
+    lpips_w = load_lpips_weights(args, device, logger)  # (read once; None without --r2l_lpips_weights)
 
     scene = D.load_scene(args)
     images, poses, hwf = scene.images, scene.poses, scene.hwf
@@ -595,10 +650,10 @@ def main(argv=None):
 
     if args.test_pretrained:
         _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images, rank=rank,
-                              world=world, teacher=teacher)
-        logger.info("Pretrained test: TestLoss %.4f TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f TestFLIP %.4f" %
+                              world=world, teacher=teacher, lpips_params=lpips_w)
+        logger.info("Pretrained test: TestLoss %.4f TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
                     (misc["test_loss"].item(), misc["test_psnr"].item(), misc["test_psnr_v2"].item(),
-                     misc["test_ssim"].item(), misc["test_flip"].item()))
+                     misc["test_ssim"].item(), lpips_field(misc), misc["test_flip"].item()))
 
     if args.render_only:
         logger.info("RENDER ONLY")
@@ -607,9 +662,10 @@ def main(argv=None):
         if args.render_test:
             rgbs, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
                                      savedir=logger.gen_img_path if rank == 0 or world > 1 else None, rank=rank,
-                                     world=world, teacher=teacher)
-            logger.info("[TEST] TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f TestFLIP %.4f" %
-                        (misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), misc["test_flip"].item()))
+                                     world=world, teacher=teacher, lpips_params=lpips_w)
+            logger.info("[TEST] TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
+                        (misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), lpips_field(misc),
+                         misc["test_flip"].item()))
         else:
             rgbs, misc = render_path(video_poses, model, point_sampler, device, logger, savedir=logger.gen_img_path,
                                      rank=rank, world=world, teacher=teacher)
@@ -763,15 +819,15 @@ def main(argv=None):
             os.makedirs(savedir, exist_ok=True)
             t_ = time.time()
             _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
-                                  savedir=savedir, rank=rank, world=world)
+                                  savedir=savedir, rank=rank, world=world, lpips_params=lpips_w)
             if misc["test_psnr_v2"] > best_psnr:
                 best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
                 if rank == 0:
                     save_ckpt(os.path.join(logger.weights_path, "ckpt_best.tar"), i, model,
                               trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, r2l_config=r2l_config)
-            logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f TestFLIP %.4f BestPSNRv2 %.4f (Iter %d) "
+            logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f BestPSNRv2 %.4f (Iter %d) "
                         "TrainHistPSNR %.4f LR %.8f Time %.1fs" %
-                        (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(),
+                        (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), lpips_field(misc),
                          misc["test_flip"].item(), best_psnr, best_psnr_step, hist_psnr, lr, time.time() - t_))
         if i % args.i_video == 0:
             # test: using novel poses (main.py:1473-1484)

@@ -191,3 +191,191 @@ def flip(img, ref, pixels_per_degree=None, rescale=None, return_map=False):
     if single:
         return (out[0], fmap[0]) if return_map else out[0]
     return (out, fmap) if return_map else out
+
+
+# ---- LPIPS (lpips.LPIPS(net='alex', version='0.1') in eval mode, as main.py:359-369 calls it) ---------------------------------
+# (in, out, kernel, stride, zero padding) of the five AlexNet convolutions; a 3 / 2 max-pool (floor) sits in front of 1 and 2
+LPIPS_CONVS = ((3, 64, 11, 4, 2), (64, 192, 5, 1, 2), (192, 384, 3, 1, 1), (384, 256, 3, 1, 1), (256, 256, 3, 1, 1))
+LPIPS_SHIFT, LPIPS_SCALE = (-0.030, -0.088, -0.188), (0.458, 0.448, 0.450)
+LPIPS_PARAM_FLOATS = sum(ci * co * k * k + 2 * co for ci, co, k, _, _ in LPIPS_CONVS)  # 2 470 848
+_LPIPS_FEATURES = (0, 3, 6, 8, 10)  # torchvision's alexnet.features indices of the convolutions
+
+
+def lpips_sizes(H, W):
+    """[(Ho, Wo)] of the five feature maps of an H x W image (400 -> 99, 49, 24, 24, 24; 31 -> 7, 3, 1, 1, 1)."""
+    out = []
+    for l, (_, _, k, s, p) in enumerate(LPIPS_CONVS):
+        if l in (1, 2):
+            H, W = (H - 3) // 2 + 1, (W - 3) // 2 + 1
+        H, W = (H + 2 * p - k) // s + 1, (W + 2 * p - k) // s + 1
+        out.append((H, W))
+    return out
+
+
+def lpips_flatten(convs, lins):
+    """[(weight [Co,Ci,k,k], bias [Co])] x 5 and five lin weights -> the flat fp32 vector of r2l_lpips_pack."""
+    flat = torch.cat([t.detach().float().reshape(-1) for wb in convs for t in wb] + [t.detach().float().reshape(-1) for t in lins])
+    assert flat.numel() == LPIPS_PARAM_FLOATS
+    return flat.contiguous()
+
+
+def lpips_params(path):
+    """The flat fp32 parameter vector (for l = 0..4 { conv weight, bias }, then lin_0 .. lin_4) from the user's files: one file,
+    or two joined by ':' whose keys are merged.  Two naming schemes are understood: torchvision's AlexNet checkpoint
+    (features.{0,3,6,8,10}.{weight,bias}) beside the lpips package's alex.pth (lin{0..4}.model.1.weight), and a saved
+    lpips.LPIPS().state_dict() (net.slice{1..5}.{0,3,6,8,10}.{weight,bias} + lin{k}.model.1.weight).  Extra keys are ignored; a
+    missing key or a wrong shape is a ValueError that names the key."""
+    sd = {}
+    for part in str(path).split(":"):
+        if not part:
+            continue
+        obj = torch.load(part, map_location="cpu", weights_only=True)
+        if not isinstance(obj, dict):
+            raise ValueError("%s: expected a state dict, got %s" % (part, type(obj).__name__))
+        sd.update(obj)
+    convs, lins = [], []
+    for l, (ci, co, k, _, _) in enumerate(LPIPS_CONVS):
+        pair = []
+        for leaf, shape in (("weight", (co, ci, k, k)), ("bias", (co,))):
+            names = ("features.%d.%s" % (_LPIPS_FEATURES[l], leaf), "net.slice%d.%d.%s" % (l + 1, _LPIPS_FEATURES[l], leaf))
+            key = next((n for n in names if n in sd), None)
+            if key is None:
+                raise ValueError("LPIPS weights %s: missing key %s (or %s)" % (path, names[0], names[1]))
+            if tuple(sd[key].shape) != shape:
+                raise ValueError("LPIPS weights %s: key %s has shape %s, expected %s" % (path, key, tuple(sd[key].shape), shape))
+            pair.append(sd[key])
+        convs.append(pair)
+    for l, (_, co, _, _, _) in enumerate(LPIPS_CONVS):
+        key = "lin%d.model.1.weight" % l
+        if key not in sd:
+            raise ValueError("LPIPS weights %s: missing key %s" % (path, key))
+        if tuple(sd[key].shape) != (1, co, 1, 1):
+            raise ValueError("LPIPS weights %s: key %s has shape %s, expected %s" % (path, key, tuple(sd[key].shape), (1, co, 1, 1)))
+        lins.append(sd[key])
+    return lpips_flatten(convs, lins)
+
+
+def lpips_unflatten(params):
+    """The flat vector -> ([(weight, bias)] x 5, [lin] x 5) as views."""
+    assert params.numel() == LPIPS_PARAM_FLOATS, "LPIPS parameters: %d floats, expected %d" % (params.numel(), LPIPS_PARAM_FLOATS)
+    convs, lins, o = [], [], 0
+    for ci, co, k, _, _ in LPIPS_CONVS:
+        n = co * ci * k * k
+        convs.append((params[o:o + n].view(co, ci, k, k), params[o + n:o + n + co]))
+        o += n + co
+    for _, co, _, _, _ in LPIPS_CONVS:
+        lins.append(params[o:o + co])
+        o += co
+    return convs, lins
+
+
+def _lpips_features(x, convs, shift=True, pad_first=False, ceil_mode=False):
+    """The five post-ReLU feature maps [K,C,Ho,Wo] of a [K,H,W,3] stack, op by op.  The keywords exist for the tests: anything
+    but the defaults is a deliberately wrong evaluation (no shift; zero padding in front of the scaling layer; ceil-mode pools)
+    that the bars must be able to see."""
+    import torch.nn.functional as F
+    t = dict(dtype=x.dtype, device=x.device)
+    # the scaling layer's constants are fp32 numbers (the lpips package holds them in fp32 buffers, the kernel as float literals):
+    # the float64 yardstick uses those values, not the decimal fractions
+    sh = torch.tensor(LPIPS_SHIFT if shift else (0., 0., 0.), dtype=torch.float32).to(**t).view(1, 3, 1, 1)
+    sc = torch.tensor(LPIPS_SCALE, dtype=torch.float32).to(**t).view(1, 3, 1, 1)
+    x = x.permute(0, 3, 1, 2)
+    if pad_first:
+        x = F.pad(x, (2, 2, 2, 2))
+    x = (x - sh) / sc
+    feats = []
+    for l, ((w, b), (_, _, _, s, p)) in enumerate(zip(convs, LPIPS_CONVS)):
+        if l in (1, 2):
+            x = F.max_pool2d(x, 3, 2, ceil_mode=ceil_mode)
+        x = F.relu(F.conv2d(x, w.to(**t), b.to(**t), stride=s, padding=0 if (l == 0 and pad_first) else p))
+        feats.append(x)
+    return feats
+
+
+def _lpips_torch(a, b, params, **wrong):
+    """-> per-layer means [K,5] and the five maps [K,Ho,Wo] of two [K,H,W,3] stacks, in their dtype and on their device."""
+    convs, lins = lpips_unflatten(params)
+    fa, fb = _lpips_features(a, convs, **wrong), _lpips_features(b, convs, **wrong)
+    maps = []
+    for l in range(5):
+        na = fa[l] / (fa[l].pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+        nb = fb[l] / (fb[l].pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+        maps.append(((na - nb).pow(2) * lins[l].to(dtype=a.dtype, device=a.device).view(1, -1, 1, 1)).sum(1))
+    return torch.stack([m.mean((1, 2)) for m in maps], 1), maps
+
+
+_LPIPS_PACKED = {}  # (device, data_ptr, version of the params tensor) -> (params, packed stream): a few entries at most
+
+
+def _lpips_stream(L, params, device):
+    key = (str(device), params.data_ptr(), params._version)
+    hit = _LPIPS_PACKED.get(key)
+    if hit is not None and hit[0] is params:
+        return hit[1]
+    assert params.numel() == L.r2l_lpips_param_floats(), "LPIPS parameters: %d floats, expected %d" % (
+        params.numel(), L.r2l_lpips_param_floats())
+    flat = params.detach().to(device).float().contiguous()
+    wpack = torch.empty(L.r2l_lpips_pack_floats(), device=device)
+    from . import _lib
+    _lib.check(L.r2l_lpips_pack(flat.data_ptr(), wpack.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+               "r2l_lpips_pack")
+    while len(_LPIPS_PACKED) >= 4:
+        _LPIPS_PACKED.pop(next(iter(_LPIPS_PACKED)))
+    _LPIPS_PACKED[key] = (params, wpack)  # (holding params keeps its address from being reused under this key)
+    return wpack
+
+
+def lpips(img, ref, params, rescale=None, normalize=False, return_layers=False, return_maps=False):
+    """LPIPS (AlexNet, v0.1) of [H,W,3] or [K,H,W,3] images with values in [-1, 1]; H, W >= 31.  params: the flat vector of
+    lpips_params.  normalize: the images are in [0, 1] and are mapped by 2 x - 1 first.  rescale: None or a 4-tensor
+    {min_img, max_img, min_ref, max_ref}: each input is first mapped by 2 / (max - min) * (x - min) - 1, the [-1, 1] rescale
+    main.py:361-363 applies to the whole stack.  CUDA tensors run the fused HIP kernels (r2l_lpips; the packed weight stream is
+    cached per device and params tensor); CPU tensors an op-by-op torch evaluation in their own dtype (fp32: the CPU plumbing
+    config; float64: the yardstick of the tests).  Returns the values ([K], or 0-d for a single pair), then, if asked for, the
+    per-layer means v_0 .. v_4 ([K,5] / [5]) and the list of the five maps d_l ([K,Ho,Wo] / [Ho,Wo])."""
+    assert img.shape == ref.shape and img.dim() in (3, 4) and img.shape[-1] == 3
+    single = img.dim() == 3
+    H, W = img.shape[-3:-1]
+    if H < 31 or W < 31:
+        raise ValueError("LPIPS needs images of at least 31 x 31 pixels (got %d x %d): the deepest feature map would be empty" % (H, W))
+    if img.is_cuda:
+        from . import _lib
+        L = _lib.load()
+        a, b = img.detach().float().contiguous(), ref.detach().to(img.device).float().contiguous()
+        if normalize:
+            a, b = 2 * a - 1, 2 * b - 1
+        K = 1 if single else a.shape[0]
+        wpack = _lpips_stream(L, params, a.device)
+        work = torch.empty(L.r2l_lpips_work_floats(K, H, W), device=a.device)
+        out = torch.empty(K, device=a.device)
+        layers = torch.empty((K, 5), device=a.device) if return_layers else None
+        flat = torch.empty((K, L.r2l_lpips_map_floats(H, W)), device=a.device) if return_maps else None
+        ext = rescale.detach().to(a.device).float().contiguous() if rescale is not None else None
+        assert ext is None or ext.numel() == 4
+        _lib.check(L.r2l_lpips(a.data_ptr(), b.data_ptr(), K, H, W, ext.data_ptr() if ext is not None else None, wpack.data_ptr(),
+                               work.data_ptr(), layers.data_ptr() if return_layers else None,
+                               flat.data_ptr() if return_maps else None, out.data_ptr(),
+                               ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_lpips")
+        maps, o = [], 0
+        for ho, wo in (lpips_sizes(H, W) if return_maps else ()):
+            maps.append(flat[:, o:o + ho * wo].view(K, ho, wo))
+            o += ho * wo
+    else:
+        a, b = (img[None], ref[None]) if single else (img, ref)
+        a, b = (a, b.to(a.dtype)) if a.dtype == torch.float64 else (a.float(), b.float())
+        if normalize:
+            a, b = 2 * a - 1, 2 * b - 1
+        if rescale is not None:
+            e = rescale.to(a.dtype)
+            assert e.numel() == 4
+            a, b = 2 / (e[1] - e[0]) * (a - e[0]) - 1, 2 / (e[3] - e[2]) * (b - e[2]) - 1
+        layers, maps = _lpips_torch(a, b, params.detach().to(a.dtype))
+        out = layers[:, 0]
+        for l in range(1, 5):
+            out = out + layers[:, l]
+    res = [out[0] if single else out]
+    if return_layers:
+        res.append(layers[0] if single else layers)
+    if return_maps:
+        res.append([m[0] for m in maps] if single else maps)
+    return res[0] if len(res) == 1 else tuple(res)

@@ -71,6 +71,10 @@ FLAGS = {
     # device from Philox streams of (R2L_SEED, iteration) instead of torch's generator, and the loop reads the loss only where it
     # prints, tests or ends; opt-in, GPU only.  main.py / create_data.py ignore it
     "r2l_fused_step": ("flag", False),
+    # LPIPS(AlexNet, v0.1) in the test-set loop (r2l_lpips): the user's weight file(s), one path or two joined by ':' (torchvision's
+    # AlexNet checkpoint and the lpips package's alex.pth, or a saved lpips.LPIPS().state_dict(): metrics.lpips_params).  None are
+    # shipped; '' = no LPIPS, every log line as it always was
+    "r2l_lpips_weights": (str, ""),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),
@@ -168,8 +172,22 @@ def parse_args(argv=None):
     return args
 
 
+def validate_lpips(args):
+    """--r2l_lpips_weights: only the AlexNet variant exists here, and the files must be there at start-up, not at the first
+    evaluation hours into a run."""
+    if not args.r2l_lpips_weights:
+        return
+    if args.lpips_net != "alex":
+        raise NotImplementedError("--r2l_lpips_weights evaluates LPIPS with the AlexNet features only (--lpips_net alex), got "
+                                  "--lpips_net %s" % args.lpips_net)
+    for part in args.r2l_lpips_weights.split(":"):
+        if not os.path.isfile(part):
+            raise FileNotFoundError("--r2l_lpips_weights: no such file: %r" % part)
+
+
 def validate_accelerated(args):
     """Fail loudly for reference variants this build does not accelerate (out of scope)."""
+    validate_lpips(args)
     for name in ("plucker", "learn_depth", "shuffle_input", "given_render_path_rays", "convert_to_onnx"):
         if getattr(args, name):
             raise NotImplementedError("--%s is a reference variant outside the accelerated R2L path" % name)

@@ -27,7 +27,7 @@ import torch
 
 from . import data as D
 from .checkpoint import load_ckpt, save_ckpt
-from .driver import apply_arithmetic, create_nerf_teacher, init_distributed, render_path
+from .driver import lpips_field, apply_arithmetic, create_nerf_teacher, init_distributed, load_lpips_weights, render_path
 from .logger import Logger
 from .options import parse_args, validate_accelerated
 from .pixel_batch import PixelBatcher
@@ -112,6 +112,7 @@ def main(argv=None):
                                   "device '%s'" % device)
     _seed(0)
     logger = Logger(args, rank)
+    lpips_w = load_lpips_weights(args, device, logger)  # (read once; None without --r2l_lpips_weights)
     scene = D.load_scene(args)
     images, poses, hwf = scene.images, scene.poses, scene.hwf
     logger.info("Loaded %s" % scene.kind, tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
@@ -194,15 +195,15 @@ def main(argv=None):
         if i % args.i_testset == 0 and len(i_test):
             savedir = os.path.join(logger.gen_img_path, "testset_%s_iter%d" % (logger.ExpID, i))
             _, misc = render_path(test_poses, coarse, None, device, logger, gt_imgs=test_images, savedir=savedir,
-                                  teacher=teacher)
+                                  teacher=teacher, lpips_params=lpips_w)
             for net in (coarse, fine):
                 if net is not None:
                     net.train()
             if misc["test_psnr_v2"].item() > best_psnr:
                 best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
                 save(os.path.join(logger.weights_path, "ckpt_best.tar"), i, lr)
-            logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f BestPSNRv2 %.4f (Iter %d)" %
-                        (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), best_psnr, best_psnr_step))
+            logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f%s BestPSNRv2 %.4f (Iter %d)" %
+                        (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), lpips_field(misc), best_psnr, best_psnr_step))
         if i % args.i_weights == 0:
             name = "ckpt_%d.tar" % i if args.save_intermediate_models else "ckpt.tar"
             path = save(os.path.join(logger.weights_path, name), i, lr)
