@@ -450,7 +450,8 @@ int r2l_lpips(const float* img_a, const float* img_b, int K, int H, int W, const
 /* ---- hard-ray pool (training data path) ---------------------------------------------------------------------------------
  * The three data movements of main.py:1325-1347 (n_hard_out random pool rows [o, d, rgb] appended to every batch) and
  * main.py:1410-1425 (the hard rays of the step enter the pool, appended until it is full, then replacing the rows that were
- * handed out), one kernel each; ranking the per-ray errors stays a sort on the host's side of the ABI.
+ * handed out), one kernel each, and the ranking of the per-ray errors that picks those hard rays (r2l_pool_select below): an
+ * iteration needs no sort on the host's side of the ABI.
  *   r2l_pool_pick: idx_out[i], i < n_out = n_out DISTINCT rows of [0, n_rows), every row equally likely: a keyed bijection
  *     (4-round Feistel, cycle-walked) evaluated at 0 .. n_out-1 — replaces np.random.permutation(n_rows)[:n_out]; same key,
  *     same rows.
@@ -465,6 +466,25 @@ int r2l_pool_augment(const float* rays_o, const float* rays_d, const float* targ
 int r2l_pool_store(const float* rays_o, const float* rays_d, const float* target, int64_t stride_o, int64_t stride_d,
                    int64_t stride_t, const int64_t* hard, float* pool, const int64_t* dst_idx, int64_t dst0, int64_t n_in,
                    void* stream);
+
+/* r2l_pool_select: the k hardest of the first B rows of a step (csrc/r2l_pool.hip: a radix select on 8-bit digits and one ordered
+ * compaction; one workgroup up to 12 288 rows, up to 1024 beyond).  rgb / target: device fp32 rows of 3, row strides in floats
+ * (>= 3: the step's output next to a column slice of a [B, 9] shard batch).
+ *   error of row i:  e_i = fl(fl(fl(d0*d0) + fl(d1*d1)) + fl(d2*d2)),  d = rgb[i] - target[i], every operation rounded to fp32 —
+ *     the SUM of squares, not the mean (dividing by 3 can merge two distinct sums into a tie).
+ *   rank key:  the bit pattern of e_i as uint32 (e_i >= +0: the order of the values); any NaN -> 0xFFFFFFFF, among the hardest.
+ *   result:  the rows ordered by (key descending, index ascending), the first k of them; a tie at the threshold goes to the lower
+ *     index.  hard_out (device int64[k]) holds these k indices in ASCENDING INDEX order; err_out (device [B], or NULL) receives
+ *     e_i of every row.
+ * A pure function of its inputs: the same for every launch geometry, no position depends on the arrival order of an atomic.
+ * Stateless; allocates nothing, never synchronises, enqueues on `stream`.  work: device scratch of r2l_pool_select_work_bytes B
+ * bytes (-1: B < 0 or B >= 2^31), 16-byte aligned; written before it is read, so its contents on entry do not matter.
+ * hipErrorInvalidValue (with r2l_last_error), checked before any launch: rgb, target, work or (with k > 0) hard_out NULL, a
+ * stride below 3, B < 0, B >= 2^31, k < 0, k > B, work not 16-byte aligned.  B == 0 or k == 0 is a successful no-op.
+ * r2l_amd/pool_select.py (select_spec) restates the result in numpy. */
+int64_t r2l_pool_select_work_bytes(int64_t B);
+int r2l_pool_select(const float* rgb, const float* target, int64_t stride_rgb, int64_t stride_t, int64_t B, int64_t k,
+                    int64_t* hard_out /*[k]*/, float* err_out /*[B] or NULL*/, void* work, void* stream);
 
 /* ---- device-resident ray store (training data path without shard files) ---------------------------------------------------
  * The teacher's [o, d, rgb] rows stay in device memory between their rendering and the student's steps, instead of being
@@ -531,7 +551,9 @@ int r2l_pixel_batch(const float* images /*dev [n_img,H,W,3]*/, const float* c2w 
  * loss_out[1] = psnr of the fine net (of the coarse net when it is alone), each mse / psnr as r2l_loss_finish with 1/(3 N_rand).
  * Adam: r2l_adam_step(lr, beta1, beta2, eps, step, grad_scale 1); its bias corrections take min(step, 2^31 - 1).
  *
- * Draws: made inside the call, stream_id = 2^62 + 4*step + k of `seed` (the frames call uses stream ids 2*frame_id, far below):
+ * Draws: made inside the call, stream_id = 2^62 + 4*step + k of `seed` (the frames call uses stream ids 2*frame_id, far below;
+ * the student's training loop with its device pool draws the jitter of iteration i on rank r from stream 2^61 + 4096*i + r of
+ * r2l_draw_uniform, element ray*16 + sample: between the two, apart from both for any run length and rank count in use):
  *   k = 0  t_rand[r,s]      element r*N_samples + s                    of r2l_draw_uniform        (perturb == 1)
  *   k = 1  u[r,i]           element r*N_importance + i                 of r2l_draw_uniform        (perturb == 1, N_importance > 0)
  *   k = 2  coarse noise     element r*N_samples + s                    of r2l_draw_normal, scale = raw_noise_std   (raw_noise_std > 0)

@@ -132,6 +132,8 @@ SIGNATURES = {
     "r2l_pool_pick": (_i, [_p, _l, _l, ctypes.c_uint64, _p]),
     "r2l_pool_augment": (_i, [_p, _p, _p, _l, _l, _l, _p, _p, _l, _l, _p, _p, _p, _p]),
     "r2l_pool_store": (_i, [_p, _p, _p, _l, _l, _l, _p, _p, _p, _l, _l, _p]),
+    "r2l_pool_select_work_bytes": (_l, [_l]),
+    "r2l_pool_select": (_i, [_p, _p, _l, _l, _l, _l, _p, _p, _p, _p]),
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
     "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),

@@ -61,10 +61,11 @@ def load_weights_v2(model, ckpt, key):
 
 
 def save_ckpt(path, global_step, model, optimizer_state_dict, best_psnr, best_psnr_step, model_name="R2L",
-              model_fine=None, r2l_config=None):
+              model_fine=None, r2l_config=None, extra=None):
     """Write a reference-layout checkpoint (main.py:1516-1542).  r2l_config: the arithmetic the run trained on
     ({'precision', 'dw_mode', 'requested'}, driver.apply_arithmetic), stored under a key of its own — the reference's loaders
-    read the keys they know by name (main.py:481-509) and never see it."""
+    read the keys they know by name (main.py:481-509) and never see it.  extra: further keys of this build's own, merged in the
+    same way (the driver's r2l_hard_pool); none may take the name of a key above."""
     model = undataparallel(model)
     to_save = {
         "global_step": global_step,
@@ -79,6 +80,10 @@ def save_ckpt(path, global_step, model, optimizer_state_dict, best_psnr, best_ps
         to_save["network_fn"] = model  # pickled whole, engine state excluded by NeRF_v3_2.__getstate__
     if r2l_config is not None:
         to_save["r2l_config"] = dict(r2l_config)
+    for key, value in (extra or {}).items():
+        if key in to_save:
+            raise ValueError("save_ckpt: extra key %r is a key of the checkpoint layout" % key)
+        to_save[key] = value
     os.makedirs(os.path.dirname(os.path.abspath(path)), exist_ok=True)
     torch.save(to_save, path)
     return path

@@ -19,7 +19,7 @@ from .metrics import flip, img2mse, lpips, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import parse_args, validate_accelerated
 from .dist_utils import split_shards
-from .train_step import R2LTrainer, lr_schedule
+from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -52,10 +52,17 @@ class HardRayPool:
 
     The pool ([rows, 9] = o,d,rgb; 59 MB at the README sizes) lives on the device of the rays it is fed, is allocated
     once at its final size, and on a GPU the random row choice is a device randperm: the reference's host-side
-    np.random.permutation(1.6 M) per step costs as much as a whole MI355X training step."""
+    np.random.permutation(1.6 M) per step costs as much as a whole MI355X training step.
 
-    def __init__(self, hard_ratio, hard_mul, rng=None, seed=0):
+    device_select=True (GPU only, --r2l_device_pool): update() ranks the rays inside the library — r2l_pool_select, a radix
+    select, then r2l_pool_store: two launches — instead of a torch sort of all B errors.  The hard rays then enter the pool in
+    index order (the default path stores them in error order), so a run with the switch is another run than one without.
+    state_dict() / load_state_dict(): what a checkpoint needs to continue the pool bit for bit."""
+
+    def __init__(self, hard_ratio, hard_mul, rng=None, seed=0, device_select=False):
         self.ratio, self.mul = hard_ratio, hard_mul
+        self.device_select = bool(device_select)
+        self._batch_size = None  # the batch size the store was sized for (first update)
         self.pool = None      # rows filled so far (a view of _store once allocated)
         self._store = None
         self.full = False
@@ -121,17 +128,62 @@ class HardRayPool:
         return (torch.cat([rays_o, picked[:, :3]], 0), torch.cat([rays_d, picked[:, 3:6]], 0),
                 torch.cat([target, picked[:, 6:]], 0))
 
+    def _allocate(self, batch_size, n_in, device):
+        steps = max(1, -(-int(np.ceil(batch_size * self.mul)) // n_in))
+        self._store = torch.empty(steps * n_in, 9, dtype=torch.float32, device=device)
+        self._n = 0
+        self._batch_size = int(batch_size)
+
+    def state_dict(self):
+        """The pool as a checkpoint carries it: the filled rows on the host, the fill state, the draw counter of the keyed row
+        choice and the three numbers the store's size follows from."""
+        rows = self.pool.detach().cpu().clone() if self.pool is not None else torch.empty(0, 9, dtype=torch.float32)
+        return {"rows": rows, "full": bool(self.full), "n": int(rows.shape[0]), "draws": int(self._draws),
+                "hard_ratio": self.ratio, "hard_mul": self.mul, "batch_size": self._batch_size}
+
+    def load_state_dict(self, state, device=None, batch_size=None):
+        """Continue from state_dict().  device: where the pool lives (default: where the saved rows are); batch_size: the batch
+        size of the run that continues, when it is known.  ValueError naming the field if the pool was built for other numbers."""
+        for field, mine in (("hard_ratio", self.ratio), ("hard_mul", self.mul)):
+            if state[field] != mine:
+                raise ValueError("HardRayPool.load_state_dict: %s is %r in the saved pool, %r here" % (field, state[field], mine))
+        if batch_size is not None and state["batch_size"] is not None and int(batch_size) != state["batch_size"]:
+            raise ValueError("HardRayPool.load_state_dict: batch_size is %d in the saved pool, %d here" %
+                             (state["batch_size"], int(batch_size)))
+        rows = state["rows"]
+        if rows.shape[0] != state["n"] or (state["batch_size"] is None and state["n"]):
+            raise ValueError("HardRayPool.load_state_dict: n is %d in the saved pool, which holds %d rows" %
+                             (state["n"], rows.shape[0]))
+        self._draws, self.full, self._ix_out = int(state["draws"]), False, None
+        self.pool = self._store = self._batch_size = None
+        if state["batch_size"] is None:
+            return
+        n_in, _ = self.sizes(state["batch_size"])
+        self._allocate(state["batch_size"], n_in, torch.device(device) if device is not None else rows.device)
+        if state["n"] > self._store.shape[0]:
+            raise ValueError("HardRayPool.load_state_dict: n is %d in the saved pool, the store holds %d rows" %
+                             (state["n"], self._store.shape[0]))
+        self._n = int(state["n"])
+        self._store[:self._n].copy_(rows)
+        self.pool = self._store[:self._n]
+        self.full = bool(state["full"])
+
     def update(self, rgb, rays_o, rays_d, target, batch_size):
         n_in, _ = self.sizes(batch_size)
         if n_in <= 0:
             return
-        err = torch.mean((rgb[:batch_size] - target[:batch_size])**2, dim=1)
-        _, order = torch.sort(err)
-        hard = order[-n_in:]
+        if self.device_select:
+            if not (rgb.is_cuda and rays_o.is_cuda):
+                raise NotImplementedError("HardRayPool(device_select=True) ranks the rays on the GPU only (r2l_pool_select of "
+                                          "libr2l_hip.so); these rays are on %s" % rays_o.device)
+            from .pool_select import select
+            hard = select(rgb[:batch_size], target[:batch_size], n_in)  # ascending index order, ties to the lower index
+        else:
+            err = torch.mean((rgb[:batch_size] - target[:batch_size])**2, dim=1)
+            _, order = torch.sort(err)
+            hard = order[-n_in:]
         if self._store is None:  # final size: the first multiple of n_in that reaches batch_size * hard_mul
-            steps = max(1, -(-int(np.ceil(batch_size * self.mul)) // n_in))
-            self._store = torch.empty(steps * n_in, 9, dtype=torch.float32, device=rays_o.device)
-            self._n = 0
+            self._allocate(batch_size, n_in, rays_o.device)
         if rays_o.is_cuda:  # one kernel: gather the hard rows [o, d, rgb] and put them where they go (replace / append)
             from . import _lib
             lib = _lib.load()
@@ -608,6 +660,9 @@ def main(argv=None):
                                   "without --render_test / --test_pretrained) and uses it in utils/create_data.py; TRAINING "
                                   "the teacher runs through utils/train_nerf.py")
     rank, world, device = init_distributed()
+    if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
+        raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
+                                  "r2l_draw_uniform of libr2l_hip.so); this run is on the CPU")
     np.random.seed(0)
     # every rank must build the same student: torch's default generator is seeded per process otherwise (the reference had
     # ONE module that nn.DataParallel re-broadcast every step, main.py:472-479); R2LTrainer additionally broadcasts rank 0's
@@ -771,7 +826,29 @@ def main(argv=None):
     if ckpt is not None and args.resume:
         trainer.load_optimizer_state_dict(ckpt["optimizer_state_dict"])
         logger.info("Resume optimizer successfully.")
-    pool = HardRayPool(args.hard_ratio, args.hard_mul, seed=1000 + rank) if args.hard_ratio else None
+    pool = None
+    if args.hard_ratio:
+        pool = HardRayPool(args.hard_ratio, args.hard_mul, seed=1000 + rank, device_select=args.r2l_device_pool)
+    # --r2l_device_pool: the pool ranks on the device, the jitter comes from the library's Philox streams (include/r2l_hip.h:
+    # stream 2^61 + 4096 * iteration + rank of R2L_SEED), and at world size 1 the pool travels in every checkpoint: with the ray
+    # store's seek a resumed run repeats the uninterrupted one bit for bit
+    jitter_seed = int(os.environ.get("R2L_SEED", "0"))
+    save_pool = bool(args.r2l_device_pool and pool is not None and world == 1)
+    if args.r2l_device_pool:
+        from .render import draw_uniform
+        logger.info("[Config] Device pool (--r2l_device_pool): hard rays ranked by r2l_pool_select, jitter from Philox stream "
+                    "2^61 + 4096 * iteration + %d of seed %d" % (rank, jitter_seed))
+        if pool is not None and ckpt is not None and args.resume:
+            if world > 1:
+                logger.info("hard-ray pool: every rank has its own and rank 0 writes the checkpoint, so the pools of a multi-rank "
+                            "run are not saved: they start empty after --resume")
+            elif ckpt.get("r2l_hard_pool") is not None:
+                pool.load_state_dict(ckpt["r2l_hard_pool"], device=device, batch_size=shards[rank] * loader.rows_per_file)
+                logger.info("hard-ray pool: resumed with %d rows (full: %s, draw counter %d)" %
+                            (0 if pool.pool is None else pool.pool.shape[0], pool.full, pool._draws))
+            else:
+                logger.info("hard-ray pool: the checkpoint carries none (written without --r2l_device_pool?): it starts empty")
+    pool_extra = lambda: {"r2l_hard_pool": pool.state_dict()} if save_pool else None
     hist_psnr, t_data, t_batch = 0., 0., 0.
     logger.info("Begin training")
     for i in range(start + 1, args.N_iters + 1):
@@ -798,7 +875,11 @@ def main(argv=None):
             if rays_o.shape[0] != n_global[rank]:
                 raise RuntimeError("uneven --N_rand: rank %d holds %d rays in iteration %d, the share computed on every rank "
                                    "says %d (shards with differing row counts?)" % (rank, rays_o.shape[0], i, n_global[rank]))
-        rgb, loss_out = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, n_global=n_global)
+        t_rand = None
+        if args.r2l_device_pool and args.perturb > 0:  # (perturb 0: nothing is drawn)
+            n = rays_o.shape[0]
+            t_rand = draw_uniform(n * N_SAMPLE, jitter_seed, 2**61 + i * 4096 + rank, device).view(n, N_SAMPLE)
+        rgb, loss_out = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, t_rand=t_rand, n_global=n_global)
         if pool is not None:
             pool.update(rgb, rays_o, rays_d, target, batch_size)
         t_batch = time.time() - t0
@@ -824,7 +905,8 @@ def main(argv=None):
                 best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
                 if rank == 0:
                     save_ckpt(os.path.join(logger.weights_path, "ckpt_best.tar"), i, model,
-                              trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, r2l_config=r2l_config)
+                              trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, r2l_config=r2l_config,
+                              extra=pool_extra())
             logger.info("[TEST] Iter %d TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f BestPSNRv2 %.4f (Iter %d) "
                         "TrainHistPSNR %.4f LR %.8f Time %.1fs" %
                         (i, misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), lpips_field(misc),
@@ -840,7 +922,7 @@ def main(argv=None):
         if i % args.i_weights == 0 and rank == 0:
             name = "ckpt_%d.tar" % i if args.save_intermediate_models else "ckpt.tar"
             path = save_ckpt(os.path.join(logger.weights_path, name), i, model, trainer.optimizer_state_dict(lr),
-                             best_psnr, best_psnr_step, r2l_config=r2l_config)
+                             best_psnr, best_psnr_step, r2l_config=r2l_config, extra=pool_extra())
             logger.info('Iter %d Save checkpoint: "%s".' % (i, path))
     loader.close()
     if world > 1 and os.environ.get("R2L_CHECK_SYNC"):  # tests: the replicas must have stayed bit-identical

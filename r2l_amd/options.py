@@ -71,6 +71,11 @@ FLAGS = {
     # device from Philox streams of (R2L_SEED, iteration) instead of torch's generator, and the loop reads the loss only where it
     # prints, tests or ends; opt-in, GPU only.  main.py / create_data.py ignore it
     "r2l_fused_step": ("flag", False),
+    # student training with the hard-ray pool's ranking inside the library (r2l_pool_select instead of a torch sort), the jitter
+    # t_rand from Philox streams of (R2L_SEED, iteration, rank) instead of torch's generator, and — at world size 1 — the pool in
+    # every checkpoint, so that --resume on a ray store repeats the uninterrupted run bit for bit; opt-in, GPU only.
+    # utils/create_data.py / utils/train_nerf.py ignore it
+    "r2l_device_pool": ("flag", False),
     # LPIPS(AlexNet, v0.1) in the test-set loop (r2l_lpips): the user's weight file(s), one path or two joined by ':' (torchvision's
     # AlexNet checkpoint and the lpips package's alex.pth, or a saved lpips.LPIPS().state_dict(): metrics.lpips_params).  None are
     # shipped; '' = no LPIPS, every log line as it always was
