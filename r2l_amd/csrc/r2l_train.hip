@@ -13,7 +13,15 @@
 struct R2LAdamK {
     float step_size, b1, b2, eps, sqrt_bc2, gscale;
 };
-// one parameter: torch.optim.Adam's op sequence (exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad, 1-b2))
+// one parameter: torch.optim.Adam's op sequence (exp_avg.lerp_(grad, 1-b1); exp_avg_sq.mul_(b2).addcmul_(grad, grad, 1-b2)), with ONE
+// stated difference in the constants.  The weights 1 - b are formed here from the fp32 b the ABI receives (1.0f - 0.999f =
+// 0.00099998713, exact: b + (1 - b) = 1 in the arithmetic that runs), and the bias corrections from the same promoted fp32 b.
+// torch rounds the DOUBLES b and 1 - b separately (0.999f beside 0.001f) and corrects with the double b.  So against torch's
+// fp32 Adam one step from the same state differs by up to 1.29e-5 relative in v's increment, 2.2e-7 in m's and — the bias
+// correction of b2 moving by the same 1.29e-5 at small steps — up to ~8e-6 in the update (measured over steps 1 .. 10: v 1.30e-5,
+// m 7e-8 of |m| + |g|, update 7.8e-6 of itself; tests/test_optimizer_cpu.py::test_distance_to_torch_fp32_adam).  The contract
+// this kernel is held to per entry is the fp64 statement of ITS constants (tests/optim_util.py adam64: 4 / 6 / 8 roundings on
+// m / v / p), not torch's bits.
 __device__ __forceinline__ float r2l_adam_one(float p, float g, float& m, float& v, const R2LAdamK& k) {
     const float gi = g * k.gscale;
     const float mi = m + (gi - m) * (1.0f - k.b1);
