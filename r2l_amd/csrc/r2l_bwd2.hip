@@ -2,9 +2,11 @@
 // three fp16 products per fp32 product, ~2^-21 relative.  The chain runs on gscale * g (a power of two chosen from the MSE
 // gradient scale, r2l_backward), which puts its values into fp16's range; a range guard raises a status word and the bf16x3
 // kernel launched behind it redoes the launch.  Stage order, mask ring and stash stores are r2l_bwd3.hip's; six 16 KiB
-// weight buffers fit beside the 32 KiB mask ring.
+// weight buffers fit beside the 32 KiB mask ring.  The file also owns the range control of a step of the fp16 trio: the two
+// kernels that write the B2S_* status words in front of the chain (r2l_bwd_prepare_kernel, r2l_gscale_kernel; r2l_bwd2_open_step).
 #include "r2l_f2.h"
 #include "r2l_coopf.h"
+#include "r2l_dw.h"  // r2l_bwd2_open_step
 
 #define B3_RING 2  // mask pieces (one per block) per wave
 
@@ -272,6 +274,108 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd2_kernel(const B2Args a) {
     }
 }
 
+// Generic mode of the fp16 trio: the caller's dL/drgb has no known scale, so the power of two that puts the dX chain into
+// fp16's range is chosen on the device: out = {gscale, 1 / gscale}, gscale = 2^(8 - e) for max |drgb| = m * 2^e — the rule
+// r2l_backward_part applies on the host to the MSE gradient scale.  One workgroup (generic mode is not the training loop's).
+__global__ __launch_bounds__(1024) void r2l_gscale_kernel(const float* __restrict__ drgb, int64_t n, float* __restrict__ out) {
+    __shared__ float red[1024];
+    float m = 0.f;
+    for (int64_t i = threadIdx.x; i < n; i += 1024) m = fmaxf(m, fabsf(drgb[i]));
+    red[threadIdx.x] = m;
+    __syncthreads();
+    for (int k = 512; k > 0; k >>= 1) {
+        if ((int)threadIdx.x < k) red[threadIdx.x] = fmaxf(red[threadIdx.x], red[threadIdx.x + k]);
+        __syncthreads();
+    }
+    if (threadIdx.x == 0) {
+        float g = 1.0f;
+        if (red[0] > 0.f && red[0] < 3.0e38f) {
+            int e = 0;
+            (void)frexpf(red[0], &e);
+            g = ldexpf(1.0f, 8 - e);
+        }
+        out[0] = g;
+        out[1] = 1.0f / g;
+    }
+}
+
+// The 16 status words behind the fp16 dX stream (r2l_common.h B2S_*), at the start of every step of the fp16 trio: FLAG and
+// AMAX cleared, and — MSE mode — the power of two the step's dX chain runs on written to GSCALE / GINV:
+//   * first step (or after a step that fell back, or a zero gradient): the a-priori rule of rounds 1 - 3, 2^(8 - e) for
+//     grad_scale = m * 2^e (the seed is then <= 64 |rgb - target|), corrected by the size of the tail weights the seed goes
+//     through: x 2^(-3 - e_w) for max |W_tail| = m * 2^e_w (the default init's 1/16 gives 1);
+//   * afterwards the scale is KEPT while the last clean step's largest |chain value| (times grad_scale / its grad_scale: batch
+//     sizes may change) lies in [2^-2, 2^13] scaled — a factor 4 below the guard (R2L_F2_RANGE) and, at the low end, still
+//     2^-23 of the largest value in absolute fp16 (hi + mid) resolution — and re-centred to 2^8 when it leaves that band.
+//     So nets whose gradients live where the a-priori rule expects them (default init, the trained nets measured so far) run
+//     bit for bit as in round 3, and a net whose gradients drift (or start) elsewhere follows on the next step instead of
+//     falling back (overflow) or silently losing bits (underflow) from then on.
+// Powers of two commute with fp32 rounding: whatever the scale, the bf16x3 fallback run on it is bit-identical after unscaling.
+// (A kernel, not hipMemsetAsync: a memset node captured into a hipGraph wrote a stale pattern on replay, ROCm 7.0; the history
+// is device state, so captured steps adapt on replay as eager ones do.)  generic mode (mse == 0): GSCALE is r2l_gscale_kernel's.
+__global__ __launch_bounds__(64) void r2l_bwd_prepare_kernel(unsigned* status, const float* __restrict__ tail_w, float grad_scale,
+                                                             int mse) {
+    float wm = 0.f;
+    if (mse)
+        for (int i = threadIdx.x; i < 3 * R2L_W; i += 64) wm = fmaxf(wm, fabsf(tail_w[i]));
+#pragma unroll
+    for (int off = 32; off >= 1; off >>= 1) wm = fmaxf(wm, __shfl_xor(wm, off));
+    if (threadIdx.x != 0) return;
+    const float gs = fabsf(grad_scale);
+    const bool valid = status[B2S_MAGIC] == F2_MAGIC;
+    const bool clean = valid && status[B2S_FLAG] == 0u;
+    const float a_raw = valid ? __builtin_bit_cast(float, status[B2S_AMAX]) : 0.f;  // 0: the chain did not run (forward fell back)
+    const float a = clean ? a_raw : 0.f;
+    const float g_prev = valid ? __builtin_bit_cast(float, status[B2S_GSCALE]) : 0.f;
+    const float gs_prev = valid ? __builtin_bit_cast(float, status[B2S_GS]) : 0.f;
+    int ex_prev = 0;
+    const bool g_ok = g_prev > 0.f && g_prev < 3.0e38f && frexpf(g_prev, &ex_prev) == 0.5f;  // a power of two: 2^(ex_prev - 1)
+    float peak = valid ? __builtin_bit_cast(float, status[B2S_PEAK]) : 0.f;
+    unsigned trips = valid ? status[B2S_TRIPS] : 0u;
+    if (valid && status[B2S_FLAG] != 0u) ++trips;
+    // a step whose CHAIN tripped the guard (round 5): its AMAX is the truth while every value stayed finite in fp32 — the guard
+    // trips at 32768, the fp32 B values are tracked before their fp16 conversion — so the next step re-centres on it instead of
+    // repeating the a-priori rule (and tripping again, step after step, on a net whose gradients grow through the body);
+    // AMAX = inf / NaN: only "too large" is known — the scale drops by 2^8 and the following step refines it
+    bool blind = false;
+    if (clean && g_ok && a > 0.f && a < 3.0e38f) peak = a / g_prev;  // unscaled amax of the last clean step
+    else if (!clean && valid && g_ok && a_raw > 0.f && a_raw < 3.0e38f) peak = a_raw / g_prev;
+    else if (!clean && valid && g_ok && !(a_raw <= 0.f) && !(a_raw < 3.0e38f)) { blind = true; peak = 0.f; }
+    else if (!clean) peak = 0.f;                                      // (a step whose forward fell back says nothing reliable)
+    if (mse) {
+        int ex = 0;
+        const float est = (peak > 0.f && gs_prev > 0.f && gs > 0.f && g_ok) ? peak * (gs / gs_prev) : 0.f;
+        if (blind) {
+            ex = (ex_prev - 1) - 8;
+        } else if (est > 0.f && est < 3.0e38f) {
+            const float scaled = est * g_prev;
+            if (scaled >= 0.25f && scaled <= 8192.f) {
+                ex = ex_prev - 1;
+            } else {
+                (void)frexpf(est, &ex);
+                ex = 8 - ex;
+            }
+        } else if (gs > 0.f) {
+            int e = 0, ew = -3;
+            (void)frexpf(gs, &e);
+            if (wm > 0.f && wm < 3.0e38f) (void)frexpf(wm, &ew);
+            ex = (8 - e) + (-3 - ew);
+        }
+        ex = ex > 120 ? 120 : (ex < -120 ? -120 : ex);
+        status[B2S_GSCALE] = __builtin_bit_cast(unsigned, ldexpf(1.0f, ex));
+        status[B2S_GINV] = __builtin_bit_cast(unsigned, ldexpf(1.0f, -ex));
+        status[B2S_GS] = __builtin_bit_cast(unsigned, gs);
+    } else {
+        status[B2S_GS] = 0u;
+    }
+    status[B2S_PEAK] = __builtin_bit_cast(unsigned, peak);
+    status[B2S_TRIPS] = trips;
+    status[B2S_MAGIC] = F2_MAGIC;
+    status[B2S_AMAX] = 0u;
+    status[B2S_EXPANDED] = 0u;
+    status[B2S_FLAG] = 0u;
+}
+
 // ------------------------------------------------------------------------------------------------------------------
 // host side
 // ------------------------------------------------------------------------------------------------------------------
@@ -299,5 +403,20 @@ int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, 
     if (a.stash_mid != 0u) hipLaunchKernelGGL(r2l_bwd2_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
     else hipLaunchKernelGGL(r2l_bwd2_kernel<false>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// opens a step of the fp16 trio in front of its dX chain (here or r2l_coopf_bwd.hip); generic mode: drgb != nullptr
+// (a kernel, not hipMemsetAsync: a memset node captured into a hipGraph wrote a stale 16-byte pattern instead of zeros on
+// replay — ROCm 7.0 —, which sent every replayed step to the fallback kernels)
+int r2l_bwd2_open_step(unsigned* status, const float* params, int n_block, float grad_scale, const float* drgb, int64_t N,
+                       hipStream_t stream) {
+    hipLaunchKernelGGL(r2l_bwd_prepare_kernel, dim3(1), dim3(64), 0, stream, status, params + b2_off_tail_w(n_block), grad_scale,
+                       drgb == nullptr ? 1 : 0);
+    R2L_CHECK(hipGetLastError());
+    if (drgb != nullptr) {
+        hipLaunchKernelGGL(r2l_gscale_kernel, dim3(1), dim3(1024), 0, stream, drgb, 3 * N, reinterpret_cast<float*>(status + B2S_GSCALE));
+        R2L_CHECK(hipGetLastError());
+    }
     return 0;
 }

@@ -467,7 +467,7 @@ __host__ __device__ static inline int64_t r2l_bwd2_stream_floats(int n_block) { 
 // the 16 status words of a training step's backward (fp16 trio).  FLAG: this step belongs to the bf16x3 kernels (range guard of
 // the dX chain, or the forward already fell back); GSCALE / GINV: the power of two the chain runs on and its inverse — every
 // kernel of the step reads them here; AMAX: largest |B value| of the step's chain (scaled units, float bits); MAGIC / PEAK / GS:
-// history for the next step's scale (r2l_bwd_prepare_kernel, r2l_backward.hip): unscaled gradient amax and grad_scale of the
+// history for the next step's scale (r2l_bwd_prepare_kernel, r2l_bwd2.hip): unscaled gradient amax and grad_scale of the
 // last clean step; TRIPS: steps that fell back (telemetry)
 // EXPANDED: workgroups of the fallback pack that have expanded their slot of an fp16 forward stash (r2l_bwd3.hip), per step
 enum { B2S_FLAG = 0, B2S_GSCALE = 4, B2S_GINV = 5, B2S_AMAX = 8, B2S_MAGIC = 9, B2S_TRIPS = 10, B2S_PEAK = 11, B2S_GS = 12, B2S_EXPANDED = 13 };

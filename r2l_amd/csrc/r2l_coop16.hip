@@ -529,7 +529,7 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_c16_kernel(const C16BwdArgs a)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
-// launchers used by the C ABI entry points in r2l_forward.hip / r2l_backward.hip
+// launchers used by the C ABI entry points in r2l_forward.hip / r2l_backward.hip (host only; the fp32 chain: r2l_bwd32.hip)
 // ------------------------------------------------------------------------------------------------------------------
 int r2l_coop16_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
                        const float* c2w_host12, int H, int W, float focal, const float* wstream16, const float* params,

@@ -1,6 +1,7 @@
-// r2l_dw.h — what the weight-gradient kernels of the body layers share (r2l_backward.hip: fp32-MFMA and bf16x3 kernels, the
+// r2l_dw.h — what the weight-gradient kernels of the body layers share (r2l_dw_body.hip: fp32-MFMA and bf16x3 kernels, the
 // slab reduce; r2l_dw16.hip: the fp16 kernel of the default training trio): flat-parameter offsets, the (layer, ray-chunk)
-// work list and the per-workgroup partial-sum slab.
+// work list and the per-workgroup partial-sum slab; the head gradient's arguments and encoding columns; and the launchers of
+// the backward's stages that r2l_backward.hip (host only) calls.
 #pragma once
 #include "r2l_common.h"
 
@@ -61,7 +62,7 @@ struct R2LDwArgs {
 #define DW_TAIL_SLAB_BASE (DW_BODY_SLAB + DW_HEAD_SLAB_MAX)
 #define DW_TAIL_SLAB ((int64_t)512 * 4 * R2L_W)
 
-// ---- head weight gradient (r2l_backward.hip: fp32 MFMA; r2l_dw_head16.hip: fp16 MFMA of the default trio) ----------------------
+// ---- head weight gradient (r2l_dw_head.hip: fp32 MFMA; r2l_dw_head16.hip: fp16 MFMA of the default trio) ----------------------
 struct R2LDwHeadArgs {
     const float* rays_o;
     const float* rays_d;
@@ -115,3 +116,22 @@ int r2l_dw_head16_launch(const R2LDwHeadArgs& a, int64_t slices, hipStream_t str
 // (r2l_f2.h).  run_unless: the dX chain's status word — when the step fell back to the bf16x3 chains (fp32 stash) this launch
 // raises *status and returns, and the bf16x3 weight-gradient kernel launched behind it (run_if = status) does the work.
 int r2l_dw16_launch(const R2LDwArgs& a, int64_t wgs, const unsigned* run_unless, hipStream_t stream);
+
+// ---- the stages of a step, one launcher per file (called by r2l_backward_part_cfg, r2l_backward.hip) ---------------------------
+// fp32-MFMA dX chain (r2l_bwd32.hip)
+int r2l_bwd32_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
+                       const float* wstream_bwd32, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
+                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream);
+// opens a step of the fp16 trio in front of its dX chain (r2l_bwd2.hip: the B2S_* status words); drgb: generic mode, else nullptr
+int r2l_bwd2_open_step(unsigned* status, const float* params, int n_block, float grad_scale, const float* drgb, int64_t N,
+                       hipStream_t stream);
+// body stage (r2l_dw_body.hip): the kernel dw_body (R2L_DWBODY_*, r2l_dispatch.h) names — DW16: r2l_dw16_launch with
+// r2l_dw_body3c_kernel behind it unless no_fallback —, then the slab reduce when a.slab is given
+int r2l_dw_body_launch(R2LDwArgs a, int dw_body, int64_t wgs, unsigned* status, bool no_fallback, hipStream_t stream);
+// head stage (r2l_dw_head.hip): dw_head16: r2l_dw_head16_launch in front, the fp32 kernel behind it unless no_fallback; then
+// the reduce when a.slab is given
+int r2l_dw_head_launch(R2LDwHeadArgs a, int64_t slices, bool dw_head16, const unsigned* status, bool no_fallback,
+                       hipStream_t stream);
+// tail stage (r2l_dw_tail.hip): part = per-workgroup partials (then reduced) or nullptr -> atomics
+int r2l_dw_tail_launch(const float* dpre, const float* x0, const float* xn, float* grads, float* part, int n_block, int64_t N,
+                       int64_t wgs, int64_t rays_per_wg, hipStream_t stream);

@@ -25,7 +25,7 @@
 //     (8 x v_fma_mix_f32, exact; waves with wi = 0).
 //   * one barrier per tile, in its middle: behind it the next tile's image is published and the current one's buffer is handed
 //     to the DMA of the tile four steps ahead.
-// Work split, slab partials and the reduce are those of r2l_backward.hip (r2l_dw.h).
+// Work split, slab partials and the reduce are those of r2l_dw_body.hip (r2l_dw.h).
 #include "r2l_f2.h"
 #include "r2l_dw.h"
 

@@ -3,7 +3,7 @@
 // Gh = gx[0] = dL/d(head pre-activation) [N,256] fp32 (written by the dX chain), PE = the 1008-d positional encoding of the
 // ray's 16 sample points, recomputed on the fly from (rays_o, rays_d, t_rand, ztab) exactly as the forward did (never stored:
 // 4 KB/ray).  Replaces the head part of loss.backward() (/root/reference/main.py:1403-1404) like r2l_dw_head_kernel
-// (r2l_backward.hip), on the fp16 matrix pipe: both operands are rounded to fp16 (PE values lie in [-1, 1] or are point
+// (r2l_dw_head.hip), on the fp16 matrix pipe: both operands are rounded to fp16 (PE values lie in [-1, 1] or are point
 // coordinates; Gh carries the chain's power-of-two scale so that it sits in fp16's range) and ONE v_mfma_f32_32x32x16_f16
 // takes the place of eight v_mfma_f32_32x32x2_f32 — the same argument as r2l_dw16.hip: a reduction over ~10^5 rays of
 // independently rounded products.  The fp32 kernel took 0.71 ms of an 8.3 ms step (46 % of the fp32 MFMA peak).

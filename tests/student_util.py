@@ -217,7 +217,7 @@ def split_flat(flat, sd):
 
 # ---- the table of shapes (shared by the CPU conditions and the GPU tests) -------------------------------------------------
 # Where a step can be cut, gone through source by source (ray counts; every unit gets an N on both sides of it, or of a multiple):
-#   2      r2l_backward.hip head weight gradient: a k-step pairs rays 2s, 2s + 1; rays per slice rounded up to even
+#   2      r2l_dw_head.hip head weight gradient: a k-step pairs rays 2s, 2s + 1; rays per slice rounded up to even
 #   16     coop16 tiles (r2l_coop16.hip C16_RAYS); k-step of r2l_dw16.hip and r2l_dw_head16.hip
 #   32     R2L_TILE_RAYS: one wave's tile in every other chain, the cooperative fp16 chains' tile, the stash's padding unit
 #   64     DW_CHUNK, the body weight gradients' work unit (r2l_dw.h); two 32-ray tiles of one cooperative workgroup (coopf2)

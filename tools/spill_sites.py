@@ -1,7 +1,7 @@
 """Where a kernel's spilled registers are touched: per loop of the device assembly, the number of MFMA, scratch (spill / fill),
 global-load and LDS instructions.  A spill count alone does not say whether the scratch traffic sits in the hot loop or in a
 prologue / flush that runs once per workgroup.  Runs without a GPU:
-    python tools/spill_sites.py r2l_backward.hip r2l_dw_body_kernel > profiles/rNN_dw_body_spill_sites.txt
+    python tools/spill_sites.py r2l_dw_body.hip r2l_dw_body_kernel > profiles/rNN_dw_body_spill_sites.txt
 """
 import os
 import re
