@@ -524,6 +524,82 @@ int r2l_store_append(const float* rows_in, int64_t n_rows, float* store, int64_t
 int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
                     float* batch, int32_t* ids_out, void* stream);
 
+/* r2l_train_batch: the batch of a student step in ONE launch instead of r2l_store_batch -> r2l_pool_pick -> r2l_pool_augment
+ * (csrc/r2l_student_step.hip).  With B = n_draw * rays_per_shard, out_o / out_d / out_t are [B + n_out, 3] contiguous:
+ *   rows [0, B):          the rows of the shards id(draw0 + j), j < n_draw — id exactly as specified for r2l_store_batch above —
+ *                         de-interleaved from the store's 9-float rows [o, d, rgb];
+ *   rows [B, B + n_out):  the pool rows pi(pool_key, n_pool_rows)(i), i < n_out: the index sequence of r2l_pool_pick.
+ * ids_out (device int32[n_draw], or NULL) receives the shard ids, idx_out (device int64[n_out], required with n_out > 0: the
+ * replace step of r2l_pool_store needs it) the picked pool rows.  n_out == 0: the shard rows alone (pool may be NULL).
+ * Stateless: the arguments are checked before the launch, one kernel is enqueued on `stream`, nothing synchronises; all offsets
+ * are 64-bit.  store, out_o, out_d and out_t must be 16-byte aligned (the shard words are read and the batch rows written as
+ * 16-byte words).  hipErrorInvalidValue (with r2l_last_error): the conditions of r2l_store_batch, n_out < 0 or > n_pool_rows, a
+ * NULL output, a NULL pool / idx_out with n_out > 0.  r2l_amd/raystore.py (train_batch_spec) restates it in numpy. */
+int r2l_train_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
+                    const float* pool /*[n_pool_rows, 9]*/, int64_t n_pool_rows, int64_t n_out, uint64_t pool_key, float* out_o,
+                    float* out_d, float* out_t, int32_t* ids_out, int64_t* idx_out, void* stream);
+
+/* ---- one student training iteration in one library call --------------------------------------------------------------------
+ * What r2l_amd/train_step.py and the driver's loop assemble per iteration from the stages above (RayStore.next ->
+ * HardRayPool.augment -> draw_uniform -> R2LTrainer.step -> HardRayPool.update), behind the C ABI (csrc/r2l_student_step.hip): a
+ * pure function of (store, pool, weights, optimizer state, descriptor).  Those very kernels with those very arguments, in this
+ * order, enqueued on `stream` with no allocation and no host synchronisation; the call keeps no state.  World size 1, the uncut
+ * backward (no segmented chain, no staged buckets: the all-reduce of a data-parallel step sits between 6 and 8).
+ *   1. r2l_train_batch: B = n_draw * rays_per_shard shard rows + (pool_full ? n_out : 0) pool rows;  N = the sum
+ *   2. r2l_draw_uniform of N*16 elements on stream `jitter_stream` of `seed` (perturb == 1; else no t_rand is passed on)
+ *   3. pack == 1: r2l_pack_forward_layout / r2l_pack_backward_layout in the layouts r2l_forward_layout_for_cfg(N, 1, cfg) and
+ *      r2l_backward_layout_for_cfg(N, cfg) name
+ *   4. r2l_forward_rays_cfg with stash        5. hipMemsetAsync of grads
+ *   6. r2l_backward_part_cfg(R2L_BWD_ALL), grad_scale = 2 lw_rgb / (3 N)      7. r2l_loss_finish, inv_denom = lw_rgb / (3 N)
+ *   8. r2l_adam_step_guarded(lr, beta1, beta2, eps, step, gradient scale 1, no guard word)
+ *   9. n_in > 0: r2l_pool_select of the first B rows, k = n_in, then r2l_pool_store — appended at row pool_rows while the pool is
+ *      not full, replacing the rows idx_out[0 .. n_in) of step 1 once it is.
+ * pack: the weight streams are packed IN FRONT of the step, as the trainer's lazy version check packs them: on exit they hold the
+ * parameters the step READ, not the updated ones, and a render that follows must re-pack (r2l_amd: engine.mark_dirty()).  A host
+ * that does nothing else with the weights passes pack = 0 at its first step (after packing both streams once itself) and 1 from
+ * its second step on.  r2l_adam_step_packed (R2L_ADAM_PACK of the trainer) is not used by this call.  Range control and the bf16x3
+ * fallback live inside the forward and backward entry points: nothing to do here.
+ * The host computes pool_key (the key r2l_pool_pick would be given), jitter_stream (the trainer: 2^61 + 4096 * iteration + rank),
+ * lr and the pool's fill state — plain arithmetic; passing them in is what keeps the call a pure function.
+ *
+ * Caller-owned: store (n_shards filled shards), pool ([pool_capacity_rows, 9]; NULL allowed when nothing is read or written:
+ * n_in == 0 and no augmented rows), ztab[32], params / grads / exp_avg / exp_avg_sq (r2l_param_count(n_block) each; grads is
+ * overwritten), wstream / wstream_bwd (zero-filled once after allocation, packed from params before a step with pack == 0),
+ * loss_out[2] (loss, psnr), rgb_out ([N, 3], or NULL: the step's rgb then stays in the work buffer).
+ * work: 16-byte aligned, r2l_student_step_work_floats(d) floats (-1 with r2l_last_error for an invalid descriptor).  Every part
+ * rounded up to a multiple of 1024 floats, so that every part starts on a 4 KiB boundary; with slot = r2l_stash_slot_floats(N):
+ *   o, d, t [N,3] each; t_rand [N,16] (perturb); rgb [N,3]; save_x (n_block + 1 slots), save_t (max(n_block, 1) slots), gx, gt
+ *   likewise; dpre [N,3]; sqerr (r2l_num_tiles(N)); the dW slab (r2l_dw_slab_floats()); idx_out (int64 [n_out], pool_full);
+ *   hard (int64 [n_in]); the scratch of r2l_pool_select (r2l_pool_select_work_bytes(B), n_in > 0).
+ * hipErrorInvalidValue (with r2l_last_error naming the field or pointer) before any launch: a NULL required pointer, n_block < 0,
+ * an invalid r2l_config, rays_per_shard not a positive multiple of 4, n_shards < 1, n_draw < 1, draw0 < 0, perturb / pack /
+ * pool_full not 0 or 1, n_in > n_out or n_in > B, pool_rows + n_in > pool_capacity_rows while the pool is not full, pool_full with
+ * n_out > pool_rows, 2^31 rays or more, step < 1, non-zero reserved, a work buffer that is not 16-byte aligned.
+ * r2l_amd/train_step.py (R2LTrainer.fused_step) and tests/chost/train_host.c are the worked examples. */
+typedef struct r2l_student_step_desc {
+    int n_block;
+    int perturb, pack, pool_full;     /* 0 | 1 */
+    const r2l_config* cfg;            /* dispatch of every launch of the step; NULL = AUTO */
+    int64_t rays_per_shard;           /* positive multiple of 4 */
+    int64_t n_shards;                 /* FILLED shards of the store at this step, >= 1 */
+    int64_t n_draw, draw0;            /* this step takes the draws draw0 .. draw0 + n_draw - 1 */
+    uint64_t store_seed;              /* seed of r2l_store_batch */
+    int64_t pool_capacity_rows;
+    int64_t pool_rows;                /* rows filled on entry */
+    int64_t n_in, n_out;              /* hard rays entering the pool per step / pool rows appended to a batch once pool_full */
+    uint64_t pool_key;                /* key of r2l_pool_pick for this step (read with pool_full and n_out > 0) */
+    uint64_t seed, jitter_stream;     /* r2l_draw_uniform(seed, jitter_stream) */
+    double lw_rgb;
+    float lr, beta1, beta2, eps;
+    int64_t step;                     /* Adam's step count of this update, 1 <= step < 2^60 */
+    int reserved[4];                  /* must be 0 */
+} r2l_student_step_desc;
+int64_t r2l_student_step_work_floats(const r2l_student_step_desc* d);   /* -1: invalid descriptor */
+int r2l_student_train_step(const r2l_student_step_desc* d, const float* store, float* pool, const float* ztab, float* params,
+                           float* grads, float* exp_avg, float* exp_avg_sq, float* wstream, float* wstream_bwd,
+                           float* loss_out /* dev [2]: loss, psnr */, float* rgb_out /* dev [N,3] or NULL */, float* work,
+                           void* stream);
+
 /* ---- pixel sampler of teacher training (batching mode without a bank of rays) ----------------------------------------------
  * The reference's use_batching mode (main.py:1137-1162, 1199-1210) builds the rays of every pixel of every training image,
  * shuffles that bank and hands out N_rand rows per step.  Here one draw is one pixel and its ray is computed when it is drawn:

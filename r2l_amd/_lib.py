@@ -48,6 +48,18 @@ class TeacherStepDesc(ctypes.Structure):
 _stepp = ctypes.POINTER(TeacherStepDesc)
 
 
+class StudentStepDesc(ctypes.Structure):
+    """r2l_student_step_desc of include/r2l_hip.h (r2l_student_train_step)."""
+    _fields_ = [("n_block", _i), ("perturb", _i), ("pack", _i), ("pool_full", _i), ("cfg", _cfgp), ("rays_per_shard", _l),
+                ("n_shards", _l), ("n_draw", _l), ("draw0", _l), ("store_seed", ctypes.c_uint64), ("pool_capacity_rows", _l),
+                ("pool_rows", _l), ("n_in", _l), ("n_out", _l), ("pool_key", ctypes.c_uint64), ("seed", ctypes.c_uint64),
+                ("jitter_stream", ctypes.c_uint64), ("lw_rgb", ctypes.c_double), ("lr", _f), ("beta1", _f), ("beta2", _f),
+                ("eps", _f), ("step", _l), ("reserved", _i * 4)]
+
+
+_sstepp = ctypes.POINTER(StudentStepDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -136,6 +148,9 @@ SIGNATURES = {
     "r2l_pool_select": (_i, [_p, _p, _l, _l, _l, _l, _p, _p, _p, _p]),
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
+    "r2l_train_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
+    "r2l_student_step_work_floats": (_l, [_sstepp]),
+    "r2l_student_train_step": (_i, [_sstepp] + [_p] * 13),
     "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
     "r2l_teacher_step_work_floats": (_l, [_stepp]),
     "r2l_teacher_train_step": (_i, [_stepp] + [_p] * 15),

@@ -17,7 +17,7 @@ from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
 from .metrics import flip, img2mse, lpips, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
-from .options import parse_args, validate_accelerated
+from .options import parse_args, validate_accelerated, validate_fused_iter
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -86,11 +86,44 @@ class HardRayPool:
             lib = _lib.load()
             ix = torch.empty(n_out, dtype=torch.int64, device=device)
             self._draws += 1
-            key = (self.seed * 0x9E3779B97F4A7C15 + self._draws * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+            key = self._key(self._draws)
             _lib.check(lib.r2l_pool_pick(ctypes.c_void_p(ix.data_ptr()), n_out, n_rows, key,
                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "r2l_pool_pick")
             return ix
         return torch.as_tensor(self.rng.permutation(n_rows)[:n_out], device=device)
+
+    def _key(self, draws):
+        """Key of the keyed row choice number `draws` (counted from 1) of this pool."""
+        return (self.seed * 0x9E3779B97F4A7C15 + draws * 0xD1B54A32D192ED03) & 0xFFFFFFFFFFFFFFFF
+
+    # ---- a step that moves the rows itself (r2l_student_train_step: R2LTrainer.fused_step) ------------------------------------
+    def plan(self, batch_size, device="cpu"):
+        """What the next step on a batch of `batch_size` rays does with the pool, as augment() + update() would: n_in hard rays
+        enter (appended at row pool_rows while the pool is not full, else replacing picked rows), n_out rows picked with `key`
+        are appended to the batch once it is full.  Allocates the store (on `device`) if this is the first step.  Changes
+        nothing else: advance() does."""
+        n_in, n_out = self.sizes(batch_size)
+        if n_in > 0 and self._store is None:
+            self._allocate(batch_size, n_in, torch.device(device))
+        rows = self._n if self._store is not None else 0
+        return {"n_in": max(n_in, 0), "n_out": n_out if n_in > 0 else 0, "pool_rows": rows, "full": bool(self.full),
+                "capacity": self._store.shape[0] if self._store is not None else 0,
+                "key": self._key(self._draws + 1) if self.full else 0}
+
+    def advance(self, batch_size):
+        """The bookkeeping of augment() + update() for a step whose rows were moved by the library (plan() said how): the draw
+        counter, the fill count and the fill state."""
+        n_in, _ = self.sizes(batch_size)
+        if self.full:
+            self._draws += 1
+            self._ix_out = None  # (the rows that step picked stayed in its work buffer: nothing of an earlier augment() is valid)
+            return
+        if n_in <= 0:
+            return
+        self._n += n_in
+        self.pool = self._store[:self._n]
+        if self._n >= batch_size * self.mul:
+            self.full = True
 
     @staticmethod
     def _rows(x):
@@ -653,6 +686,7 @@ def lpips_field(misc):
 def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
+    validate_fused_iter(args)
     is_teacher = args.model_name == "nerf"
     if is_teacher and (not args.render_only or args.benchmark):
         # (--benchmark times render_func = the R2L student's forward, main.py:401-404,1124-1133)
@@ -663,6 +697,8 @@ def main(argv=None):
     if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
         raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
                                   "r2l_draw_uniform of libr2l_hip.so); this run is on the CPU")
+    if not (args.render_only or args.benchmark):
+        validate_fused_iter(args, world, device.type)
     np.random.seed(0)
     # every rank must build the same student: torch's default generator is seeded per process otherwise (the reference had
     # ONE module that nn.DataParallel re-broadcast every step, main.py:472-479); R2LTrainer additionally broadcasts rank 0's
@@ -849,6 +885,10 @@ def main(argv=None):
             else:
                 logger.info("hard-ray pool: the checkpoint carries none (written without --r2l_device_pool?): it starts empty")
     pool_extra = lambda: {"r2l_hard_pool": pool.state_dict()} if save_pool else None
+    if args.r2l_fused_iter:
+        # the whole iteration below — batch, pool rows, jitter, step, pool update — is one call of r2l_student_train_step
+        logger.info("[Config] Fused iteration (--r2l_fused_iter): one library call per iteration, jitter from Philox stream "
+                    "2^61 + 4096 * iteration + %d of seed %d" % (rank, jitter_seed))
     hist_psnr, t_data, t_batch = 0., 0., 0.
     logger.info("Begin training")
     for i in range(start + 1, args.N_iters + 1):
@@ -859,29 +899,32 @@ def main(argv=None):
             logger.info("Iter %d ray store grew to %d shards (%d poses pending)" % (i, loader.n_shards, filler.pending))
             if filler.done:
                 filler = None
-        batch = loader.next()  # device tensor (shard reader: its H2D copy ran on the loader's stream during the last step)
-        rays_o, rays_d, target = batch[:, :3], batch[:, 3:6], batch[:, 6:9]
-        batch_size = rays_o.shape[0]
-        if pool is not None:
-            rays_o, rays_d, target = pool.augment(rays_o, rays_d, target)
-        t_data = time.time() - t0
-        n_global = None
-        if uneven:  # this step's rays over all ranks: shard rows + what each rank's hard-ray pool appends (deterministic)
-            rows = [q * loader.rows_per_file for q in shards]
-            n_global = [r + (pool.extra_rays(r, i - start - 1) if pool is not None else 0) for r in rows]
-            # the ray count PREDICTED for this rank is the weight its gradient gets: it must be the batch it really holds (a
-            # shard with another row count, a pool that fills differently: silently wrong weights, and ranks that disagree
-            # on the collective sequence — ADVICE r3)
-            if rays_o.shape[0] != n_global[rank]:
-                raise RuntimeError("uneven --N_rand: rank %d holds %d rays in iteration %d, the share computed on every rank "
-                                   "says %d (shards with differing row counts?)" % (rank, rays_o.shape[0], i, n_global[rank]))
-        t_rand = None
-        if args.r2l_device_pool and args.perturb > 0:  # (perturb 0: nothing is drawn)
-            n = rays_o.shape[0]
-            t_rand = draw_uniform(n * N_SAMPLE, jitter_seed, 2**61 + i * 4096 + rank, device).view(n, N_SAMPLE)
-        rgb, loss_out = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, t_rand=t_rand, n_global=n_global)
-        if pool is not None:
-            pool.update(rgb, rays_o, rays_d, target, batch_size)
+        if args.r2l_fused_iter:  # one library call; the store's shard count of the moment goes into its descriptor
+            _, loss_out = trainer.fused_step(loader, pool, lr, i, perturb=args.perturb, seed=jitter_seed, rank=rank)
+        else:
+            batch = loader.next()  # device tensor (shard reader: its H2D copy ran on the loader's stream during the last step)
+            rays_o, rays_d, target = batch[:, :3], batch[:, 3:6], batch[:, 6:9]
+            batch_size = rays_o.shape[0]
+            if pool is not None:
+                rays_o, rays_d, target = pool.augment(rays_o, rays_d, target)
+            t_data = time.time() - t0
+            n_global = None
+            if uneven:  # this step's rays over all ranks: shard rows + what each rank's hard-ray pool appends (deterministic)
+                rows = [q * loader.rows_per_file for q in shards]
+                n_global = [r + (pool.extra_rays(r, i - start - 1) if pool is not None else 0) for r in rows]
+                # the ray count PREDICTED for this rank is the weight its gradient gets: it must be the batch it really holds (a
+                # shard with another row count, a pool that fills differently: silently wrong weights, and ranks that disagree
+                # on the collective sequence — ADVICE r3)
+                if rays_o.shape[0] != n_global[rank]:
+                    raise RuntimeError("uneven --N_rand: rank %d holds %d rays in iteration %d, the share computed on every rank "
+                                       "says %d (shards with differing row counts?)" % (rank, rays_o.shape[0], i, n_global[rank]))
+            t_rand = None
+            if args.r2l_device_pool and args.perturb > 0:  # (perturb 0: nothing is drawn)
+                n = rays_o.shape[0]
+                t_rand = draw_uniform(n * N_SAMPLE, jitter_seed, 2**61 + i * 4096 + rank, device).view(n, N_SAMPLE)
+            rgb, loss_out = trainer.step(rays_o, rays_d, target, lr, perturb=args.perturb, t_rand=t_rand, n_global=n_global)
+            if pool is not None:
+                pool.update(rgb, rays_o, rays_d, target, batch_size)
         t_batch = time.time() - t0
         if i % args.i_print == 0:
             loss, psnr = loss_out.tolist()  # the only host sync of the loop, every i_print iterations

@@ -76,6 +76,11 @@ FLAGS = {
     # every checkpoint, so that --resume on a ray store repeats the uninterrupted run bit for bit; opt-in, GPU only.
     # utils/create_data.py / utils/train_nerf.py ignore it
     "r2l_device_pool": ("flag", False),
+    # student training with one library call per iteration (r2l_student_train_step: batch from the ray store, pool rows, jitter,
+    # forward, backward, Adam and the pool update behind the C ABI), bit for bit the --r2l_device_store --r2l_device_pool loop;
+    # opt-in, one GPU, needs a ray store and, with --hard_ratio, --r2l_device_pool.  utils/create_data.py / utils/train_nerf.py
+    # ignore it
+    "r2l_fused_iter": ("flag", False),
     # LPIPS(AlexNet, v0.1) in the test-set loop (r2l_lpips): the user's weight file(s), one path or two joined by ':' (torchvision's
     # AlexNet checkpoint and the lpips package's alex.pth, or a saved lpips.LPIPS().state_dict(): metrics.lpips_params).  None are
     # shipped; '' = no LPIPS, every log line as it always was
@@ -221,6 +226,22 @@ def validate_ray_store(args):
         raise ValueError("--r2l_kd_every needs --r2l_online_kd")
     if args.r2l_device_store and (args.data_mode != "rays" or not args.datadir_kd):
         raise ValueError("--r2l_device_store needs --data_mode rays and --datadir_kd")
+
+
+def validate_fused_iter(args, world=1, device_type="cuda"):
+    """--r2l_fused_iter (main.py only): the student's iteration as one library call draws its batch from a ray store and moves
+    the pool's rows itself, on one GPU.  Names what is missing before anything is loaded."""
+    if not args.r2l_fused_iter:
+        return
+    if not (args.r2l_device_store or args.r2l_online_kd):
+        raise ValueError("--r2l_fused_iter draws its batches from a ray store: it needs --r2l_device_store or --r2l_online_kd")
+    if args.hard_ratio and not args.r2l_device_pool:
+        raise ValueError("--r2l_fused_iter with --hard_ratio needs --r2l_device_pool (the hard rays are ranked inside the call)")
+    if device_type != "cuda":
+        raise NotImplementedError("--r2l_fused_iter runs r2l_student_train_step of libr2l_hip.so on a GPU; this run is on the CPU")
+    if world != 1:
+        raise NotImplementedError("--r2l_fused_iter runs at world size 1 (the gradient all-reduce of a data-parallel step sits "
+                                  "inside the call's sequence); this run has %d ranks" % world)
 
 
 def parse_teacher_config(path, teacher_ckpt=None):

@@ -90,6 +90,24 @@ def shard_ids(seed, n_shards, draw0, n_draw):
     return out
 
 
+def train_batch_spec(store, n_shards, rays_per_shard, draw0, n_draw, seed, pool=None, n_pool_rows=0, n_out=0, pool_key=0):
+    """What r2l_train_batch writes, in numpy: (out_o, out_d, out_t, ids, idx).  store: the store's rows [>= n_shards *
+    rays_per_shard, 9]; pool: [>= n_pool_rows, 9].  out_*: float32[n_draw * rays_per_shard + n_out, 3] — the rows of the shards
+    shard_ids(seed, n_shards, draw0, n_draw), then the pool rows perm(pool_key, n_pool_rows)[:n_out]; ids int32[n_draw], idx
+    int64[n_out]."""
+    store = np.asarray(store, dtype=np.float32).reshape(-1, 9)
+    rps = int(rays_per_shard)
+    ids = shard_ids(seed, n_shards, draw0, n_draw)
+    rows = [store[i * rps:(i + 1) * rps] for i in ids]
+    idx = np.empty(0, dtype=np.int64)
+    if n_out > 0:
+        idx = perm_at(pool_key, n_pool_rows, np.arange(n_out, dtype=np.uint64))
+        rows.append(np.asarray(pool, dtype=np.float32).reshape(-1, 9)[idx])
+    rows = np.concatenate(rows, 0) if rows else np.empty((0, 9), dtype=np.float32)
+    o, d, t = (np.ascontiguousarray(rows[:, c:c + 3]) for c in (0, 3, 6))
+    return o, d, t, ids.astype(np.int32), idx
+
+
 def _p(t):
     return ctypes.c_void_p(t.data_ptr()) if t is not None else None
 
@@ -222,6 +240,20 @@ class RayStore:
         return self._buf[k]
 
     __next__ = next
+
+    def plan(self, n_files=None):
+        """What a caller that draws the next batch itself (r2l_train_batch, r2l_student_train_step) needs: the store's base
+        pointer, the shards filled at this moment, rays per shard, the sampler's seed, and the draws next() would take.
+        advance() afterwards moves the counter as next() does."""
+        if self.data is None:
+            raise RuntimeError("RayStore is closed")
+        if self.n_shards < 1:
+            raise RuntimeError("RayStore.plan: the store is empty")
+        return {"ptr": _p(self.data), "n_shards": self.n_shards, "rays_per_shard": self.rows_per_file, "seed": self.seed,
+                "draw0": self.draw, "n_draw": int(self.n_files if n_files is None else n_files)}
+
+    def advance(self, n_files=None):
+        self.draw += int(self.n_files if n_files is None else n_files)
 
     def __iter__(self):
         return self

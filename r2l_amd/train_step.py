@@ -84,6 +84,7 @@ class R2LTrainer:
         self.cap = 0
         self._fused_repack = False
         self.dw_slab = None
+        self._fused_work = self._fused_rgb = None  # fused_step: its work buffer (grown on demand) and the step's rgb
         self._alloc_state()
 
     # ---- buffers --------------------------------------------------------------------------------------------------
@@ -399,6 +400,92 @@ class R2LTrainer:
         rgb = self.forward_backward(rays_o, rays_d, target, perturb, t_rand, n_global=n_global)
         self.allreduce_grads()
         self.adam(lr)
+        return rgb, self.loss_out
+
+    # ---- the whole iteration in one library call (include/r2l_hip.h r2l_student_train_step; driver --r2l_fused_iter) ----------------
+    def _fused_pack(self, n):
+        """The lazy version check of forward_backward for a fused step of n rays: 1 if BOTH streams are stale in the layouts the
+        step reads (the call then packs them, and they are booked as packed here), else whatever is stale is packed now and 0."""
+        eng = self.eng
+        if not eng._aliased():
+            eng.flatten(eng.params[0].device)
+        if eng._packed_version is None:
+            eng._packed_version = {16: None, 32: None, 3: None, 2: None}
+        if self._bwd_packed is None:
+            self._bwd_packed = {16: None, 32: None, 3: None, 2: None}
+        eff = eng.effective_config()
+        ver, lf = eng.version(), eng.layout_for(n, True)
+        bver, lb = (ver, eff.precision, eff.tiling), self.lib.r2l_backward_layout_for_cfg(int(n), eng._cfg())
+        if eng._packed_version[lf] != ver and self._bwd_packed[lb] != bver:
+            eng._packed_version[lf], self._bwd_packed[lb] = ver, bver
+            return 1
+        eng.ensure_packed(n)
+        self._pack_bwd(n)
+        return 0
+
+    def fused_step(self, store, pool, lr, iteration, perturb=0., seed=0, rank=0, n_files=None):
+        """One iteration of the --r2l_device_store --r2l_device_pool loop — store.next -> pool.augment -> draw_uniform(stream 2^61 +
+        4096 * iteration + rank of `seed`) -> step -> pool.update — as ONE library call on the current stream, bit for bit the
+        staged loop's result.  store: a RayStore; pool: a HardRayPool(device_select=True) or None.  Advances the store's draw
+        counter and the pool's bookkeeping.  World size 1, the uncut backward; R2L_ADAM_PACK is not honoured (the streams are
+        packed in front of the step).  Returns (rgb[N,3], loss_out[2]) on the device, no host sync; rgb is valid until the next
+        fused step."""
+        if self.world() > 1 or self.force_staged or (self.chain_segments > 1 and not self.segments_disabled):
+            raise NotImplementedError("R2LTrainer.fused_step: world size 1 and the uncut backward only (the gradient all-reduce of "
+                                      "a data-parallel step sits inside the call's sequence)")
+        if pool is not None and not pool.device_select:
+            raise ValueError("R2LTrainer.fused_step: the pool must rank on the device (HardRayPool(device_select=True))")
+        eng, lib = self.eng, self.lib
+        sp = store.plan(n_files)
+        B = sp["n_draw"] * sp["rays_per_shard"]
+        pp = pool.plan(B, eng.device) if pool is not None else {"n_in": 0, "n_out": 0, "pool_rows": 0, "full": False, "capacity": 0, "key": 0}
+        n = B + (pp["n_out"] if pp["full"] else 0)
+        jitter = (2**61 + int(iteration) * 4096 + int(rank)) & (2**64 - 1)
+        pool_ptr = _ptr(pool._store) if pool is not None and pool._store is not None else None
+        if self.calibrate and not self._calibrated:
+            # range control, as forward_backward: forward-only launches on THIS step's batch (a bare r2l_train_batch and its jitter)
+            eng.ensure_packed(n)
+            self._pack_bwd(n)
+            odt = torch.empty(3, n, 3, dtype=torch.float32, device=eng.device)
+            idx = torch.empty(max(n - B, 1), dtype=torch.int64, device=eng.device)
+            _lib.check(lib.r2l_train_batch(sp["ptr"], sp["n_shards"], sp["rays_per_shard"], sp["draw0"], sp["n_draw"], sp["seed"],
+                                           pool_ptr, pp["pool_rows"], n - B, pp["key"], _ptr(odt[0]), _ptr(odt[1]), _ptr(odt[2]), None,
+                                           _ptr(idx), self._stream()), "r2l_train_batch")
+            t_rand = None
+            if perturb > 0:
+                t_rand = torch.empty(n, N_SAMPLE, dtype=torch.float32, device=eng.device)
+                _lib.check(lib.r2l_draw_uniform(_ptr(t_rand), n * N_SAMPLE, int(seed) & (2**64 - 1), jitter, self._stream()),
+                           "r2l_draw_uniform")
+            self._calibrate(odt[0], odt[1], perturb, t_rand)
+            pack = 0
+        else:
+            pack = self._fused_pack(n)
+        self._fused_cfg = eng.effective_config()  # (kept alive: the descriptor points at it)
+        d = _lib.StudentStepDesc(
+            n_block=eng.n_block, perturb=int(perturb > 0), pack=pack, pool_full=int(pp["full"]), cfg=ctypes.pointer(self._fused_cfg),
+            rays_per_shard=sp["rays_per_shard"], n_shards=sp["n_shards"], n_draw=sp["n_draw"], draw0=sp["draw0"],
+            store_seed=sp["seed"], pool_capacity_rows=pp["capacity"], pool_rows=pp["pool_rows"], n_in=pp["n_in"], n_out=pp["n_out"],
+            pool_key=pp["key"], seed=int(seed) & (2**64 - 1), jitter_stream=jitter, lw_rgb=float(self.lw_rgb), lr=float(lr),
+            beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=self.step_count + 1)
+        need = int(lib.r2l_student_step_work_floats(ctypes.byref(d)))
+        if need < 0:
+            _lib.check(1, "r2l_student_step_work_floats")
+        work = self._fused_work
+        if work is None or work.numel() < need:
+            self._fused_work = work = torch.empty(need, dtype=torch.float32, device=eng.device)
+        rgb = self._fused_rgb
+        if rgb is None or rgb.shape[0] != n:
+            self._fused_rgb = rgb = torch.empty(n, 3, dtype=torch.float32, device=eng.device)
+        _lib.check(lib.r2l_student_train_step(ctypes.byref(d), sp["ptr"], pool_ptr, _ptr(eng.ztab(self.ps.z_vals, perturb)), _ptr(eng.flat),
+                                              _ptr(self.grads), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), _ptr(eng.wstream),
+                                              _ptr(self.wstream_bwd), _ptr(self.loss_out), _ptr(rgb), _ptr(work), self._stream()),
+                   "r2l_student_train_step")
+        self.step_count += 1
+        self._guard = None
+        eng.mark_dirty()
+        store.advance(n_files)
+        if pool is not None:
+            pool.advance(B)
         return rgb, self.loss_out
 
     # ---- torch.optim.Adam-compatible state (checkpoint surface: 'optimizer_state_dict', main.py:1528-1529) --------------
