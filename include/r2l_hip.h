@@ -455,6 +455,23 @@ int64_t r2l_lpips_map_floats(int H, int W);
 int r2l_lpips(const float* img_a, const float* img_b, int K, int H, int W, const float* rescale_dev, const float* wpack,
               float* work, float* per_layer, float* maps, float* out, void* stream);
 
+/* The VGG-16 variant (lpips.LPIPS(net='vgg'), version 0.1, eval mode: the one the published NeRF / R2L tables report), same
+ * contract as r2l_lpips.  The same scaling layer, then thirteen 3/1/1 convolutions with bias and ReLU (zero padding after the
+ * scaling layer): 3-64, 64-64 | 64-128, 128-128 | 128-256, 256-256, 256-256 | 256-512, 512-512, 512-512 | 512-512, 512-512,
+ * 512-512, a 2/2 max-pool (floor, no padding) at each '|'; the five feature maps are the last of each group after its ReLU
+ * (64, 128, 256, 512, 512 channels); d_l, v_l and out as above, lin_l with the tap's channel count.
+ * r2l_lpips_vgg_param_floats() = 14716160 flat floats: for l = 0..12 { conv weight [Co,Ci,3,3] (torch order), bias [Co] }, then
+ * lin_0 .. lin_4.  H, W >= 16 (16 -> 8 -> 4 -> 2 -> 1).  r2l_lpips_vgg_work_floats is -1 for K < 1, H or W < 16, or when
+ * 2 K H W does not fit the kernels' int row index; the feature maps are full resolution: 236 MB per 400x400 pair (the file
+ * header of csrc/r2l_lpips_vgg.hip has the plan).  maps: [K, r2l_lpips_vgg_map_floats(H, W)], layer 0's [H, W] map first. */
+int64_t r2l_lpips_vgg_param_floats(void);
+int64_t r2l_lpips_vgg_pack_floats(void);
+int r2l_lpips_vgg_pack(const float* params_dev, float* wpack_dev, void* stream);
+int64_t r2l_lpips_vgg_work_floats(int K, int H, int W);
+int64_t r2l_lpips_vgg_map_floats(int H, int W);
+int r2l_lpips_vgg(const float* img_a, const float* img_b, int K, int H, int W, const float* rescale_dev, const float* wpack,
+                  float* work, float* per_layer, float* maps, float* out, void* stream);
+
 /* ---- hard-ray pool (training data path) ---------------------------------------------------------------------------------
  * The three data movements of main.py:1325-1347 (n_hard_out random pool rows [o, d, rgb] appended to every batch) and
  * main.py:1410-1425 (the hard rays of the step enter the pool, appended until it is full, then replacing the rows that were

@@ -141,6 +141,12 @@ SIGNATURES = {
     "r2l_lpips_work_floats": (_l, [_i, _i, _i]),
     "r2l_lpips_map_floats": (_l, [_i, _i]),
     "r2l_lpips": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
+    "r2l_lpips_vgg_param_floats": (_l, []),
+    "r2l_lpips_vgg_pack_floats": (_l, []),
+    "r2l_lpips_vgg_pack": (_i, [_p, _p, _p]),
+    "r2l_lpips_vgg_work_floats": (_l, [_i, _i, _i]),
+    "r2l_lpips_vgg_map_floats": (_l, [_i, _i]),
+    "r2l_lpips_vgg": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p, _p, _p, _p]),
     "r2l_pool_pick": (_i, [_p, _l, _l, ctypes.c_uint64, _p]),
     "r2l_pool_augment": (_i, [_p, _p, _p, _l, _l, _l, _p, _p, _l, _l, _p, _p, _p, _p]),
     "r2l_pool_store": (_i, [_p, _p, _p, _l, _l, _l, _p, _p, _p, _l, _l, _p]),

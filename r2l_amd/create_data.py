@@ -108,7 +108,7 @@ def main(argv=None):
     if args.test_teacher:
         # "Testing teacher..." (create_data.py:723-741): the test views through render_path with render_kwargs_test (perturb =
         # --perturb_test, raw_noise_std = 0), Loss / PSNR logged before any data is generated; frames sharded over the ranks
-        from .driver import lpips_field, load_lpips_weights, render_path
+        from .driver import lpips_field, load_lpips_vgg_weights, load_lpips_weights, render_path
         if not args.teacher_ckpt or scene is None:
             raise SystemExit("--test_teacher needs --teacher_ckpt and a scene directory (--datadir) with test views")
         images, poses, i_split = scene.rgb_images(args.white_bkgd), scene.poses, (scene.i_train, scene.i_val, scene.i_test)
@@ -116,7 +116,8 @@ def main(argv=None):
         _, misc = render_path(poses[i_split[2]], coarse, None, device, logger, gt_imgs=images[i_split[2]], rank=rank, world=world,
                               teacher=dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kw_test, render_factor=args.render_factor,
                                            fused=args.r2l_fused_frames),
-                              lpips_params=load_lpips_weights(args, device, logger))
+                              lpips_params=load_lpips_weights(args, device, logger),
+                              lpips_vgg_params=load_lpips_vgg_weights(args, device, logger))
         logger.info("Teacher test: Loss %.4f PSNR %.4f%s" % (misc["test_loss"].item(), misc["test_psnr"].item(), lpips_field(misc)))
 
     datadir_new = args.datadir_kd.split(":")[-1]

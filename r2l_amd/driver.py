@@ -15,7 +15,7 @@ import torch.distributed as dist
 from . import data as D
 from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
-from .metrics import flip, img2mse, lpips, mse2psnr, ssim, to8b
+from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import parse_args, validate_accelerated, validate_fused_iter
 from .dist_utils import split_shards
@@ -472,6 +472,16 @@ def lpips_frames_per_launch(H, W):
     return max(1, min(64, LPIPS_WORK_BYTES // max(per_pair, 1)))
 
 
+LPIPS_VGG_WORK_BYTES = 1 << 30  # the same for r2l_lpips_vgg, whose maps are full resolution (236 MB per 400x400 pair: 4 pairs)
+
+
+def lpips_vgg_frames_per_launch(H, W):
+    """Frame pairs per r2l_lpips_vgg launch, from the size of its work buffer (at least 1, at most 64)."""
+    from . import _lib
+    per_pair = 4 * _lib.load().r2l_lpips_vgg_work_floats(1, H, W)
+    return max(1, min(64, LPIPS_VGG_WORK_BYTES // max(per_pair, 1)))
+
+
 def _stack_extrema(rgbs, gts, device, world):
     """-> the target stack and {min, max} of the rendered and of the target stack over ALL frames of the test set (main.py:361-363
     rescales both to [-1, 1] by them before LPIPS and FLIP).  The extrema stay on the device (one all_reduce(MAX) makes them
@@ -495,14 +505,15 @@ def _flip_sum(rgbs, gts, extrema, device):
     return total
 
 
-def _lpips_sum(rgbs, gts, extrema, params, device):
-    """Sum over this rank's frames of LPIPS(AlexNet) on the same rescaled stacks (main.py:359-369), in launch groups sized by
-    the kernels' work buffer."""
+def _lpips_sum(rgbs, gts, extrema, params, device, vgg=False):
+    """Sum over this rank's frames of LPIPS(AlexNet; vgg: VGG-16) on the same rescaled stacks (main.py:359-369), in launch groups
+    sized by the kernels' work buffer."""
     total = torch.zeros((), dtype=torch.float64, device=device)
     if len(gts):
-        n = lpips_frames_per_launch(*rgbs.shape[1:3]) if device.type == "cuda" else 8  # (the reference's batches of 8)
+        fn, per_launch = (lpips_vgg, lpips_vgg_frames_per_launch) if vgg else (lpips, lpips_frames_per_launch)
+        n = per_launch(*rgbs.shape[1:3]) if device.type == "cuda" else 8  # (the reference's batches of 8)
         for g0 in range(0, len(gts), n):
-            total += lpips(rgbs[g0:g0 + n], gts[g0:g0 + n], params, rescale=extrema).double().sum()
+            total += fn(rgbs[g0:g0 + n], gts[g0:g0 + n], params, rescale=extrema).double().sum()
     return total
 
 
@@ -517,7 +528,7 @@ def _runs(idx):
 
 
 def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, savedir=None, rank=0, world=1, teacher=None,
-                lpips_params=None):
+                lpips_params=None, lpips_vgg_params=None):
     """Render poses[rank::world]; returns (rgbs [n,H,W,3], misc with test_loss/test_psnr/test_psnr_v2 over ALL frames)
     and test_ssim / test_flip — main.py:189-398.  No host
     sync inside the loop: metrics stay on the device, frames are written by _FrameWriter, per-frame times come from device
@@ -526,6 +537,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
     lpips_params = the flat AlexNet + lin weights of metrics.lpips_params (--r2l_lpips_weights: the user's files, none are
     shipped): misc gains test_lpips (main.py:359-369, 392), evaluated behind the loop on the same rescaled stacks (_lpips_sum);
     None: no LPIPS work at all and no such key.
+    lpips_vgg_params = the flat VGG-16 + lin weights of metrics.lpips_vgg_params (--r2l_lpips_vgg_weights): misc gains
+    test_lpips_vgg in the same way (the number the published tables call LPIPS); None: no VGG work and no such key.
     teacher = None: the R2L branch (main.py:284-324), `model` = the student.
     teacher = dict(hwf=(H, W, focal), chunk=, render_kwargs=): the `model_name in ['nerf']` branch (main.py:275-282): every
     frame is render(H, W, focal, chunk, c2w=pose[:3,:4], **render_kwargs) of r2l_amd/render.py (coarse + fine NeRF on the
@@ -626,12 +639,14 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
             logger.info("[#%d] frame, rendering done, time for this frame: %.4fs" % (i, time.time() - t0))
             account(i, rgb)
     rgbs = torch.stack(rgbs, 0) if rgbs else torch.empty(0)
-    flip_sum = lpips_sum = None
+    flip_sum = lpips_sum = lpips_vgg_sum = None
     if gt_imgs is not None:  # (enqueued before the host waits below)
         gts, extrema = _stack_extrema(rgbs, gts, device, world)
         flip_sum = _flip_sum(rgbs, gts, extrema, device)
         if lpips_params is not None:
             lpips_sum = _lpips_sum(rgbs, gts, extrema, lpips_params, device)
+        if lpips_vgg_params is not None:
+            lpips_vgg_sum = _lpips_sum(rgbs, gts, extrema, lpips_vgg_params, device, vgg=True)
     if writer is not None:
         writer.flush()  # (shared writer: threads and pinned slots stay for the next evaluation)
     if on_gpu:
@@ -649,9 +664,10 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
         stats = torch.stack([sums[0].reshape(()), sums[1].reshape(()),
                              torch.tensor(float(len(mine)), dtype=torch.float64, device=device),
                              sums[2].reshape(()), flip_sum.reshape(())] +
-                            ([lpips_sum.reshape(())] if lpips_sum is not None else [])).to(device)
+                            ([lpips_sum.reshape(())] if lpips_sum is not None else []) +
+                            ([lpips_vgg_sum.reshape(())] if lpips_vgg_sum is not None else [])).to(device)
         if world > 1:
-            dist.all_reduce(stats)  # host-side metric gather (5 scalars, 6 with LPIPS), not on the data path
+            dist.all_reduce(stats)  # host-side metric gather (5 scalars, one more per LPIPS variant), not on the data path
         stats = stats.tolist()
         misc["test_loss"] = torch.tensor(stats[0] / max(stats[2], 1))
         misc["test_psnr"] = mse2psnr(misc["test_loss"].float()).squeeze()
@@ -660,6 +676,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
         misc["test_flip"] = torch.tensor(stats[4] / max(stats[2], 1))  # (frames of one size: the mean of per-frame means, main.py:393)
         if lpips_sum is not None:
             misc["test_lpips"] = torch.tensor(stats[5] / max(stats[2], 1))
+        if lpips_vgg_sum is not None:  # (the last entry)
+            misc["test_lpips_vgg"] = torch.tensor(stats[-1] / max(stats[2], 1))
         misc["errors"] = torch.stack(errors, 0) if errors else torch.empty(0)
     model.train()
     return rgbs, misc
@@ -677,9 +695,23 @@ def load_lpips_weights(args, device, logger):
     return params
 
 
+def load_lpips_vgg_weights(args, device, logger):
+    """--r2l_lpips_vgg_weights -> the flat parameter vector on the device (metrics.lpips_vgg_params), or None without the flag."""
+    from .metrics import lpips_vgg_params
+    from .options import validate_lpips
+    validate_lpips(args)
+    if not args.r2l_lpips_vgg_weights:
+        return None
+    params = lpips_vgg_params(args.r2l_lpips_vgg_weights).to(device)
+    logger.info("LPIPS (VGG-16, v0.1) in the test-set loop: %d parameters from %s" % (params.numel(), args.r2l_lpips_vgg_weights))
+    return params
+
+
 def lpips_field(misc):
-    """' TestLPIPS %.4f' for the test-set log lines (main.py:1080, 1468: between TestSSIM and TestFLIP), '' without the flag."""
-    return " TestLPIPS %.4f" % misc["test_lpips"].item() if "test_lpips" in misc else ""
+    """' TestLPIPS %.4f' for the test-set log lines (main.py:1080, 1468: between TestSSIM and TestFLIP), then ' TestLPIPSvgg %.4f';
+    each only with its flag."""
+    return ((" TestLPIPS %.4f" % misc["test_lpips"].item() if "test_lpips" in misc else "") +
+            (" TestLPIPSvgg %.4f" % misc["test_lpips_vgg"].item() if "test_lpips_vgg" in misc else ""))
 
 
 # ---------------------------------------------------------------------------------------------------------------
@@ -706,6 +738,7 @@ def main(argv=None):
     torch.manual_seed(int(os.environ.get("R2L_SEED", "0")))
     logger = Logger(args, rank)
     lpips_w = load_lpips_weights(args, device, logger)  # (read once; None without --r2l_lpips_weights)
+    lpips_vgg_w = load_lpips_vgg_weights(args, device, logger)  # (None without --r2l_lpips_vgg_weights)
 
     scene = D.load_scene(args)
     images, poses, hwf = scene.images, scene.poses, scene.hwf
@@ -741,7 +774,7 @@ def main(argv=None):
 
     if args.test_pretrained:
         _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images, rank=rank,
-                              world=world, teacher=teacher, lpips_params=lpips_w)
+                              world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
         logger.info("Pretrained test: TestLoss %.4f TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
                     (misc["test_loss"].item(), misc["test_psnr"].item(), misc["test_psnr_v2"].item(),
                      misc["test_ssim"].item(), lpips_field(misc), misc["test_flip"].item()))
@@ -753,7 +786,7 @@ def main(argv=None):
         if args.render_test:
             rgbs, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
                                      savedir=logger.gen_img_path if rank == 0 or world > 1 else None, rank=rank,
-                                     world=world, teacher=teacher, lpips_params=lpips_w)
+                                     world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
             logger.info("[TEST] TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
                         (misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), lpips_field(misc),
                          misc["test_flip"].item()))
@@ -943,7 +976,7 @@ def main(argv=None):
             os.makedirs(savedir, exist_ok=True)
             t_ = time.time()
             _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
-                                  savedir=savedir, rank=rank, world=world, lpips_params=lpips_w)
+                                  savedir=savedir, rank=rank, world=world, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
             if misc["test_psnr_v2"] > best_psnr:
                 best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
                 if rank == 0:

@@ -379,3 +379,192 @@ def lpips(img, ref, params, rescale=None, normalize=False, return_layers=False, 
     if return_maps:
         res.append([m[0] for m in maps] if single else maps)
     return res[0] if len(res) == 1 else tuple(res)
+
+
+# ---- LPIPS, the VGG-16 variant (lpips.LPIPS(net='vgg', version='0.1') in eval mode: the published NeRF / R2L tables) --------------
+# (in, out) of the thirteen 3 x 3 / 1 / 1 convolutions; a 2 / 2 max-pool (floor) sits in front of 2, 4, 7 and 10; the taps are the
+# post-ReLU outputs of 1, 3, 6, 9 and 12 (conv1_2, conv2_2, conv3_3, conv4_3, conv5_3)
+LPIPS_VGG_CONVS = ((3, 64), (64, 64), (64, 128), (128, 128), (128, 256), (256, 256), (256, 256), (256, 512), (512, 512), (512, 512),
+                   (512, 512), (512, 512), (512, 512))
+LPIPS_VGG_TAPS = (1, 3, 6, 9, 12)
+_LPIPS_VGG_POOLS = (2, 4, 7, 10)
+LPIPS_VGG_PARAM_FLOATS = (sum(9 * ci * co + co for ci, co in LPIPS_VGG_CONVS) +
+                          sum(LPIPS_VGG_CONVS[t][1] for t in LPIPS_VGG_TAPS))  # 14 716 160
+_LPIPS_VGG_FEATURES = (0, 2, 5, 7, 10, 12, 14, 17, 19, 21, 24, 26, 28)  # torchvision's vgg16.features indices of the convolutions
+_LPIPS_VGG_SLICE = (1, 1, 2, 2, 3, 3, 3, 4, 4, 4, 5, 5, 5)              # the lpips package's slice of each
+
+
+def lpips_vgg_sizes(H, W):
+    """[(Ho, Wo)] of the five feature maps of an H x W image (400 -> 400, 200, 100, 50, 25; 16 -> 16, 8, 4, 2, 1)."""
+    return [(H >> s, W >> s) for s in range(5)]
+
+
+def lpips_vgg_flatten(convs, lins):
+    """[(weight [Co,Ci,3,3], bias [Co])] x 13 and five lin weights -> the flat fp32 vector of r2l_lpips_vgg_pack."""
+    flat = torch.cat([t.detach().float().reshape(-1) for wb in convs for t in wb] + [t.detach().float().reshape(-1) for t in lins])
+    assert flat.numel() == LPIPS_VGG_PARAM_FLOATS
+    return flat.contiguous()
+
+
+def lpips_vgg_unflatten(params):
+    """The flat vector -> ([(weight, bias)] x 13, [lin] x 5) as views."""
+    assert params.numel() == LPIPS_VGG_PARAM_FLOATS, "LPIPS (VGG) parameters: %d floats, expected %d" % (
+        params.numel(), LPIPS_VGG_PARAM_FLOATS)
+    convs, lins, o = [], [], 0
+    for ci, co in LPIPS_VGG_CONVS:
+        n = co * ci * 9
+        convs.append((params[o:o + n].view(co, ci, 3, 3), params[o + n:o + n + co]))
+        o += n + co
+    for t in LPIPS_VGG_TAPS:
+        co = LPIPS_VGG_CONVS[t][1]
+        lins.append(params[o:o + co])
+        o += co
+    return convs, lins
+
+
+def lpips_vgg_params(path):
+    """The flat fp32 parameter vector (for l = 0..12 { conv weight, bias }, then lin_0 .. lin_4) from the user's files: one file, or
+    two joined by ':' whose keys are merged.  Understood: torchvision's VGG-16 checkpoint
+    (features.{0,2,5,7,10,12,14,17,19,21,24,26,28}.{weight,bias}) beside the lpips package's vgg.pth (lin{0..4}.model.1.weight,
+    shape (1, C, 1, 1)), and a saved lpips.LPIPS(net='vgg').state_dict() (net.slice1.{0,2}, net.slice2.{5,7}, net.slice3.{10,12,14},
+    net.slice4.{17,19,21}, net.slice5.{24,26,28} + the same lin keys).  Extra keys (torchvision's classifier.*) are ignored; a
+    missing key or a wrong shape is a ValueError that names the key."""
+    sd = {}
+    for part in str(path).split(":"):
+        if not part:
+            continue
+        obj = torch.load(part, map_location="cpu", weights_only=True)
+        if not isinstance(obj, dict):
+            raise ValueError("%s: expected a state dict, got %s" % (part, type(obj).__name__))
+        sd.update(obj)
+    convs, lins = [], []
+    for l, (ci, co) in enumerate(LPIPS_VGG_CONVS):
+        pair = []
+        for leaf, shape in (("weight", (co, ci, 3, 3)), ("bias", (co,))):
+            names = ("features.%d.%s" % (_LPIPS_VGG_FEATURES[l], leaf),
+                     "net.slice%d.%d.%s" % (_LPIPS_VGG_SLICE[l], _LPIPS_VGG_FEATURES[l], leaf))
+            key = next((n for n in names if n in sd), None)
+            if key is None:
+                raise ValueError("LPIPS (VGG) weights %s: missing key %s (or %s)" % (path, names[0], names[1]))
+            if tuple(sd[key].shape) != shape:
+                raise ValueError("LPIPS (VGG) weights %s: key %s has shape %s, expected %s" % (path, key, tuple(sd[key].shape), shape))
+            pair.append(sd[key])
+        convs.append(pair)
+    for l, t in enumerate(LPIPS_VGG_TAPS):
+        key, co = "lin%d.model.1.weight" % l, LPIPS_VGG_CONVS[t][1]
+        if key not in sd:
+            raise ValueError("LPIPS (VGG) weights %s: missing key %s" % (path, key))
+        if tuple(sd[key].shape) != (1, co, 1, 1):
+            raise ValueError("LPIPS (VGG) weights %s: key %s has shape %s, expected %s" % (path, key, tuple(sd[key].shape), (1, co, 1, 1)))
+        lins.append(sd[key])
+    return lpips_vgg_flatten(convs, lins)
+
+
+def _lpips_vgg_features(x, convs, shift=True, ceil_mode=False, pre_relu=False):
+    """The five feature maps [K,C,Ho,Wo] of a [K,H,W,3] stack, op by op.  The keywords exist for the tests: anything but the
+    defaults is a deliberately wrong evaluation (no shift; ceil-mode pools; the tap taken in front of its ReLU) that the bars must
+    be able to see."""
+    import torch.nn.functional as F
+    t = dict(dtype=x.dtype, device=x.device)
+    # (the scaling layer's constants are fp32 numbers, as in _lpips_features)
+    sh = torch.tensor(LPIPS_SHIFT if shift else (0., 0., 0.), dtype=torch.float32).to(**t).view(1, 3, 1, 1)
+    sc = torch.tensor(LPIPS_SCALE, dtype=torch.float32).to(**t).view(1, 3, 1, 1)
+    x = (x.permute(0, 3, 1, 2) - sh) / sc
+    feats = []
+    for l, (w, b) in enumerate(convs):
+        if l in _LPIPS_VGG_POOLS:
+            x = F.max_pool2d(x, 2, 2, ceil_mode=ceil_mode)
+        y = F.conv2d(x, w.to(**t), b.to(**t), padding=1)
+        x = F.relu(y)
+        if l in LPIPS_VGG_TAPS:
+            feats.append(y if pre_relu else x)
+    return feats
+
+
+def _lpips_vgg_torch(a, b, params, **wrong):
+    """-> per-layer means [K,5] and the five maps [K,Ho,Wo] of two [K,H,W,3] stacks, in their dtype and on their device."""
+    convs, lins = lpips_vgg_unflatten(params)
+    fa, fb = _lpips_vgg_features(a, convs, **wrong), _lpips_vgg_features(b, convs, **wrong)
+    maps = []
+    for l in range(5):
+        na = fa[l] / (fa[l].pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+        nb = fb[l] / (fb[l].pow(2).sum(1, keepdim=True).sqrt() + 1e-10)
+        maps.append(((na - nb).pow(2) * lins[l].to(dtype=a.dtype, device=a.device).view(1, -1, 1, 1)).sum(1))
+    return torch.stack([m.mean((1, 2)) for m in maps], 1), maps
+
+
+_LPIPS_VGG_PACKED = {}  # as _LPIPS_PACKED
+
+
+def _lpips_vgg_stream(L, params, device):
+    key = (str(device), params.data_ptr(), params._version)
+    hit = _LPIPS_VGG_PACKED.get(key)
+    if hit is not None and hit[0] is params:
+        return hit[1]
+    assert params.numel() == L.r2l_lpips_vgg_param_floats(), "LPIPS (VGG) parameters: %d floats, expected %d" % (
+        params.numel(), L.r2l_lpips_vgg_param_floats())
+    flat = params.detach().to(device).float().contiguous()
+    wpack = torch.empty(L.r2l_lpips_vgg_pack_floats(), device=device)
+    from . import _lib
+    _lib.check(L.r2l_lpips_vgg_pack(flat.data_ptr(), wpack.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+               "r2l_lpips_vgg_pack")
+    while len(_LPIPS_VGG_PACKED) >= 4:
+        _LPIPS_VGG_PACKED.pop(next(iter(_LPIPS_VGG_PACKED)))
+    _LPIPS_VGG_PACKED[key] = (params, wpack)
+    return wpack
+
+
+def lpips_vgg(img, ref, params, rescale=None, normalize=False, return_layers=False, return_maps=False):
+    """LPIPS (VGG-16, v0.1) of [H,W,3] or [K,H,W,3] images with values in [-1, 1]; H, W >= 16.  params: the flat vector of
+    lpips_vgg_params.  normalize, rescale, the CUDA / CPU branches and the return values: as lpips (the kernels are r2l_lpips_vgg;
+    the five maps have the sizes of lpips_vgg_sizes)."""
+    assert img.shape == ref.shape and img.dim() in (3, 4) and img.shape[-1] == 3
+    single = img.dim() == 3
+    H, W = img.shape[-3:-1]
+    if H < 16 or W < 16:
+        raise ValueError("LPIPS (VGG) needs images of at least 16 x 16 pixels (got %d x %d): the deepest feature map would be empty"
+                         % (H, W))
+    if img.is_cuda:
+        from . import _lib
+        L = _lib.load()
+        a, b = img.detach().float().contiguous(), ref.detach().to(img.device).float().contiguous()
+        if normalize:
+            a, b = 2 * a - 1, 2 * b - 1
+        K = 1 if single else a.shape[0]
+        wpack = _lpips_vgg_stream(L, params, a.device)
+        nwork = L.r2l_lpips_vgg_work_floats(K, H, W)
+        if nwork < 0:
+            raise ValueError("LPIPS (VGG): %d pairs of %d x %d exceed one launch" % (K, H, W))
+        work = torch.empty(nwork, device=a.device)
+        out = torch.empty(K, device=a.device)
+        layers = torch.empty((K, 5), device=a.device) if return_layers else None
+        flat = torch.empty((K, L.r2l_lpips_vgg_map_floats(H, W)), device=a.device) if return_maps else None
+        ext = rescale.detach().to(a.device).float().contiguous() if rescale is not None else None
+        assert ext is None or ext.numel() == 4
+        _lib.check(L.r2l_lpips_vgg(a.data_ptr(), b.data_ptr(), K, H, W, ext.data_ptr() if ext is not None else None,
+                                   wpack.data_ptr(), work.data_ptr(), layers.data_ptr() if return_layers else None,
+                                   flat.data_ptr() if return_maps else None, out.data_ptr(),
+                                   ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_lpips_vgg")
+        maps, o = [], 0
+        for ho, wo in (lpips_vgg_sizes(H, W) if return_maps else ()):
+            maps.append(flat[:, o:o + ho * wo].view(K, ho, wo))
+            o += ho * wo
+    else:
+        a, b = (img[None], ref[None]) if single else (img, ref)
+        a, b = (a, b.to(a.dtype)) if a.dtype == torch.float64 else (a.float(), b.float())
+        if normalize:
+            a, b = 2 * a - 1, 2 * b - 1
+        if rescale is not None:
+            e = rescale.to(a.dtype)
+            assert e.numel() == 4
+            a, b = 2 / (e[1] - e[0]) * (a - e[0]) - 1, 2 / (e[3] - e[2]) * (b - e[2]) - 1
+        layers, maps = _lpips_vgg_torch(a, b, params.detach().to(a.dtype))
+        out = layers[:, 0]
+        for l in range(1, 5):
+            out = out + layers[:, l]
+    res = [out[0] if single else out]
+    if return_layers:
+        res.append(layers[0] if single else layers)
+    if return_maps:
+        res.append([m[0] for m in maps] if single else maps)
+    return res[0] if len(res) == 1 else tuple(res)

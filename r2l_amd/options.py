@@ -85,6 +85,10 @@ FLAGS = {
     # AlexNet checkpoint and the lpips package's alex.pth, or a saved lpips.LPIPS().state_dict(): metrics.lpips_params).  None are
     # shipped; '' = no LPIPS, every log line as it always was
     "r2l_lpips_weights": (str, ""),
+    # LPIPS(VGG-16, v0.1) in the test-set loop (r2l_lpips_vgg), a switch of its own beside the one above (both may be given; --lpips_net
+    # plays no part in it): one path or two joined by ':' (torchvision's VGG-16 checkpoint and the lpips package's vgg.pth, or a
+    # saved lpips.LPIPS(net='vgg').state_dict(): metrics.lpips_vgg_params).  None are shipped; '' = no VGG work at all
+    "r2l_lpips_vgg_weights": (str, ""),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),
@@ -183,13 +187,16 @@ def parse_args(argv=None):
 
 
 def validate_lpips(args):
-    """--r2l_lpips_weights: only the AlexNet variant exists here, and the files must be there at start-up, not at the first
-    evaluation hours into a run."""
+    """--r2l_lpips_weights is the AlexNet variant only, --r2l_lpips_vgg_weights the VGG-16 one whatever --lpips_net says; the files
+    must be there at start-up, not at the first evaluation hours into a run."""
+    for part in (args.r2l_lpips_vgg_weights.split(":") if args.r2l_lpips_vgg_weights else ()):
+        if not os.path.isfile(part):
+            raise FileNotFoundError("--r2l_lpips_vgg_weights: no such file: %r" % part)
     if not args.r2l_lpips_weights:
         return
     if args.lpips_net != "alex":
         raise NotImplementedError("--r2l_lpips_weights evaluates LPIPS with the AlexNet features only (--lpips_net alex), got "
-                                  "--lpips_net %s" % args.lpips_net)
+                                  "--lpips_net %s; the VGG-16 variant has its own switch, --r2l_lpips_vgg_weights" % args.lpips_net)
     for part in args.r2l_lpips_weights.split(":"):
         if not os.path.isfile(part):
             raise FileNotFoundError("--r2l_lpips_weights: no such file: %r" % part)

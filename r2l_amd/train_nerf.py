@@ -27,7 +27,7 @@ import torch
 
 from . import data as D
 from .checkpoint import load_ckpt, save_ckpt
-from .driver import lpips_field, apply_arithmetic, create_nerf_teacher, init_distributed, load_lpips_weights, render_path
+from .driver import lpips_field, apply_arithmetic, create_nerf_teacher, init_distributed, load_lpips_vgg_weights, load_lpips_weights, render_path
 from .logger import Logger
 from .options import parse_args, validate_accelerated
 from .pixel_batch import PixelBatcher
@@ -113,6 +113,7 @@ def main(argv=None):
     _seed(0)
     logger = Logger(args, rank)
     lpips_w = load_lpips_weights(args, device, logger)  # (read once; None without --r2l_lpips_weights)
+    lpips_vgg_w = load_lpips_vgg_weights(args, device, logger)  # (None without --r2l_lpips_vgg_weights)
     scene = D.load_scene(args)
     images, poses, hwf = scene.images, scene.poses, scene.hwf
     logger.info("Loaded %s" % scene.kind, tuple(images.shape), tuple(poses.shape), hwf, args.datadir)
@@ -195,7 +196,7 @@ def main(argv=None):
         if i % args.i_testset == 0 and len(i_test):
             savedir = os.path.join(logger.gen_img_path, "testset_%s_iter%d" % (logger.ExpID, i))
             _, misc = render_path(test_poses, coarse, None, device, logger, gt_imgs=test_images, savedir=savedir,
-                                  teacher=teacher, lpips_params=lpips_w)
+                                  teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
             for net in (coarse, fine):
                 if net is not None:
                     net.train()
