@@ -541,6 +541,56 @@ int r2l_store_append(const float* rows_in, int64_t n_rows, float* store, int64_t
 int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
                     float* batch, int32_t* ids_out, void* stream);
 
+/* ---- compact ray store (16 bytes a ray; o and d recomputed per draw) ------------------------------------------------------------
+ * A store that the TEACHER fills is redundant at 36 bytes a ray: every row of a flush group comes from r2l_teacher_frames_cfg,
+ * so its o, d are a pure function of the pose's c2w, the pose's focal and the pixel — the arithmetic pinned under r2l_frame_rays
+ * above (pixel_ray of csrc/r2l_pixel_ray.h, the one definition behind both).  Only rgb is information.  The compact store keeps
+ * { rgb, id } per ray, 13 floats per pose and one int per shard, and r2l_cstore_batch hands out the [o, d, rgb] rows that
+ * r2l_store_batch would have handed out from a plain store filled with the same groups and keys, BIT FOR BIT.
+ *
+ * The store is CALLER-OWNED memory described by one struct (72 bytes, no padding):
+ *   rows         capacity_shards * rays_per_shard rows of 16 bytes { float rgb[3]; uint32_t id; }, 16-byte aligned; shard s is
+ *                rows [s * rays_per_shard, (s+1) * rays_per_shard)
+ *   pose_c2w     [capacity_poses][3][4], pose_focal [capacity_poses]: the pose table
+ *   shard_pose0  [capacity_shards]: pose-table index of pose 0 of the flush group that wrote the shard
+ * id is the row number inside its flush group, (k*H + row)*W + col with k the pose within the group: the ray index of
+ * r2l_frame_rays / r2l_teacher_frames_cfg.  ids are unsigned 32-bit: a group of K*H*W > 2^32 - 1 rays is refused.
+ * Both calls are stateless, check their arguments before any launch (hipErrorInvalidValue, r2l_last_error names the argument),
+ * enqueue one kernel on `stream` and never synchronise.  r2l_amd/raystore.py (cstore_append_spec, cstore_batch_spec) restates
+ * them in numpy. */
+typedef struct r2l_cstore {
+    void*    rows;
+    float*   pose_c2w;
+    float*   pose_focal;
+    int32_t* shard_pose0;
+    int64_t  capacity_shards, capacity_poses;   /* each < 2^31 */
+    int64_t  rays_per_shard;                    /* positive multiple of 4 */
+    int      H, W;                              /* the frames' size: one per store; H*W <= 2^32 - 1 */
+    int      reserved[2];                       /* must be 0 */
+} r2l_cstore;
+
+/*   r2l_cstore_append: one flush group of K whole frames.  With n_rows = K*H*W and m = floor(n_rows / rays_per_shard), output row
+ *     i < m * rays_per_shard of shards first_shard .. first_shard + m - 1 is { rgb[pi(key, n_rows)(i)], id = pi(key, n_rows)(i) }
+ *     — pi as specified for r2l_store_append above, the tail of the permuted sequence dropped as there; shuffle = 0: the identity.
+ *     rgb: device fp32, row r at rgb + r * rgb_stride (3 for the rgb output of r2l_teacher_frames_cfg, 9 for rows + 6).
+ *     The K poses c2w_dev[K][3][4] and focals (focal_dev[K], or NULL: the scalar focal K times) are copied to the pose table at
+ *     first_pose, shard_pose0[first_shard .. first_shard + m) = first_pose, *n_written_out = m (host arithmetic).  m == 0 enqueues
+ *     nothing (no shard refers to the poses).  Refused: a NULL pointer (store, its four pointers, rgb, c2w_dev, n_written_out),
+ *     K < 1, H or W < 1, K*H*W > 2^32 - 1, first_shard + m > capacity_shards, first_pose + K > capacity_poses, rays_per_shard not a
+ *     positive multiple of 4, rgb_stride < 3, focal <= 0 with a NULL focal_dev, non-zero reserved, rows not 16-byte aligned.
+ *   r2l_cstore_batch: draw t = draw0 + j, j < n_draw, takes the shard r2l_store_batch takes (the same sampler: a pure function
+ *     of (seed, n_shards, t)); row x of that shard becomes row j * rays_per_shard + x of batch [n_draw * rays_per_shard, 9]:
+ *       p = shard_pose0[shard] + id / (H*W);   row = (id % (H*W)) / W;   col = id % W
+ *       [o, d] = the ray of pixel (row, col) with pose_c2w[p] and pose_focal[p], in the arithmetic of r2l_frame_rays;  rgb copied.
+ *     A row whose p lies outside the pose table (a store nobody appended to) gets NaN rays; nothing outside the table is read.
+ *     ids_out: device int32[n_draw] receiving the shard ids, or NULL.  batch must be 16-byte aligned; 1 <= n_shards <=
+ *     capacity_shards; the other conditions are those of r2l_store_batch and of the struct.  16 bytes read and 36 written per ray. */
+int r2l_cstore_append(const r2l_cstore* store, const float* rgb, int64_t rgb_stride, const float* c2w_dev, const float* focal_dev,
+                      float focal, int K, int64_t first_shard, int64_t first_pose, uint64_t key, int shuffle,
+                      int64_t* n_written_out, void* stream);
+int r2l_cstore_batch(const r2l_cstore* store, int64_t n_shards, int64_t draw0, int64_t n_draw, uint64_t seed,
+                     float* batch /*[n_draw * rays_per_shard, 9]*/, int32_t* ids_out, void* stream);
+
 /* r2l_train_batch: the batch of a student step in ONE launch instead of r2l_store_batch -> r2l_pool_pick -> r2l_pool_augment
  * (csrc/r2l_student_step.hip).  With B = n_draw * rays_per_shard, out_o / out_d / out_t are [B + n_out, 3] contiguous:
  *   rows [0, B):          the rows of the shards id(draw0 + j), j < n_draw — id exactly as specified for r2l_store_batch above —

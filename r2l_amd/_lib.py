@@ -60,6 +60,15 @@ class StudentStepDesc(ctypes.Structure):
 _sstepp = ctypes.POINTER(StudentStepDesc)
 
 
+class CompactStoreDesc(ctypes.Structure):
+    """r2l_cstore of include/r2l_hip.h (r2l_cstore_append / r2l_cstore_batch): 72 bytes, no padding."""
+    _fields_ = [("rows", _p), ("pose_c2w", _p), ("pose_focal", _p), ("shard_pose0", _p), ("capacity_shards", _l),
+                ("capacity_poses", _l), ("rays_per_shard", _l), ("H", _i), ("W", _i), ("reserved", _i * 2)]
+
+
+_cstorep = ctypes.POINTER(CompactStoreDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -154,6 +163,8 @@ SIGNATURES = {
     "r2l_pool_select": (_i, [_p, _p, _l, _l, _l, _l, _p, _p, _p, _p]),
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
+    "r2l_cstore_append": (_i, [_cstorep, _p, _l, _p, _p, _f, _i, _l, _l, ctypes.c_uint64, _i, _p, _p]),
+    "r2l_cstore_batch": (_i, [_cstorep, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
     "r2l_train_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
     "r2l_student_step_work_floats": (_l, [_sstepp]),
     "r2l_student_train_step": (_i, [_sstepp] + [_p] * 13),

@@ -15,6 +15,7 @@
 // The kernels here move 12 - 72 bytes per ray: a thread per ray (per Philox block of four draws), no LDS.
 #include "r2l_dispatch.h"
 #include "r2l_perm.h"
+#include "r2l_pixel_ray.h"
 #include <math.h>
 
 namespace {
@@ -89,17 +90,8 @@ __device__ __forceinline__ void ndc_one(const float (&o)[3], const float (&d)[3]
     d2[0] = cw * (dx - qx); d2[1] = ch * (dy - qy); d2[2] = (-2.f * near) / sz;
 }
 
-// World ray of pixel (row, col) of an H x W frame with pose c ([3][4]) and focal f: separately rounded fp32 in the order of
-// include/r2l_hip.h (the build passes -ffp-contract=off).  The one definition behind r2l_frame_rays and r2l_pixel_batch.
-__device__ __forceinline__ void pixel_ray(const float* __restrict__ c, float f, int H, int W, int row, int col, float (&o)[3],
-                                          float (&d)[3]) {
-    const float dx = ((float)col - (float)W * .5f) / f, dy = -(((float)row - (float)H * .5f) / f), dz = -1.f;
-#pragma unroll
-    for (int i = 0; i < 3; ++i) {
-        d[i] = (dx * c[i * 4 + 0] + dy * c[i * 4 + 1]) + dz * c[i * 4 + 2];
-        o[i] = c[i * 4 + 3];
-    }
-}
+// pixel_ray (csrc/r2l_pixel_ray.h): the world ray of a pixel, the one definition behind r2l_frame_rays and r2l_pixel_batch —
+// and behind r2l_cstore_batch, which recomputes these very rays.
 
 // (x^2 + z^2) + y^2: the association of torch.norm's reduction over a 3-vector, so that render()'s own normalisation of
 // these rays_d gives these bits (tests/test_teacher_frames_gpu.py: fused = unfused)

@@ -17,7 +17,7 @@ from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
-from .options import parse_args, validate_accelerated, validate_fused_iter
+from .options import parse_args, validate_accelerated, validate_compact_store, validate_fused_iter
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -719,6 +719,7 @@ def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
     validate_fused_iter(args)
+    validate_compact_store(args)
     is_teacher = args.model_name == "nerf"
     if is_teacher and (not args.render_only or args.benchmark):
         # (--benchmark times render_func = the R2L student's forward, main.py:401-404,1124-1133)
@@ -851,7 +852,14 @@ def main(argv=None):
         cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
         if cap < 1:
             raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
-        loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
+        if args.r2l_compact_store:
+            # 16 bytes a ray: rgb and the ray's number in its flush group; o, d are recomputed per draw from the group's poses
+            # (one pose-table slot per pose of this rank) and the batches are the plain store's bit for bit
+            from .online_kd import rank_poses
+            from .raystore import CompactRayStore
+            loader = CompactRayStore(cap, len(rank_poses(n_pose, rank, world)), H, W, device, seed=9973 * rank, logger=logger)
+        else:
+            loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
         filler = TeacherFill(loader, targs, H, W, float(hwf[2]), near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
                              rand_pose=scene.rand_pose, ndc=scene.ndc)
         # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose

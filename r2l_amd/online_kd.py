@@ -87,14 +87,17 @@ class TeacherFill:
         focals = torch.tensor([g[2] for g in group], dtype=torch.float32, device=self.device)
         e = [torch.cuda.Event(enable_timing=True) for _ in range(3)]
         e[0].record()
+        # a compact store (raystore.CompactRayStore) takes rgb and the poses: the 24 bytes of o, d per ray are never written
+        compact = hasattr(self.store, "append_frames")
         with torch.no_grad():
             parts = [render_frames(c2ws[s:s + n], self.H, self.W, focals[s:s + n], self.near, self.far, self.coarse, self.fine,
                                    a.N_samples, a.N_importance, a.perturb, a.white_bkgd, seed=1000003 * self.rank,
-                                   frame_id0=ids[s], rows=True, ndc=self.ndc, ndc_focal=self.focal)["rows"] for s, n in _runs(ids)]
+                                   frame_id0=ids[s], rows=not compact, ndc=self.ndc,
+                                   ndc_focal=self.focal)["rgb" if compact else "rows"] for s, n in _runs(ids)]
         rows = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         key = int(self.rng.randint(0, 2**31 - 1))  # the flush seed: drawn where create_data.main's flush() draws it
         e[1].record()
-        m = self.store.append(rows, key, shuffle=True)
+        m = self.store.append_frames(rows, c2ws, focals, key, shuffle=True) if compact else self.store.append(rows, key, shuffle=True)
         e[2].record()
         self.append_ms.append(e)
         self.at += len(group)

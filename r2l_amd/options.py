@@ -60,6 +60,11 @@ FLAGS = {
     # before iteration 1 (r2l_kd_every 0) or one flush group of --create_data_chunk poses every r2l_kd_every iterations
     "r2l_device_store": ("flag", False), "r2l_online_kd": ("flag", False), "r2l_teacher_config": (str, ""),
     "r2l_kd_every": (int, 0),
+    # r2l_compact_store (with r2l_online_kd): the store keeps 16 bytes a ray — rgb and the ray's number in its flush group — and
+    # recomputes o, d per draw from the group's poses (raystore.CompactRayStore, r2l_cstore_append / r2l_cstore_batch): the same
+    # batches bit for bit in 4/9 of the memory.  Not with r2l_device_store (rows from files carry arbitrary rays) or
+    # r2l_fused_iter (the one-call iteration reads 36-byte rows).  utils/create_data.py / utils/train_nerf.py ignore it
+    "r2l_compact_store": ("flag", False),
     # forward-facing LLFF scenes (--dataset_type llff: --factor, --llffhold, --no_ndc; NDC rays through r2l_ndc_rays); opt-in —
     # without the switch --dataset_type llff is refused as it always was.  configs/fern.txt and its kin carry it
     "r2l_llff": ("flag", False),
@@ -233,6 +238,21 @@ def validate_ray_store(args):
         raise ValueError("--r2l_kd_every needs --r2l_online_kd")
     if args.r2l_device_store and (args.data_mode != "rays" or not args.datadir_kd):
         raise ValueError("--r2l_device_store needs --data_mode rays and --datadir_kd")
+
+
+def validate_compact_store(args):
+    """--r2l_compact_store (main.py only; the sibling entry points accept and ignore it): the 16-bytes-a-ray store recomputes the
+    rays of teacher frames, so it needs the teacher fill and excludes what reads other rows.  Names the other flag."""
+    if not args.r2l_compact_store:
+        return
+    if args.r2l_device_store:
+        raise ValueError("--r2l_compact_store recomputes the rays of teacher frames: not with --r2l_device_store, whose rows "
+                         "come from files and carry arbitrary rays")
+    if args.r2l_fused_iter:
+        raise ValueError("--r2l_compact_store hands out batches through its own kernel: not with --r2l_fused_iter, which reads "
+                         "the 36-byte rows of the plain store")
+    if not args.r2l_online_kd:
+        raise ValueError("--r2l_compact_store needs --r2l_online_kd (the teacher fills the store)")
 
 
 def validate_fused_iter(args, world=1, device_type="cuda"):

@@ -7,6 +7,10 @@ pool's row choice uses) and the sampler built on it; they are the specification 
 Sampler: draw t takes shard  perm(epoch_key(seed, t // n_shards), n_shards)[t % n_shards]  — a fresh permutation of the shards
 per epoch, without replacement inside an epoch (the InfiniteSampler of main.py:759-767), a pure function of (seed, n_shards, t).
 A store that grows while it is trained from (driver --r2l_kd_every) is sampled with the shard count of the moment.
+
+CompactRayStore (driver --r2l_compact_store) is the 16-bytes-a-ray form of a store the teacher fills: a row keeps rgb and the
+ray's number in its flush group, o and d are recomputed per draw (r2l_cstore_append / r2l_cstore_batch); cstore_append_spec,
+cstore_batch_spec and pixel_ray_spec restate it, and its batches are RayStore's bit for bit.
 """
 import ctypes
 import time
@@ -106,6 +110,52 @@ def train_batch_spec(store, n_shards, rays_per_shard, draw0, n_draw, seed, pool=
     rows = np.concatenate(rows, 0) if rows else np.empty((0, 9), dtype=np.float32)
     o, d, t = (np.ascontiguousarray(rows[:, c:c + 3]) for c in (0, 3, 6))
     return o, d, t, ids.astype(np.int32), idx
+
+
+def pixel_ray_spec(c2w, focal, H, W, row, col):
+    """pixel_ray of csrc/r2l_pixel_ray.h on n pixels, every operation separately rounded in np.float32: c2w [n, 3, 4], focal [n],
+    row / col integer arrays [n] -> (o [n, 3], d [n, 3]).  The arithmetic include/r2l_hip.h pins under r2l_frame_rays."""
+    f32 = np.float32
+    c = np.asarray(c2w, dtype=f32).reshape(-1, 3, 4)
+    f = np.asarray(focal, dtype=f32).reshape(-1)
+    dx = (np.asarray(col).astype(f32) - f32(W) * f32(.5)) / f
+    dy = -((np.asarray(row).astype(f32) - f32(H) * f32(.5)) / f)
+    d = np.empty((c.shape[0], 3), dtype=f32)
+    for i in range(3):
+        d[:, i] = (dx * c[:, i, 0] + dy * c[:, i, 1]) + f32(-1.) * c[:, i, 2]
+    return np.ascontiguousarray(c[:, :, 3]), d
+
+
+def cstore_append_spec(rgb, rays_per_shard, key, shuffle=True):
+    """What r2l_cstore_append writes into its new shards, in numpy: rgb [n_rows, 3] (n_rows = K*H*W of a flush group) ->
+    (rgb_rows float32[m * rays_per_shard, 3], ids uint32[m * rays_per_shard]) with m = n_rows // rays_per_shard: row i holds
+    rgb[perm(key, n_rows)[i]] and that index; the tail of the permuted sequence is dropped.  shuffle=False: the identity."""
+    rgb = np.asarray(rgb, dtype=np.float32).reshape(-1, 3)
+    n_rows = rgb.shape[0]
+    if n_rows > 2**32 - 1:
+        raise ValueError("cstore_append_spec: %d rows, a row's id is 32 bits" % n_rows)
+    n_out = n_rows // int(rays_per_shard) * int(rays_per_shard)
+    src = perm_at(key, n_rows, np.arange(n_out, dtype=np.uint64)) if shuffle else np.arange(n_out, dtype=np.int64)
+    return np.ascontiguousarray(rgb[src]), src.astype(np.uint32)
+
+
+def cstore_batch_spec(rgb_rows, ids, pose_c2w, pose_focal, shard_pose0, H, W, n_shards, rays_per_shard, draw0, n_draw, seed):
+    """What r2l_cstore_batch writes, in numpy: (batch float32[n_draw * rays_per_shard, 9], shard ids int32[n_draw]).  rgb_rows
+    [>= n_shards * rays_per_shard, 3] and ids (uint32, same length) are the store's rows, pose_c2w [n_pose, 3, 4] / pose_focal
+    [n_pose] its pose table, shard_pose0 [>= n_shards] the pose-table index of each shard's flush group.  Row = [o, d, rgb] with
+    (o, d) = pixel_ray_spec of pose shard_pose0[shard] + id // (H*W) at pixel ((id % (H*W)) // W, id % W)."""
+    rps, hw = int(rays_per_shard), int(H) * int(W)
+    rgb_rows = np.asarray(rgb_rows, dtype=np.float32).reshape(-1, 3)
+    ids = np.asarray(ids).astype(np.uint64).reshape(-1)
+    sh = shard_ids(seed, n_shards, draw0, n_draw)
+    at = (sh[:, None] * rps + np.arange(rps, dtype=np.int64)[None, :]).reshape(-1)
+    rid = ids[at]
+    p = np.repeat(np.asarray(shard_pose0, dtype=np.int64)[sh], rps) + (rid // np.uint64(hw)).astype(np.int64)
+    pix = rid % np.uint64(hw)
+    row, col = (pix // np.uint64(W)).astype(np.int64), (pix % np.uint64(W)).astype(np.int64)
+    o, d = pixel_ray_spec(np.asarray(pose_c2w, dtype=np.float32).reshape(-1, 3, 4)[p],
+                          np.asarray(pose_focal, dtype=np.float32).reshape(-1)[p], H, W, row, col)
+    return np.concatenate([o, d, rgb_rows[at]], 1), sh.astype(np.int32)
 
 
 def _p(t):
@@ -273,4 +323,143 @@ class RayStore:
 
     def close(self):
         self.data = None
+        self._buf, self._ids, self.last_ids = [None, None], [None, None], None
+
+
+class CompactRayStore:
+    """A ray store the TEACHER fills, at 16 bytes a ray instead of 36 (include/r2l_hip.h r2l_cstore_append / r2l_cstore_batch): a
+    row keeps { rgb, id } — id = the ray's number inside its flush group — and next() recomputes o, d from the group's pose table
+    with the arithmetic r2l_frame_rays computed them with, so the batches equal the plain store's bit for bit.  capacity_shards x
+    rays_per_shard rows, capacity_poses pose-table slots (13 floats each) and one int per shard, for frames of one size H x W.
+
+    RayStore's surface: append_frames() instead of append(), then next / seek / files / n_files / rows_per_file / describe /
+    close with the same contracts (two buffers, everything ordered on the CURRENT stream).  There is no append_files — rows from
+    files carry arbitrary rays — and plan() refuses: the fused iteration reads the 36-byte layout."""
+
+    ROW_BYTES, POSE_BYTES, SHARD_BYTES = 16, 52, 4
+
+    @staticmethod
+    def bytes_needed(capacity_shards, capacity_poses, rays_per_shard=4096):
+        """16 B per ray + 52 B per pose + 4 B per shard."""
+        return (int(capacity_shards) * int(rays_per_shard) * CompactRayStore.ROW_BYTES + int(capacity_poses) * CompactRayStore.POSE_BYTES
+                + int(capacity_shards) * CompactRayStore.SHARD_BYTES)
+
+    def __init__(self, capacity_shards, capacity_poses, H, W, device, rays_per_shard=4096, seed=0, logger=None):
+        import torch
+        from . import _lib
+        self.device = torch.device(device)
+        if self.device.type != "cuda":
+            raise RuntimeError("CompactRayStore lives in GPU memory: it needs a ROCm device (got %s)" % self.device)
+        if self.device.index is None:
+            self.device = torch.device("cuda", torch.cuda.current_device())
+        self.capacity, self.capacity_poses = int(capacity_shards), int(capacity_poses)
+        self.H, self.W = int(H), int(W)
+        self.rows_per_file, self.seed = int(rays_per_shard), int(seed) & M64
+        if self.capacity < 1 or self.capacity_poses < 1 or self.rows_per_file < 1 or self.rows_per_file % 4:
+            raise ValueError("CompactRayStore: capacity_shards >= 1, capacity_poses >= 1 and rays_per_shard a positive multiple of 4 "
+                             "(got %d, %d, %d)" % (self.capacity, self.capacity_poses, self.rows_per_file))
+        if self.H < 1 or self.W < 1 or self.H * self.W > 2**32 - 1:
+            raise ValueError("CompactRayStore: need H >= 1, W >= 1 and H * W <= 2^32 - 1 (got %d x %d)" % (self.H, self.W))
+        need = self.bytes_needed(self.capacity, self.capacity_poses, self.rows_per_file)
+        free, _total = torch.cuda.mem_get_info(self.device)
+        if need > 0.8 * free:
+            raise MemoryError("CompactRayStore: %d shards of %d rays and %d poses need %.2f GB, more than 80 %% of the %.2f GB free on %s"
+                              % (self.capacity, self.rows_per_file, self.capacity_poses, need / 1e9, free / 1e9, self.device))
+        self._lib, self._L = _lib, _lib.load()
+        self.data = torch.empty(self.capacity * self.rows_per_file, 4, dtype=torch.float32, device=self.device)  # { rgb, id }
+        self.pose_c2w = torch.empty(self.capacity_poses, 3, 4, dtype=torch.float32, device=self.device)
+        self.pose_focal = torch.empty(self.capacity_poses, dtype=torch.float32, device=self.device)
+        self.shard_pose0 = torch.empty(self.capacity, dtype=torch.int32, device=self.device)
+        self.desc = _lib.CompactStoreDesc(rows=self.data.data_ptr(), pose_c2w=self.pose_c2w.data_ptr(),
+                                          pose_focal=self.pose_focal.data_ptr(), shard_pose0=self.shard_pose0.data_ptr(),
+                                          capacity_shards=self.capacity, capacity_poses=self.capacity_poses,
+                                          rays_per_shard=self.rows_per_file, H=self.H, W=self.W)
+        self.nbytes = need
+        self.n_shards = 0
+        self.n_poses = 0
+        self.files = []  # one name per filled shard ("cstore:<k>")
+        self.n_files = None  # default of next()
+        self.draw = 0
+        self.last_ids = None
+        self._buf, self._ids, self._k = [None, None], [None, None], 0
+        self.logger = logger
+
+    def _stream(self):
+        import torch
+        return ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
+
+    def append_frames(self, rgb, c2ws, focals, key, shuffle=True):
+        """Append one flush group of K whole frames: rgb [K*H*W, 3] fp32 on the device (rows may be strided: the [:, 6:9] of
+        [o, d, rgb] rows), c2ws [K, 3, 4], focals [K] device tensor or one number for all K.  floor(K*H*W / rays_per_shard)
+        shards, rows shuffled by perm(key, K*H*W) as RayStore.append shuffles them.  Returns the number of shards written."""
+        import torch
+        if self.data is None:
+            raise RuntimeError("CompactRayStore is closed")
+        c2ws = torch.as_tensor(c2ws, dtype=torch.float32)  # (as render_frames takes its poses: [K, 3|4, 4], converted to fp32)
+        if c2ws.dim() != 3 or c2ws.shape[0] < 1 or c2ws.shape[1] not in (3, 4) or c2ws.shape[2] != 4:
+            raise ValueError("CompactRayStore.append_frames: need c2ws [K, 3|4, 4], K >= 1")
+        K = c2ws.shape[0]
+        c2ws = c2ws.to(self.device)[:, :3, :4].contiguous()
+        if (rgb.device != self.device or rgb.dtype != torch.float32 or rgb.dim() != 2 or tuple(rgb.shape) != (K * self.H * self.W, 3)):
+            raise ValueError("CompactRayStore.append_frames: need rgb [K*H*W, 3] = [%d, 3] fp32 on %s" % (K * self.H * self.W, self.device))
+        if rgb.stride(1) != 1 or rgb.stride(0) < 3:
+            rgb = rgb.contiguous()
+        fdev, f = None, 0.
+        if torch.is_tensor(focals):
+            if focals.device != self.device or focals.dtype != torch.float32 or tuple(focals.shape) != (K,):
+                raise ValueError("CompactRayStore.append_frames: need focals [K] fp32 on %s, or one number" % self.device)
+            fdev = focals.contiguous()
+        else:
+            f = float(focals)
+        m = ctypes.c_int64()
+        self._lib.check(self._L.r2l_cstore_append(ctypes.byref(self.desc), _p(rgb), rgb.stride(0), _p(c2ws), _p(fdev), f, K,
+                                                  self.n_shards, self.n_poses, int(key) & M64, int(bool(shuffle)), ctypes.byref(m),
+                                                  self._stream()), "r2l_cstore_append")
+        self.files += ["cstore:%d" % k for k in range(self.n_shards, self.n_shards + m.value)]
+        self.n_shards += m.value
+        self.n_poses += K
+        return m.value
+
+    def next(self, n_files=None):
+        """[n_files * rays_per_shard, 9] device tensor [o, d, rgb] of the next n_files draws; valid until the second-next call."""
+        import torch
+        n = int(self.n_files if n_files is None else n_files)
+        if self.data is None:
+            raise RuntimeError("CompactRayStore is closed")
+        if self.n_shards < 1:
+            raise RuntimeError("CompactRayStore.next: the store is empty")
+        k = self._k
+        if self._buf[k] is None or self._buf[k].shape[0] != n * self.rows_per_file:
+            # (a new tensor: the one handed out two calls ago stays the caller's; the allocator is stream-ordered)
+            self._buf[k] = torch.empty(n * self.rows_per_file, 9, dtype=torch.float32, device=self.device)
+            self._ids[k] = torch.empty(n, dtype=torch.int32, device=self.device)
+        self._lib.check(self._L.r2l_cstore_batch(ctypes.byref(self.desc), self.n_shards, self.draw, n, self.seed, _p(self._buf[k]),
+                                                 _p(self._ids[k]), self._stream()), "r2l_cstore_batch")
+        self.draw += n
+        self.last_ids = self._ids[k]
+        self._k ^= 1
+        return self._buf[k]
+
+    __next__ = next
+
+    def __iter__(self):
+        return self
+
+    def plan(self, n_files=None):
+        raise NotImplementedError("CompactRayStore.plan: r2l_train_batch / r2l_student_train_step read the 36-byte rows of a RayStore; "
+                                  "a compact store hands out batches through next() only")
+
+    def seek(self, draw):
+        if draw < 0:
+            raise ValueError("CompactRayStore.seek: negative draw")
+        self.draw = int(draw)
+
+    def describe(self):
+        return "compact, %d / %d shards of %d rays and %d / %d poses, %.3f GB of %.3f GB allocated in device memory " \
+               "(16 B/ray + 52 B/pose + 4 B/shard)" % (
+                   self.n_shards, self.capacity, self.rows_per_file, self.n_poses, self.capacity_poses,
+                   self.bytes_needed(self.n_shards, self.n_poses, self.rows_per_file) / 1e9, self.nbytes / 1e9)
+
+    def close(self):
+        self.data = self.pose_c2w = self.pose_focal = self.shard_pose0 = self.desc = None
         self._buf, self._ids, self.last_ids = [None, None], [None, None], None

@@ -8,7 +8,9 @@
   fill   poses/s of the teacher fill (fill_store_from_teacher) against create_data --r2l_fused_frames for the same poses at
          400 x 400, alternated, and the append's share of a flush group (device events)
 
-python tools/raystore_time.py [loop] [draw] [files] [fill] [--reps 3] [--poses 100] [--chunk 50]"""
+python tools/raystore_time.py [loop] [draw] [files] [fill] [--reps 3] [--poses 100] [--chunk 50]
+python tools/raystore_time.py --compact [--reps 3] [--poses 100]   the compact store (CompactRayStore, 16 B/ray) against the plain
+         one: next(20) / next(1), a flush group of fill_group, memory after the fill -> profiles/cstore.txt (compact() below)"""
 import argparse
 import os
 import shutil
@@ -112,13 +114,121 @@ def fill(reps, n_pose, chunk):
     shutil.rmtree(tmp)
 
 
+def _synthetic_group(K, H, W, rng):
+    """(rows [K*H*W, 9], c2ws [K, 3, 4], focals [K]): rays of K random poses from r2l_frame_rays, random rgb."""
+    import ctypes
+    from r2l_amd import _lib
+    c2ws = torch.stack([data.get_rand_pose(rng)[:3, :4] for _ in range(K)], 0).float().cuda().contiguous()
+    focals = torch.tensor(555.5555155968841 * (1 + rng.rand(K)), dtype=torch.float32, device="cuda")
+    rows = torch.empty(K * H * W, 9, device="cuda")
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    _lib.check(_lib.load().r2l_frame_rays(p(c2ws), p(focals), 0., K, H, W, None, None, None, p(rows),
+                                          ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "r2l_frame_rays")
+    rows[:, 6:9] = torch.rand(K * H * W, 3, device="cuda")
+    return rows, c2ws, focals
+
+
+def _us_per_call(store, n_files, calls=200):
+    for _ in range(20):
+        store.next(n_files)
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        store.next(n_files)
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls * 1e3
+
+
+def compact(reps, n_pose, out_path):
+    """--compact: the compact store (16 B/ray, CompactRayStore) against the plain one (36 B/ray, RayStore), all in this process,
+    `reps` rounds alternating the two; medians, and the spread (max - min) between the runs of the same path.
+      next   us per next(20) and per next(1) at H = W = 400 (4 flush groups of 6 poses: 936 shards), device events around 200 calls
+      fill   ms per flush group of fill_group (n_pose poses at 400 x 400 in one group), device events of TeacherFill
+      bytes  torch.cuda.memory_allocated after the fill against the byte arithmetic"""
+    from r2l_amd.online_kd import TeacherFill
+    from r2l_amd.raystore import CompactRayStore
+    H = W = 400
+    lines = ["tools/raystore_time.py --compact --reps %d --poses %d   (%s)" % (reps, n_pose, torch.cuda.get_device_name(0))]
+    say = lambda s: (lines.append(s), print(s))
+    # ---- next ----
+    K, G = 6, 4
+    cap = G * (K * H * W // 4096)
+    plain, comp = RayStore(cap, "cuda", seed=5), CompactRayStore(cap, G * K, H, W, "cuda", seed=5)
+    rng = np.random.RandomState(0)
+    for g in range(G):
+        rows, c2ws, focals = _synthetic_group(K, H, W, rng)
+        plain.append(rows, key=g + 1)
+        comp.append_frames(rows[:, 6:9], c2ws, focals, key=g + 1)
+        del rows
+    assert torch.equal(plain.next(3), comp.next(3))
+    for n in (20, 1):
+        us = {"plain": [], "compact": []}
+        for r in range(reps):
+            us["plain"].append(_us_per_call(plain, n))
+            us["compact"].append(_us_per_call(comp, n))
+        a, b = np.array(us["plain"]), np.array(us["compact"])
+        say("next(%d) over %d shards at %dx%d: plain %s us (median %.2f, spread %.2f) | compact %s us (median %.2f, spread %.2f) | "
+            "compact - plain %+.2f us; bytes per ray: plain 36 read + 36 written, compact 16 read + 36 written; compact moves "
+            "%.0f GB/s" % (n, cap, H, W, np.round(a, 2).tolist(), np.median(a), a.max() - a.min(), np.round(b, 2).tolist(), np.median(b),
+                          b.max() - b.min(), np.median(b) - np.median(a), n * 4096 * 52 / np.median(b) / 1e3))
+    plain.close()
+    comp.close()
+    del plain, comp
+    torch.cuda.empty_cache()
+    # ---- fill ----
+    tmp = tempfile.mkdtemp(prefix="r2l_cfill_")
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    ck = os.path.join(tmp, "teacher.tar")
+    torch.save({"global_step": 200000, "network_fn_state_dict": csd, "network_fine_state_dict": fsd}, ck)
+    targs = options.parse_teacher_config(os.path.join(ROOT, "configs", "lego.txt"), teacher_ckpt=ck)
+    focal = 555.5555155968841
+    shards = shards_needed(n_pose, n_pose, H, W)
+    ms, alloc = {"plain": [], "compact": []}, {}
+    for r in range(reps + 1):  # (the first round warms both up and is not counted)
+        for tag in ("plain", "compact"):
+            torch.cuda.synchronize()
+            torch.cuda.empty_cache()
+            base = torch.cuda.memory_allocated()
+            store = RayStore(shards, "cuda") if tag == "plain" else CompactRayStore(shards, n_pose, H, W, "cuda")
+            state = TeacherFill(store, targs, H, W, focal, 2., 6., n_pose, n_pose, 0, 1, "cuda")
+            state.fill_group()
+            torch.cuda.synchronize()
+            e = state.append_ms[0]
+            if r:
+                ms[tag].append((e[0].elapsed_time(e[2]), e[1].elapsed_time(e[2])))
+            del state, e
+            torch.cuda.empty_cache()
+            alloc[tag] = (torch.cuda.memory_allocated() - base, store.nbytes)
+            store.close()
+            del store
+    for tag in ("plain", "compact"):
+        g = np.array([m[0] for m in ms[tag]])
+        ap_ = np.array([m[1] for m in ms[tag]])
+        say("fill_group, %d poses at %dx%d into the %s store: %s ms per flush group (median %.1f, spread %.1f); of which the append %s ms"
+            % (n_pose, H, W, tag, np.round(g, 1).tolist(), np.median(g), g.max() - g.min(), np.round(ap_, 3).tolist()))
+    for tag in ("plain", "compact"):
+        say("after the fill, %s store: torch.cuda.memory_allocated grew by %d B; byte arithmetic %d B (%d shards of 4096 rays%s)" %
+            (tag, alloc[tag][0], alloc[tag][1], shards, "" if tag == "plain" else ", %d poses" % n_pose))
+    say("not measured: the 800x800 / 10 000-pose fill (102.4 GB by the arithmetic above)")
+    shutil.rmtree(tmp)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["draw", "files", "loop", "fill"])
     ap.add_argument("--reps", type=int, default=3)
     ap.add_argument("--poses", type=int, default=100)
     ap.add_argument("--chunk", type=int, default=50)
+    ap.add_argument("--compact", action="store_true", help="compact store against the plain one -> profiles/cstore.txt")
+    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cstore.txt"))
     a = ap.parse_args()
+    if a.compact:
+        compact(a.reps, a.poses, a.out)
+        sys.exit(0)
     sys.argv = sys.argv[:1]  # (e2e_train passes its own command line through to main.py)
     for what in a.what:
         {"loop": lambda: loop(a.reps), "draw": draw, "files": files, "fill": lambda: fill(a.reps, a.poses, a.chunk)}[what]()
