@@ -591,6 +591,22 @@ int r2l_cstore_append(const r2l_cstore* store, const float* rgb, int64_t rgb_str
 int r2l_cstore_batch(const r2l_cstore* store, int64_t n_shards, int64_t draw0, int64_t n_draw, uint64_t seed,
                      float* batch /*[n_draw * rays_per_shard, 9]*/, int32_t* ids_out, void* stream);
 
+/* ---- digest of a ray store's shards (the checksums of a store file) ------------------------------------------------------------
+ * r2l_words_digest (csrc/r2l_store_digest.hip): n_items items of words_per_item 32-bit words each, contiguous in device memory;
+ *   out[k] = sum over i < words_per_item of epoch_key(((uint64_t)i << 32) | words[k * words_per_item + i], salt + k)   (mod 2^64)
+ * with epoch_key exactly as specified for r2l_store_batch above (csrc/r2l_perm.h perm_epoch_key).  An integer sum: the result
+ * does not depend on the order of the reduction, so the kernel and r2l_amd/raystore.py (words_digest_spec) agree bit for bit with
+ * no order pinned.  The word's position i and the item's number k enter the hash: swapped words or swapped items change it.
+ * RayStore.save / .load (r2l_amd/raystore.py; INTEGRATION.md "store file") call it with one item per shard — words_per_item =
+ * rays_per_shard * 9, or * 4 for a compact store — and once per pose-table section as a single item.
+ * Stateless; checks its arguments before any launch, enqueues hipMemsetAsync(out) and one kernel on `stream`, never synchronises;
+ * all offsets are 64-bit.  Reads words[0 .. n_items * words_per_item), writes out[0 .. n_items) and nothing else.
+ * hipErrorInvalidValue (r2l_last_error names the argument): n_items < 0, words_per_item outside [1, 2^32), words or out NULL with
+ * n_items > 0, words not 4-byte aligned, out not 8-byte aligned.  n_items == 0 enqueues nothing.  Items that start on a 16-byte
+ * boundary are read with 16-byte loads throughout; others through up to 3 single words at either end. */
+int r2l_words_digest(const uint32_t* words, int64_t words_per_item, int64_t n_items, uint64_t salt, uint64_t* out /* dev [n_items] */,
+                     void* stream);
+
 /* r2l_train_batch: the batch of a student step in ONE launch instead of r2l_store_batch -> r2l_pool_pick -> r2l_pool_augment
  * (csrc/r2l_student_step.hip).  With B = n_draw * rays_per_shard, out_o / out_d / out_t are [B + n_out, 3] contiguous:
  *   rows [0, B):          the rows of the shards id(draw0 + j), j < n_draw — id exactly as specified for r2l_store_batch above —

@@ -165,6 +165,7 @@ SIGNATURES = {
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
     "r2l_cstore_append": (_i, [_cstorep, _p, _l, _p, _p, _f, _i, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_cstore_batch": (_i, [_cstorep, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
+    "r2l_words_digest": (_i, [_p, _l, _l, ctypes.c_uint64, _p, _p]),
     "r2l_train_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
     "r2l_student_step_work_floats": (_l, [_sstepp]),
     "r2l_student_train_step": (_i, [_sstepp] + [_p] * 13),

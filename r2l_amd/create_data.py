@@ -83,12 +83,42 @@ def next_free_shard_index(names):
     return max(used) + 1 if used else 0
 
 
+def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device, logger):
+    """--r2l_store_save: render this rank's poses into a ray store in device memory and write it as one file (the name is the
+    path at world size 1, <path>.rank<r>of<w> otherwise)."""
+    from .online_kd import TeacherFill, rank_poses, shards_needed
+    from .raystore import CompactRayStore, RayStore, store_rank_path
+    n_pose = args.n_pose_kd if isinstance(args.n_pose_kd, int) else int(args.n_pose_kd[0])
+    cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
+    if cap < 1:
+        raise ValueError("--r2l_store_save: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
+    if args.r2l_compact_store:
+        store = CompactRayStore(cap, len(rank_poses(n_pose, rank, world)), H, W, device, seed=9973 * rank, logger=logger)
+    else:
+        store = RayStore(cap, device, seed=9973 * rank, logger=logger)
+    t0 = time.time()
+    filler = TeacherFill(store, args, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
+                         rand_pose=rand_pose, ndc=ndc)
+    prov = filler.provenance()
+    while not filler.done:
+        filler.fill_group()
+    sync(device)
+    n_rays = store.n_shards * store.rows_per_file
+    logger.info("ray store: %s; %d rays in %.1fs" % (store.describe(), n_rays, time.time() - t0))
+    info = store.save(store_rank_path(args.r2l_store_save, rank, world), provenance=prov, rank=rank, world=world)
+    store.close()
+    return {"n_rays": n_rays, "store_file": info["path"], "save": info, "logger": logger}
+
+
 def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
     if args.create_data != "rand":
         raise NotImplementedError("only --create_data rand (the README pipeline) is on the accelerated path")
     rank, world, device = init_distributed()
+    if args.r2l_store_save:  # the store is filled through the fused frames path: its refusals, before anything is loaded
+        from .online_kd import check_teacher_args
+        check_teacher_args(args, device)
     logger = Logger(args, rank)
     rng = np.random.RandomState(1000003 * rank)  # per-rank pose / focal / shuffle stream
 
@@ -119,6 +149,13 @@ def main(argv=None):
                               lpips_params=load_lpips_weights(args, device, logger),
                               lpips_vgg_params=load_lpips_vgg_weights(args, device, logger))
         logger.info("Teacher test: Loss %.4f PSNR %.4f%s" % (misc["test_loss"].item(), misc["test_psnr"].item(), lpips_field(misc)))
+
+    if args.r2l_store_save:
+        # no shard files and no --datadir_kd: the poses go through the online fill (online_kd.TeacherFill: the same RandomState,
+        # frame ids and flush keys) into a device-resident store, compact with --r2l_compact_store, and the store is written as
+        # one checksummed file — the very rows main.py --r2l_online_kd would have rendered, for main.py --r2l_store_load
+        del coarse, fine, kwargs  # (TeacherFill builds its own pair and releases it after the last group)
+        return store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device, logger)
 
     datadir_new = args.datadir_kd.split(":")[-1]
     if rank == 0:

@@ -4,6 +4,7 @@ accelerated path only.  One process per GPU; under torchrun the ray shards, test
 rank-partitioned and the only collective is the flat-gradient all-reduce inside R2LTrainer.
 """
 import ctypes
+import json
 import math
 import os
 import time
@@ -17,7 +18,7 @@ from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
-from .options import parse_args, validate_accelerated, validate_compact_store, validate_fused_iter
+from .options import parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_store_file
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -720,6 +721,7 @@ def main(argv=None):
     validate_accelerated(args)
     validate_fused_iter(args)
     validate_compact_store(args)
+    validate_store_file(args)
     is_teacher = args.model_name == "nerf"
     if is_teacher and (not args.render_only or args.benchmark):
         # (--benchmark times render_func = the R2L student's forward, main.py:401-404,1124-1133)
@@ -821,7 +823,7 @@ def main(argv=None):
         return {"ms_per_frame": per * 1e3, "logger": logger}
 
     # ---------------- distillation training (data_mode rays) ----------------
-    if not args.r2l_online_kd and (args.data_mode != "rays" or not args.datadir_kd):
+    if not (args.r2l_online_kd or args.r2l_store_load) and (args.data_mode != "rays" or not args.datadir_kd):
         raise NotImplementedError("training on the accelerated path needs --data_mode rays --datadir_kd <dir of "
                                   "[4096,9] .npy ray shards> (README step 3/5), or --r2l_online_kd (the teacher renders into a "
                                   "device-resident ray store)")
@@ -868,8 +870,32 @@ def main(argv=None):
         while not filler.done and (n_groups is None or filler.groups < n_groups):
             filler.fill_group()
         files = loader.files
+        if args.r2l_store_save:  # (--r2l_kd_every 0, checked at start-up: the fill is complete) render once, train many times
+            from .raystore import store_rank_path
+            loader.save(store_rank_path(args.r2l_store_save, rank, world), provenance=filler.provenance(), rank=rank, world=world)
         if filler.done:
             filler = None
+    elif args.r2l_store_load:
+        # the store a run with --r2l_store_save (or utils/create_data.py) wrote: plain or compact as the file says, its digests
+        # recomputed on the device before a row of it is trained on
+        from .raystore import load_store, read_store_header, store_rank_path
+        path = store_rank_path(args.r2l_store_load, rank, world)
+        hdr = read_store_header(path)
+        if (hdr["rank"], hdr["world"]) != (rank, world):
+            raise ValueError("--r2l_store_load %s: written by rank %d of %d, this is rank %d of %d" %
+                             (path, hdr["rank"], hdr["world"], rank, world))
+        if hdr["kind"] == 1 and (hdr["H"], hdr["W"]) != (H, W):
+            raise ValueError("--r2l_store_load %s: a compact store of %d x %d frames, the scene is %d x %d" %
+                             (path, hdr["H"], hdr["W"], H, W))
+        if hdr["n_shards"] < shards[rank]:
+            raise ValueError("--r2l_store_load %s: %d shards, one step of this rank draws %d (--N_rand %d over %d ranks)" %
+                             (path, hdr["n_shards"], shards[rank], args.N_rand, world))
+        if hdr["kind"] == 1 and args.r2l_fused_iter:
+            raise ValueError("--r2l_store_load %s: a compact store hands out batches through its own kernel: not with "
+                             "--r2l_fused_iter, which reads the 36-byte rows of the plain store" % path)
+        logger.info("ray store file %s: provenance %s" % (path, json.dumps(hdr["provenance"], sort_keys=True)))
+        loader = load_store(path, device, seed=9973 * rank, logger=logger)
+        files = loader.files
     elif args.r2l_device_store:
         # the shard files are read ONCE into device memory; no reader threads, no per-step host-to-device copy
         from .raystore import RayStore
@@ -888,7 +914,7 @@ def main(argv=None):
         files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
         loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
                                   threads=max(1, min(args.num_workers, 16)))
-    if args.r2l_online_kd or args.r2l_device_store:
+    if args.r2l_online_kd or args.r2l_device_store or args.r2l_store_load:
         loader.n_files = shards[rank]
         logger.info("ray store: %s" % loader.describe())
         if start > 0:  # --resume: the sampler is a pure function of (seed, shard count, draw): only the counter is restored

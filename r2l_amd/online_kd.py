@@ -54,9 +54,11 @@ class TeacherFill:
         self.at = 0  # poses of self.mine rendered so far
         self.groups = 0
         self.append_ms = []  # (event pair) per group: the append's share of a flush group, read by tools/raystore_time.py
+        self.n_pose = int(n_pose)
         self.coarse, self.fine = create_teacher(targs, self.device)
+        self.r2l_config = None  # the record apply_arithmetic returns (precision of the teacher kernels): provenance()
         if logger is not None:
-            apply_arithmetic(targs, self.device, logger, teachers=(self.coarse, self.fine))
+            self.r2l_config = apply_arithmetic(targs, self.device, logger, teachers=(self.coarse, self.fine))
 
     @property
     def pending(self):
@@ -69,6 +71,16 @@ class TeacherFill:
     def _info(self, msg):
         if self.logger is not None:
             self.logger.info(msg)
+
+    def provenance(self):
+        """What a store file says about its fill (raystore.RayStore.save): for the log of the run that loads it, nothing is
+        derived from it.  No time stamp: equal fills give equal files."""
+        import os
+        a = self.targs
+        return {"teacher_ckpt": a.teacher_ckpt, "N_samples": a.N_samples, "N_importance": a.N_importance, "perturb": a.perturb,
+                "white_bkgd": bool(a.white_bkgd), "use_rand_focal": bool(a.use_rand_focal), "n_pose": self.n_pose,
+                "create_data_chunk": self.chunk, "near": self.near, "far": self.far, "ndc": self.ndc, "focal": self.focal,
+                "precision": (self.r2l_config or {}).get("precision", a.r2l_precision), "R2L_SEED": os.environ.get("R2L_SEED", "0")}
 
     def fill_group(self):
         """Render the next flush group into the store; returns the number of shards it added."""

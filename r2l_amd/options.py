@@ -65,6 +65,12 @@ FLAGS = {
     # batches bit for bit in 4/9 of the memory.  Not with r2l_device_store (rows from files carry arbitrary rays) or
     # r2l_fused_iter (the one-call iteration reads 36-byte rows).  utils/create_data.py / utils/train_nerf.py ignore it
     "r2l_compact_store": ("flag", False),
+    # a filled store as one checksummed file per rank (raystore.RayStore.save / load_store; INTEGRATION.md "store file"): render
+    # once, train many times.  r2l_store_save (main.py with r2l_online_kd and r2l_kd_every 0: written once the fill is complete;
+    # utils/create_data.py --create_data rand: the poses go into a store instead of shard files, compact with r2l_compact_store).
+    # r2l_store_load: a third source of main.py's training beside r2l_online_kd and r2l_device_store; the kind comes from the
+    # file.  The name is the path at world size 1, <path>.rank<r>of<w> otherwise.  utils/train_nerf.py ignores both
+    "r2l_store_save": (str, ""), "r2l_store_load": (str, ""),
     # forward-facing LLFF scenes (--dataset_type llff: --factor, --llffhold, --no_ndc; NDC rays through r2l_ndc_rays); opt-in —
     # without the switch --dataset_type llff is refused as it always was.  configs/fern.txt and its kin carry it
     "r2l_llff": ("flag", False),
@@ -255,12 +261,29 @@ def validate_compact_store(args):
         raise ValueError("--r2l_compact_store needs --r2l_online_kd (the teacher fills the store)")
 
 
+def validate_store_file(args):
+    """--r2l_store_save / --r2l_store_load as main.py takes them (utils/create_data.py has its own use of --r2l_store_save,
+    utils/train_nerf.py ignores both).  Names the other flag, before anything is loaded."""
+    if args.r2l_store_load:
+        for other in ("r2l_online_kd", "r2l_device_store", "r2l_kd_every", "r2l_store_save"):
+            if getattr(args, other):
+                raise ValueError("--r2l_store_load takes the store from a file: not with --%s (one source of rays per run, and a "
+                                 "loaded store is not saved again)" % other)
+    if args.r2l_store_save:
+        if not args.r2l_online_kd:
+            raise ValueError("--r2l_store_save writes the store the teacher fills: it needs --r2l_online_kd (or "
+                             "utils/create_data.py --create_data rand, which renders into a store and writes the file)")
+        if args.r2l_kd_every > 0:
+            raise ValueError("--r2l_store_save writes the complete store before iteration 1: not with --r2l_kd_every %d, a store "
+                             "that grows during training has no single content" % args.r2l_kd_every)
+
+
 def validate_fused_iter(args, world=1, device_type="cuda"):
     """--r2l_fused_iter (main.py only): the student's iteration as one library call draws its batch from a ray store and moves
     the pool's rows itself, on one GPU.  Names what is missing before anything is loaded."""
     if not args.r2l_fused_iter:
         return
-    if not (args.r2l_device_store or args.r2l_online_kd):
+    if not (args.r2l_device_store or args.r2l_online_kd or args.r2l_store_load):
         raise ValueError("--r2l_fused_iter draws its batches from a ray store: it needs --r2l_device_store or --r2l_online_kd")
     if args.hard_ratio and not args.r2l_device_pool:
         raise ValueError("--r2l_fused_iter with --hard_ratio needs --r2l_device_pool (the hard rays are ranked inside the call)")

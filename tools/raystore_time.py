@@ -10,7 +10,9 @@
 
 python tools/raystore_time.py [loop] [draw] [files] [fill] [--reps 3] [--poses 100] [--chunk 50]
 python tools/raystore_time.py --compact [--reps 3] [--poses 100]   the compact store (CompactRayStore, 16 B/ray) against the plain
-         one: next(20) / next(1), a flush group of fill_group, memory after the fill -> profiles/cstore.txt (compact() below)"""
+         one: next(20) / next(1), a flush group of fill_group, memory after the fill -> profiles/cstore.txt (compact() below)
+python tools/raystore_time.py --file [--reps 3] [--poses 100]   the store file: r2l_words_digest against a device copy, save and
+         load of a plain and a compact store -> profiles/store_file.txt (store_file() below)"""
 import argparse
 import os
 import shutil
@@ -217,6 +219,95 @@ def compact(reps, n_pose, out_path):
         f.write("\n".join(lines) + "\n")
 
 
+def _ms_per_call(fn, calls=20, warm=3):
+    for _ in range(warm):
+        fn()
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    for _ in range(calls):
+        fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1) / calls
+
+
+def store_file(reps, n_pose, out_path):
+    """--file: the store file (RayStore.save / load_store, r2l_words_digest) for a plain and a compact store after one flush group
+    of n_pose poses at 400 x 400, all in this process, `reps` rounds alternating the two stores; medians and the spread.
+      digest  r2l_words_digest over the rows (one item a shard) in GB/s read, device events around 20 calls, against a torch
+              device-to-device copy of the same bytes (which reads and writes them)
+      save    RayStore.save to a temporary directory: seconds and GB/s, digests, pinned staging, pwrite and fsync included
+      load    load_store of that file: seconds and GB/s, allocation, staging and the digest check included"""
+    import ctypes
+    from r2l_amd import _lib
+    from r2l_amd.online_kd import TeacherFill
+    from r2l_amd.raystore import CompactRayStore, load_store
+    H = W = 400
+    lines = ["tools/raystore_time.py --file --reps %d --poses %d   (%s)" % (reps, n_pose, torch.cuda.get_device_name(0))]
+    say = lambda s: (lines.append(s), print(s))
+    tmp = tempfile.mkdtemp(prefix="r2l_sfile_")
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    ck = os.path.join(tmp, "teacher.tar")
+    torch.save({"global_step": 200000, "network_fn_state_dict": csd, "network_fine_state_dict": fsd}, ck)
+    targs = options.parse_teacher_config(os.path.join(ROOT, "configs", "lego.txt"), teacher_ckpt=ck)
+    shards = shards_needed(n_pose, n_pose, H, W)
+    stores, prov = {}, {}
+    for tag in ("plain", "compact"):
+        store = RayStore(shards, "cuda") if tag == "plain" else CompactRayStore(shards, n_pose, H, W, "cuda")
+        state = TeacherFill(store, targs, H, W, 555.5555155968841, 2., 6., n_pose, n_pose, 0, 1, "cuda")
+        state.fill_group()
+        torch.cuda.synchronize()
+        e = state.append_ms[0]
+        say("fill_group, %d poses at %dx%d into the %s store: %.1f ms (one flush group; the plain fill is the first of the process)" %
+            (n_pose, H, W, tag, e[0].elapsed_time(e[2])))
+        stores[tag], prov[tag] = store, state.provenance()
+        del state, e
+        torch.cuda.empty_cache()
+    L, lib = _lib, _lib.load()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    res = {tag: {"digest": [], "copy": [], "save": [], "load": []} for tag in stores}
+    for r in range(reps):
+        for tag, store in stores.items():
+            rows = store.data[:store.n_shards * store.rows_per_file]
+            nbytes = rows.numel() * 4
+            out = torch.empty(store.n_shards, dtype=torch.int64, device="cuda")
+            st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+            wpi = store.rows_per_file * store.ROW_WORDS
+            ms = _ms_per_call(lambda: L.check(lib.r2l_words_digest(p(rows), wpi, store.n_shards, 1, p(out), st), "r2l_words_digest"))
+            res[tag]["digest"].append(nbytes / ms / 1e6)
+            dst = torch.empty_like(rows)
+            res[tag]["copy"].append(nbytes / _ms_per_call(lambda: dst.copy_(rows)) / 1e6)
+            del dst, out
+            path = os.path.join(tmp, tag + ".r2l")
+            info = store.save(path, provenance=prov[tag])
+            res[tag]["save"].append((info["seconds"], info["GB/s"]))
+            loaded = load_store(path, "cuda")
+            res[tag]["load"].append((loaded.load_info["seconds"], loaded.load_info["GB/s"]))
+            if r == 0:
+                assert all(torch.equal(a, b) for (_, a), (_, b) in zip(store._sections(), loaded._sections()))
+                res[tag]["bytes"] = info["bytes"]
+            loaded.close()
+            del loaded
+            torch.cuda.empty_cache()
+    for tag in stores:
+        d, c = np.array(res[tag]["digest"]), np.array(res[tag]["copy"])
+        say("%s store, %d shards of 4096 rays, rows %.3f GB: r2l_words_digest %s GB/s read (median %.0f, spread %.0f) | torch copy of "
+            "the same bytes %s GB/s copied, i.e. read and written (median %.0f, spread %.0f)" %
+            (tag, shards, stores[tag].n_shards * 4096 * stores[tag].ROW_WORDS * 4 / 1e9, np.round(d).tolist(), np.median(d), d.max() - d.min(),
+             np.round(c).tolist(), np.median(c), c.max() - c.min()))
+        for what in ("save", "load"):
+            s, g = np.array([x[0] for x in res[tag][what]]), np.array([x[1] for x in res[tag][what]])
+            say("%s store, file of %d B: %s %s s (median %.3f, spread %.3f) = %s GB/s (median %.2f)" %
+                (tag, res[tag]["bytes"], what, np.round(s, 3).tolist(), np.median(s), s.max() - s.min(), np.round(g, 2).tolist(), np.median(g)))
+    say("the file system is a temporary directory of the machine (%s) and a load reads what the save just wrote (page cache); the "
+        "rows are re-read from device memory call after call, partly out of the last-level cache at these sizes, the copy's as the "
+        "digest's; not measured: a 10 000-pose store (25.6 / 57.6 GB)" % tempfile.gettempdir())
+    shutil.rmtree(tmp)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["draw", "files", "loop", "fill"])
@@ -224,8 +315,13 @@ if __name__ == "__main__":
     ap.add_argument("--poses", type=int, default=100)
     ap.add_argument("--chunk", type=int, default=50)
     ap.add_argument("--compact", action="store_true", help="compact store against the plain one -> profiles/cstore.txt")
-    ap.add_argument("--out", default=os.path.join(ROOT, "profiles", "cstore.txt"))
+    ap.add_argument("--file", action="store_true", help="store file: digest, save and load rates -> profiles/store_file.txt")
+    ap.add_argument("--out", default=None, help="default: profiles/cstore.txt (--compact), profiles/store_file.txt (--file)")
     a = ap.parse_args()
+    a.out = a.out or os.path.join(ROOT, "profiles", "store_file.txt" if a.file else "cstore.txt")
+    if a.file:
+        store_file(a.reps, a.poses, a.out)
+        sys.exit(0)
     if a.compact:
         compact(a.reps, a.poses, a.out)
         sys.exit(0)
