@@ -702,6 +702,33 @@ int r2l_pixel_batch(const float* images /*dev [n_img,H,W,3]*/, const float* c2w 
                     float focal, int ndc, int64_t draw0, int64_t n_draw, uint64_t seed, float* rays_o, float* rays_d,
                     float* viewdirs, float* target /*each [n_draw,3]*/, int64_t* ids_out /*[n_draw] or NULL*/, void* stream);
 
+/* ---- pixel sampler of teacher training, images mode (one image and a window of it per iteration) ---------------------------
+ * The reference's no_batching mode (main.py:1260-1302) draws one training image per iteration and N_rand of its pixels without
+ * replacement, for the first precrop_iters iterations from a centre crop.  Here draw j < n_draw takes position
+ *   q = pi(key, win_h*win_w)(j)                          (pi exactly as specified for r2l_store_append above)
+ * of the win_h x win_w window whose first pixel is (row0, col0), row-major: row = row0 + q / win_w, col = col0 + q % win_w.
+ * A prefix of a bijection: the n_draw <= win_h*win_w pixels are distinct.  The five outputs are, bit for bit, what r2l_pixel_batch
+ * writes for pixel (img, row, col): target, the world ray, viewdirs of the world d, the r2l_ndc_rays image at near plane 1 with
+ * ndc == 1, and ids_out[j] = (img*H + row)*W + col (one per-pixel body serves both kernels).
+ * Stateless: the arguments are checked before any launch, one kernel is enqueued on `stream`, nothing synchronises.  n_draw == 0
+ * is a successful no-op; all offsets are 64-bit.  hipErrorInvalidValue (with r2l_last_error): what r2l_pixel_batch refuses (a NULL
+ * required pointer, n_img / H / W < 1, focal <= 0, n_draw < 0, ndc not 0 or 1, n_img*H*W > 2^31 - 1), img outside [0, n_img),
+ * win_h < 1 or win_w < 1, a window that leaves the frame (row0 < 0, row0 + win_h > H, col0 < 0, col0 + win_w > W),
+ * n_draw > win_h*win_w.  r2l_amd/image_batch.py (window_ids, host_batch) restates it.
+ *
+ * r2l_image_draw: the image and the key of an iteration, host integer arithmetic only (no device work, no stream).  With
+ * epoch_key exactly as specified for r2l_store_batch above:
+ *   z        = epoch_key(seed ^ 0x696D675F6D6F6465, iteration)            (iteration >= 1)
+ *   *img_out = ((z >> 40) * n_img) >> 24                                  (the top 24 bits of z scaled to [0, n_img))
+ *   *key_out = epoch_key(z, 0)
+ * A pure function of (seed, iteration, n_img): a C host trains in images mode with r2l_image_draw -> r2l_image_batch ->
+ * r2l_teacher_train_step and resumes with no sampler state.  hipErrorInvalidValue: iteration < 1, n_img < 1, a NULL output. */
+int r2l_image_batch(const float* images /*dev [n_img,H,W,3]*/, const float* c2w /*dev [n_img,3,4]*/, int n_img, int H, int W,
+                    float focal, int ndc, int img, int row0, int col0, int win_h, int win_w, uint64_t key, int64_t n_draw,
+                    float* rays_o, float* rays_d, float* viewdirs, float* target /*each [n_draw,3]*/,
+                    int64_t* ids_out /*[n_draw] or NULL*/, void* stream);
+int r2l_image_draw(uint64_t seed, int64_t iteration /*>= 1*/, int n_img, int* img_out, uint64_t* key_out);
+
 /* ---- one teacher training step in one library call ------------------------------------------------------------------------
  * What r2l_amd/teacher_train.py (TeacherTrainer.forward_backward + adam) assembles per step from the stages above, behind the C
  * ABI (csrc/r2l_teacher_step.hip): a pure function of (weights, optimizer state, batch, seed, step).  Those very kernels, in this

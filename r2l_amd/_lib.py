@@ -170,6 +170,8 @@ SIGNATURES = {
     "r2l_student_step_work_floats": (_l, [_sstepp]),
     "r2l_student_train_step": (_i, [_sstepp] + [_p] * 13),
     "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
+    "r2l_image_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, ctypes.c_uint64, _l, _p, _p, _p, _p, _p, _p]),
+    "r2l_image_draw": (_i, [ctypes.c_uint64, _l, _i, _p, _p]),
     "r2l_teacher_step_work_floats": (_l, [_stepp]),
     "r2l_teacher_train_step": (_i, [_stepp] + [_p] * 15),
     "r2l_png_writer_open": (_i, [_i, _i, _p]),

@@ -12,6 +12,10 @@
 //   r2l_pixel_batch       : the batching mode of teacher training (main.py:1137-1162, 1199-1210) without its bank of rays:
 //                           draw t takes pixel pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img*H*W training pixels
 //                           (csrc/r2l_perm.h, the ray store's sampler), and its ray is computed on the spot
+//   r2l_image_batch       : the images mode of teacher training (main.py:1260-1302): draw j takes position pi(key, win_h*win_w)(j)
+//                           of a window of ONE image — n_draw distinct pixels, what np.random.choice(.., replace=False) gives —
+//                           through the per-pixel body of r2l_pixel_batch; r2l_image_draw (host arithmetic) names the image and
+//                           the key of an iteration
 // The kernels here move 12 - 72 bytes per ray: a thread per ray (per Philox block of four draws), no LDS.
 #include "r2l_dispatch.h"
 #include "r2l_perm.h"
@@ -155,10 +159,34 @@ __global__ void r2l_ndc_rays_kernel(const float* rays_o, const float* rays_d, in
     }
 }
 
+// Output row j of a pixel sampler: pixel g = (img * H + row) * W + col of the training images.  The ONE per-pixel body behind
+// r2l_pixel_batch and r2l_image_batch, which differ only in how they choose (img, row, col).  NDC: viewdirs take the world ray,
+// rays_o / rays_d its ndc_rays image at near plane 1 (what train_nerf.device_rays does to the selected rays).
+template <bool NDC>
+__device__ __forceinline__ void pixel_row(const float* __restrict__ images, const float* __restrict__ c2w, int H, int W, float focal,
+                                          int64_t img, int row, int col, int64_t j, float* __restrict__ rays_o,
+                                          float* __restrict__ rays_d, float* __restrict__ viewdirs, float* __restrict__ target,
+                                          int64_t* __restrict__ ids_out, float cw, float ch) {
+    const int64_t g = (img * H + row) * W + col;
+    float o[3], d[3];
+    pixel_ray(c2w + img * 12, focal, H, W, row, col, o, d);
+    const float nrm = ray_norm(d);
+    float on[3], dn[3];
+    if (NDC) ndc_one(o, d, cw, ch, 1.f, on, dn);
+    const float* __restrict__ px = images + g * 3;
+#pragma unroll
+    for (int i = 0; i < 3; ++i) {
+        rays_o[j * 3 + i] = NDC ? on[i] : o[i];
+        rays_d[j * 3 + i] = NDC ? dn[i] : d[i];
+        viewdirs[j * 3 + i] = d[i] / nrm;
+        target[j * 3 + i] = px[i];
+    }
+    if (ids_out != nullptr) ids_out[j] = g;
+}
+
 // Draw t = draw0 + j of the pixel sampler: pixel g = pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img * hw training pixels,
 // g = (img * H + row) * W + col.  A thread per draw; the cycle walk of perm_at diverges within a wave (~2 trips at worst on
-// average).  Every index is 64-bit.  NDC: viewdirs take the world ray, rays_o / rays_d its ndc_rays image at near plane 1
-// (what train_nerf.device_rays does to the selected rays).
+// average).  Every index is 64-bit.
 template <bool NDC>
 __global__ void r2l_pixel_batch_kernel(const float* __restrict__ images, const float* __restrict__ c2w, int H, int W, float focal,
                                        int64_t M, int half_bits, int64_t draw0, int64_t n_draw, unsigned long long seed,
@@ -172,20 +200,26 @@ __global__ void r2l_pixel_batch_kernel(const float* __restrict__ images, const f
         const int64_t g = (int64_t)perm_at(t - epoch * (unsigned long long)M, (unsigned long long)M, half_bits, k);
         const int64_t img = g / hw, pix = g - img * hw;
         const int row = (int)(pix / W), col = (int)(pix - (int64_t)row * W);
-        float o[3], d[3];
-        pixel_ray(c2w + img * 12, focal, H, W, row, col, o, d);
-        const float nrm = ray_norm(d);
-        float on[3], dn[3];
-        if (NDC) ndc_one(o, d, cw, ch, 1.f, on, dn);
-        const float* __restrict__ px = images + g * 3;
-#pragma unroll
-        for (int i = 0; i < 3; ++i) {
-            rays_o[j * 3 + i] = NDC ? on[i] : o[i];
-            rays_d[j * 3 + i] = NDC ? dn[i] : d[i];
-            viewdirs[j * 3 + i] = d[i] / nrm;
-            target[j * 3 + i] = px[i];
-        }
-        if (ids_out != nullptr) ids_out[j] = g;
+        pixel_row<NDC>(images, c2w, H, W, focal, img, row, col, j, rays_o, rays_d, viewdirs, target, ids_out, cw, ch);
+    }
+}
+
+// Draw j of the images-mode sampler: position q = pi(key, n_win)(j) of the win_h x win_w window at (row0, col0) of image img,
+// row-major (n_win = win_h * win_w, j < n_draw <= n_win: a prefix of a bijection, so the pixels are distinct).  A thread per draw,
+// the same cycle walk and the same body as above.
+template <bool NDC>
+__global__ void r2l_image_batch_kernel(const float* __restrict__ images, const float* __restrict__ c2w, int H, int W, float focal,
+                                       int img, int row0, int col0, int win_w, int64_t n_win, int half_bits, int64_t n_draw,
+                                       unsigned long long key, float* __restrict__ rays_o, float* __restrict__ rays_d,
+                                       float* __restrict__ viewdirs, float* __restrict__ target, int64_t* __restrict__ ids_out,
+                                       float cw, float ch) {
+    unsigned k[4];
+    perm_round_keys(key, k);  // (uniform over the grid: a few dozen integer ops)
+    for (int64_t j = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; j < n_draw; j += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t q = (int64_t)perm_at((unsigned long long)j, (unsigned long long)n_win, half_bits, k);
+        const int wr = (int)(q / win_w), wc = (int)(q - (int64_t)wr * win_w);
+        pixel_row<NDC>(images, c2w, H, W, focal, (int64_t)img, row0 + wr, col0 + wc, j, rays_o, rays_d, viewdirs, target, ids_out, cw,
+                       ch);
     }
 }
 
@@ -344,6 +378,48 @@ extern "C" int r2l_pixel_batch(const float* images, const float* c2w, int n_img,
                            perm_half_bits(M), draw0, n_draw, (unsigned long long)seed, rays_o, rays_d, viewdirs, target, ids_out, 0.f,
                            0.f);
     R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_image_batch(const float* images, const float* c2w, int n_img, int H, int W, float focal, int ndc, int img, int row0,
+                               int col0, int win_h, int win_w, uint64_t key, int64_t n_draw, float* rays_o, float* rays_d,
+                               float* viewdirs, float* target, int64_t* ids_out, void* stream) {
+    R2L_REQUIRE(n_img >= 1 && H >= 1 && W >= 1, "r2l_image_batch: need n_img >= 1, H >= 1 and W >= 1");
+    R2L_REQUIRE(focal > 0.f, "r2l_image_batch: need focal > 0");
+    R2L_REQUIRE(ndc == 0 || ndc == 1, "r2l_image_batch: ndc is 0 or 1");
+    R2L_REQUIRE(n_draw >= 0, "r2l_image_batch: n_draw is negative");
+    const int64_t nh = (int64_t)n_img * H;  // < 2^62; checked before it is multiplied again
+    R2L_REQUIRE(nh <= 0x7fffffff && nh * W <= 0x7fffffff, "r2l_image_batch: need n_img * H * W < 2^31 pixels");
+    R2L_REQUIRE(img >= 0 && img < n_img, "r2l_image_batch: img is outside [0, n_img)");
+    R2L_REQUIRE(win_h >= 1 && win_w >= 1, "r2l_image_batch: need win_h >= 1 and win_w >= 1");
+    R2L_REQUIRE(row0 >= 0 && (int64_t)row0 + win_h <= H, "r2l_image_batch: row0 / win_h: the window leaves the frame");
+    R2L_REQUIRE(col0 >= 0 && (int64_t)col0 + win_w <= W, "r2l_image_batch: col0 / win_w: the window leaves the frame");
+    const int64_t n_win = (int64_t)win_h * win_w;  // <= H * W < 2^31
+    R2L_REQUIRE(n_draw <= n_win, "r2l_image_batch: n_draw exceeds the win_h * win_w pixels of the window");
+    R2L_REQUIRE(images && c2w && rays_o && rays_d && viewdirs && target,
+                "r2l_image_batch: a required pointer is NULL (images, c2w, rays_o, rays_d, viewdirs, target)");
+    if (n_draw == 0) return 0;
+    const hipStream_t st = (hipStream_t)stream;
+    if (ndc)
+        hipLaunchKernelGGL(r2l_image_batch_kernel<true>, dim3(grid_for(n_draw)), dim3(256), 0, st, images, c2w, H, W, focal, img, row0,
+                           col0, win_w, n_win, perm_half_bits(n_win), n_draw, (unsigned long long)key, rays_o, rays_d, viewdirs, target,
+                           ids_out, ndc_coef(W, focal), ndc_coef(H, focal));
+    else
+        hipLaunchKernelGGL(r2l_image_batch_kernel<false>, dim3(grid_for(n_draw)), dim3(256), 0, st, images, c2w, H, W, focal, img, row0,
+                           col0, win_w, n_win, perm_half_bits(n_win), n_draw, (unsigned long long)key, rays_o, rays_d, viewdirs, target,
+                           ids_out, 0.f, 0.f);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// Host arithmetic only: the image and the window key of an iteration (include/r2l_hip.h).
+extern "C" int r2l_image_draw(uint64_t seed, int64_t iteration, int n_img, int* img_out, uint64_t* key_out) {
+    R2L_REQUIRE(iteration >= 1, "r2l_image_draw: need iteration >= 1");
+    R2L_REQUIRE(n_img >= 1, "r2l_image_draw: need n_img >= 1");
+    R2L_REQUIRE(img_out != nullptr && key_out != nullptr, "r2l_image_draw: a required pointer is NULL (img_out, key_out)");
+    const unsigned long long z = perm_epoch_key(seed ^ 0x696D675F6D6F6465ull, (unsigned long long)iteration);
+    *img_out = (int)(((z >> 40) * (unsigned long long)n_img) >> 24);
+    *key_out = perm_epoch_key(z, 0);
     return 0;
 }
 

@@ -78,6 +78,11 @@ FLAGS = {
     # from all training images) through a pixel sampler on the device (r2l_amd/pixel_batch.py, r2l_pixel_batch); opt-in — without
     # the switch utils/train_nerf.py refuses a run without --no_batching as it always did.  main.py / create_data.py ignore it
     "r2l_batching": ("flag", False),
+    # teacher training in images mode (--no_batching: one training image per iteration, N_rand distinct pixels of it, of its centre
+    # crop for precrop_iters) through a pixel sampler on the device (r2l_amd/image_batch.py, r2l_image_batch) instead of
+    # train_nerf.sample_batch on the host: the image and pixel choices are a keyed bijection's, not numpy's; opt-in — without the
+    # switch, and without --no_batching, nothing changes.  main.py / create_data.py ignore it
+    "r2l_image_sampler": ("flag", False),
     # teacher training with one library call per iteration (r2l_teacher_train_step): t_rand, u and the sigma noise are drawn on the
     # device from Philox streams of (R2L_SEED, iteration) instead of torch's generator, and the loop reads the loss only where it
     # prints, tests or ends; opt-in, GPU only.  main.py / create_data.py ignore it

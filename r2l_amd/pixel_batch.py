@@ -58,9 +58,17 @@ def host_batch(images, poses, H, W, focal, ndc, seed, draw0, n_draw):
     are met, a gather at pixel_ids, the view directions of the world d with the kernel's (x^2 + z^2) + y^2 association, and
     ndc_rays at near plane 1 with ndc.  images [n_img,H,W,3], poses [n_img,3|4,4]."""
     images, poses, H, W, focal = _check(images, poses, H, W, focal)
+    return host_rows(images, poses, H, W, focal, ndc, pixel_ids(int(seed) & M64, images.shape[0] * H * W, draw0, n_draw))
+
+
+def host_rows(images, poses, H, W, focal, ndc, ids):
+    """(rays_o, rays_d, viewdirs, target, ids) of the pixels ids (int64, g = (img*H + row)*W + col) on CPU tensors: the per-pixel
+    part of host_batch, shared with the images-mode sampler (r2l_amd/image_batch.py)."""
+    images, poses, H, W, focal = _check(images, poses, H, W, focal)
     images, poses = images.cpu(), poses.cpu()
     hw = H * W
-    ids = torch.from_numpy(pixel_ids(int(seed) & M64, images.shape[0] * hw, draw0, n_draw))
+    ids = torch.from_numpy(np.ascontiguousarray(ids, dtype=np.int64))
+    n_draw = ids.shape[0]
     img, pix = ids // hw, ids % hw
     o, d = torch.empty(n_draw, 3), torch.empty(n_draw, 3)
     for k in torch.unique(img).tolist():

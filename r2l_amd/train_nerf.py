@@ -16,6 +16,12 @@ t_rand, u and the sigma noise of raw_noise_std come from the Philox streams 2^62
 torch's generator, and the loss stays on the device: the host reads it where it prints, tests and ends, never per iteration.  The
 step has no state, so --resume continues bit for bit; batching mode then skips the per-iteration re-seeding (nothing there draws
 from the host generators), images mode keeps it for its numpy pixel choice.
+With --r2l_image_sampler and --no_batching the batch of images mode comes from the device too (r2l_amd/image_batch.py): iteration i
+takes image image_draw(R2L_SEED, i, n_train) and N_rand distinct pixels of its centre crop (i < precrop_iters) or of the whole frame,
+one r2l_image_batch launch in place of sample_batch, device_rays and four copies.  The image and pixel choices are the keyed
+bijection's, not numpy's; the distribution is the reference's.  An N_rand above the crop's (or the frame's) pixel count is refused
+at start-up, where the reference would fail inside numpy at the first iteration.  With --r2l_fused_step no host generator is left
+in the loop, the re-seeding is skipped, and --resume is exact with no sampler state; the staged step keeps it for torch's draws.
 Checkpoints are the reference's layout (checkpoint.save_ckpt, model_name='nerf'): utils/create_data.py --teacher_ckpt and
 main.py --model_name nerf --render_only read them unchanged.
 """
@@ -28,6 +34,7 @@ import torch
 from . import data as D
 from .checkpoint import load_ckpt, save_ckpt
 from .driver import lpips_field, apply_arithmetic, create_nerf_teacher, init_distributed, load_lpips_vgg_weights, load_lpips_weights, render_path
+from .image_batch import ImageBatcher, crop_window, full_window
 from .logger import Logger
 from .options import parse_args, validate_accelerated
 from .pixel_batch import PixelBatcher
@@ -156,6 +163,23 @@ def main(argv=None):
         if args.precrop_iters > 0:
             logger.info("[Config] precrop_iters = %d is ignored: batching mode has no centre crop" % args.precrop_iters)
 
+    sampler = None
+    if args.no_batching and args.r2l_image_sampler:  # (in batching mode the switch changes nothing)
+        crop, frame = crop_window(H, W, args.precrop_frac), full_window(H, W)
+        if start + 1 < args.precrop_iters and args.N_rand > crop[2] * crop[3]:
+            raise ValueError("--r2l_image_sampler: N_rand %d exceeds the %d x %d = %d pixels of the centre crop (precrop_frac %g of "
+                             "%d x %d, until iteration %d): a batch is N_rand DISTINCT pixels of one image; lower N_rand or raise "
+                             "precrop_frac" % (args.N_rand, crop[2], crop[3], crop[2] * crop[3], args.precrop_frac, H, W,
+                                               args.precrop_iters))
+        if args.N_rand > H * W:
+            raise ValueError("--r2l_image_sampler: N_rand %d exceeds the %d x %d = %d pixels of a frame: a batch is N_rand DISTINCT "
+                             "pixels of one image (precrop_frac plays no part here); lower N_rand" % (args.N_rand, H, W, H * W))
+        sampler = ImageBatcher(torch.as_tensor(images[i_train]), poses[i_train], H, W, focal, scene.ndc, device,
+                               seed=int(os.environ.get("R2L_SEED", "0")))
+        logger.info("[Config] Images mode through the device pixel sampler (--r2l_image_sampler): per iteration one r2l_image_batch "
+                    "launch, N_rand %d distinct pixels of one of %s; image and pixels are a pure function of (seed %d, iteration), "
+                    "not numpy's choices" % (args.N_rand, sampler.describe(), sampler.seed))
+
     fused = bool(args.r2l_fused_step)
     if fused:
         seed = int(os.environ.get("R2L_SEED", "0"))
@@ -169,7 +193,7 @@ def main(argv=None):
 
     history, lr, t0 = [], args.lrate, time.time()
     for i in range(start + 1, args.N_iters + 1):
-        if not (fused and batcher is not None):
+        if not (fused and (batcher is not None or sampler is not None)):
             _seed(i)
         lr = lr_schedule(i, args.lrate, args.lrate_decay, args.warmup_lr)
         if batcher is not None:
@@ -177,6 +201,10 @@ def main(argv=None):
             rays_o, rays_d, viewdirs, target = batcher.next(args.N_rand)
             for e in range(-(-a // batcher.M), (batcher.draw - 1) // batcher.M + 1):  # the epochs whose first draw is in this batch
                 logger.info("[TRAIN] Iter %d: epoch %d begins (draw %d)" % (i, e, e * batcher.M))
+        elif sampler is not None:
+            rays_o, rays_d, viewdirs, target = sampler.next(i, args.N_rand, crop if i < args.precrop_iters else frame)
+            if i == start + 1 and i < args.precrop_iters:
+                logger.info("[Config] Center cropping of size %d x %d is enabled until iter %d" % (crop[2], crop[3], args.precrop_iters))
         else:
             rays_o, rays_d, viewdirs, target = sample_batch(i, args, images, poses, i_train, H, W, focal)
             if i == start + 1 and i < args.precrop_iters:
@@ -212,4 +240,4 @@ def main(argv=None):
     if fused:
         history = [tuple(row) for row in loss_hist.tolist()]
     return {"trainer": trainer, "logger": logger, "history": history, "coarse": coarse, "fine": fine,
-            "r2l_config": r2l_config, "batcher": batcher}
+            "r2l_config": r2l_config, "batcher": batcher, "image_sampler": sampler}

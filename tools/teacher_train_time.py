@@ -21,7 +21,14 @@ Wall-clock ms (time.perf_counter) around synchronised work; one line per scene t
 The staged step (TeacherTrainer.step: ~25 library calls and torch ops, the loss read back every step) against the fused step
 (TeacherTrainer.fused_step: one library call, nothing read back until the end) in the same process, on a fixed batch, at 1024 rays
 (kernel-bound) and at 64 rays (where the host's share should show), 64 + 128 samples, perturb 1.  Wall-clock ms per step over
---steps steps, --repeats times each, alternating: the spread of a path's repeats is what a difference has to exceed."""
+--steps steps, --repeats times each, alternating: the spread of a path's repeats is what a difference has to exceed.
+
+  python tools/teacher_train_time.py --images [--steps 20] [--warmup 3] [--repeats 3] [--out profiles/teacher_image_sampler.txt]
+
+Images mode's batch from the host (train_nerf._seed + sample_batch + device_rays + two copies, what the loop does without the
+switch) against ImageBatcher.next (--r2l_image_sampler), at 400 x 400 (100 views) and 800 x 800 (25 views), N_rand 1024: ms per
+batch (whole frame and centre crop; PixelBatcher.next beside it), and ms per whole iteration with the staged and the fused step,
+with and without the switch.  One process, --repeats rounds alternating the paths; [median, max - min] per path."""
 import argparse
 import json
 import os
@@ -172,6 +179,88 @@ def fused(a):
             f.write("\n".join(lines) + "\n")
 
 
+def images(a):
+    from r2l_amd import train_nerf
+    from r2l_amd.image_batch import ImageBatcher, crop_window
+    from r2l_amd.pixel_batch import PixelBatcher
+    from r2l_amd.teacher_train import TeacherTrainer
+    dev = torch.device("cuda")
+    csd, fsd = O.make_teacher_state_dicts(5, 2, alpha_bias=0.5)
+    rng = np.random.RandomState(0)
+    N_rand, near, far = 1024, 2., 6.
+    lines = ["teacher training in images mode, the batch of an iteration: host path (train_nerf: _seed + sample_batch + device_rays + "
+             "the copies of viewdirs and target) against ImageBatcher.next (--r2l_image_sampler, one r2l_image_batch launch); N_rand "
+             "%d, 64 + 128 samples, perturb 1; %s; steps %d, warmup %d, %d rounds alternating the paths in one process; wall-clock "
+             "ms, [median, max - min] over the rounds" % (N_rand, torch.cuda.get_device_name(0), a.steps, a.warmup, a.repeats)]
+    for n, H, W, focal in ((100, 400, 400, 555.5555155968841), (25, 800, 800, 1111.1110311937682)):
+        imgs = rng.rand(n, H, W, 3).astype(np.float32)
+        poses = np.stack([O.pose_spherical(-180. + 360. * k / n, -30., 4.)[:3, :4] for k in range(n)]).astype(np.float32)
+        i_train = np.arange(n)
+        tr = TeacherTrainer(make(csd), make(fsd), N_samples=64, N_importance=128, perturb=1., white_bkgd=True, raw_noise_std=0.)
+        ib = ImageBatcher(imgs, poses, H, W, focal, False, dev, seed=0)
+        pb = PixelBatcher(imgs, poses, H, W, focal, False, dev, seed=0)
+        crop = crop_window(H, W, .5)
+        hist = torch.zeros(a.warmup + a.steps, 2, device="cuda")
+        it = [0]
+
+        def host(precrop_iters=0, seed=True):
+            it[0] += 1
+            if seed:
+                train_nerf._seed(it[0])
+            args = argparse.Namespace(N_rand=N_rand, precrop_iters=precrop_iters, precrop_frac=.5)
+            o, d, v, t = train_nerf.sample_batch(it[0], args, imgs, poses, i_train, H, W, focal)
+            o, d = train_nerf.device_rays(o, d, H, W, focal, False, dev)
+            return o, d, v.to(dev), t.to(dev)
+
+        def device(window=None, seed=False):
+            it[0] += 1
+            if seed:  # (the staged step keeps the per-iteration re-seeding for torch's t_rand / u)
+                train_nerf._seed(it[0])
+            return ib.next(it[0], N_rand, window)
+
+        def staged(batch):
+            o, d, v, t = batch()
+            tr.step(o, d, v, near, far, t, 5e-4)  # (reads the loss back: synchronised)
+
+        def fused_(batch):
+            o, d, v, t = batch()
+            tr.fused_step(o, d, v, near, far, t, 5e-4, step=it[0], seed=0, loss_out=hist[it[0] % hist.shape[0]])
+
+        paths = [
+            ("batch_host_ms", lambda: host(), True),
+            ("batch_sampler_ms", lambda: device(), True),
+            ("batch_host_crop_ms", lambda: host(precrop_iters=1 << 30), True),
+            ("batch_sampler_crop_ms", lambda: device(crop), True),
+            ("batch_sampler_back_to_back_ms", lambda: device(), False),
+            ("batch_pixel_batcher_ms", lambda: pb.next(N_rand), True),
+            ("batch_pixel_batcher_back_to_back_ms", lambda: pb.next(N_rand), False),
+            ("iter_staged_host_ms", lambda: staged(host), True),
+            ("iter_staged_sampler_ms", lambda: staged(lambda: device(seed=True)), True),
+            ("iter_fused_host_ms", lambda: fused_(host), False),
+            ("iter_fused_sampler_ms", lambda: fused_(device), False),
+        ]
+        got = {name: [] for name, _, _ in paths}
+        for _ in range(a.repeats):
+            for name, fn, sync_each in paths:
+                it[0] = 0
+                got[name].append(wall(fn, a.steps, a.warmup, sync_each=sync_each))
+                hist.tolist()
+        r = {"views": n, "H": H, "W": W, "N_rand": N_rand, "bank_MB": round(ib.nbytes / 1e6, 1)}
+        for name, _, _ in paths:
+            r[name] = [round(float(np.median(got[name])), 3), round(max(got[name]) - min(got[name]), 3)]
+        for kind in ("staged", "fused"):
+            h, s = r["iter_%s_host_ms" % kind], r["iter_%s_sampler_ms" % kind]
+            r["iter_%s_sampler_minus_host_ms" % kind] = round(s[0] - h[0], 3)
+            r["iter_%s_sampler_not_slower" % kind] = bool(s[0] - h[0] <= max(h[1], s[1]))
+        lines.append(json.dumps(r))
+        print(lines[-1], flush=True)
+        del tr, ib, pb, imgs
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
@@ -180,13 +269,18 @@ def main():
     ap.add_argument("--no_baseline", action="store_true")
     ap.add_argument("--batching", action="store_true", help="time the data path: images mode's host path against PixelBatcher.next")
     ap.add_argument("--fused", action="store_true", help="time the staged step against the fused step (r2l_teacher_train_step)")
-    ap.add_argument("--repeats", type=int, default=3, help="--fused: timed runs per path")
-    ap.add_argument("--out", default=None, help="where --batching / --fused write their lines (default: profiles/teacher_batching.txt "
-                    "/ profiles/teacher_fused_step.txt)")
+    ap.add_argument("--images", action="store_true", help="time images mode's host path against ImageBatcher.next (--r2l_image_sampler), "
+                    "per batch and per whole iteration, staged and fused")
+    ap.add_argument("--repeats", type=int, default=3, help="--fused / --images: timed runs per path")
+    ap.add_argument("--out", default=None, help="where --batching / --fused / --images write their lines (default: "
+                    "profiles/teacher_batching.txt / profiles/teacher_fused_step.txt / profiles/teacher_image_sampler.txt)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "teacher_train_time needs the GPU"
     if a.out is None:
-        a.out = os.path.join("profiles", "teacher_fused_step.txt" if a.fused else "teacher_batching.txt")
+        a.out = os.path.join("profiles", "teacher_image_sampler.txt" if a.images else
+                             "teacher_fused_step.txt" if a.fused else "teacher_batching.txt")
+    if a.images:
+        return images(a)
     if a.fused:
         return fused(a)
     if a.batching:
