@@ -233,6 +233,17 @@ def load():
     return lib
 
 
+def ptr(t):
+    """The address of a tensor's data as a c_void_p; None (a null pointer argument) for None."""
+    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+
+
+def stream(device=None):
+    """The current stream of `device` (None: of the current device) as a c_void_p."""
+    import torch
+    return ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)
+
+
 def check(code, what):
     if code != 0:
         msg = load().r2l_last_error()

@@ -5,7 +5,8 @@ autograd).  The build's own training loop does not go through autograd (r2l_amd/
 import torch
 
 from . import _lib
-from .engine import _ptr, _stream, get_engine
+from ._lib import ptr as _ptr, stream as _stream
+from .engine import get_engine
 
 
 class R2LEmbFunction(torch.autograd.Function):

@@ -88,8 +88,7 @@ class HardRayPool:
             ix = torch.empty(n_out, dtype=torch.int64, device=device)
             self._draws += 1
             key = self._key(self._draws)
-            _lib.check(lib.r2l_pool_pick(ctypes.c_void_p(ix.data_ptr()), n_out, n_rows, key,
-                                         ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "r2l_pool_pick")
+            _lib.check(lib.r2l_pool_pick(_lib.ptr(ix), n_out, n_rows, key, _lib.stream()), "r2l_pool_pick")
             return ix
         return torch.as_tensor(self.rng.permutation(n_rows)[:n_out], device=device)
 
@@ -153,10 +152,9 @@ class HardRayPool:
             lib, B = _lib.load(), rays_o.shape[0]
             (o, so), (d, sd), (t, st) = self._rows(rays_o), self._rows(rays_d), self._rows(target)
             out = torch.empty(3, B + n_out, 3, dtype=torch.float32, device=self.pool.device)
-            p = lambda x: ctypes.c_void_p(x.data_ptr())
+            p = _lib.ptr
             _lib.check(lib.r2l_pool_augment(p(o), p(d), p(t), so, sd, st, p(self.pool), p(self._ix_out), B, n_out, p(out[0]),
-                                            p(out[1]), p(out[2]), ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)),
-                       "r2l_pool_augment")
+                                            p(out[1]), p(out[2]), _lib.stream()), "r2l_pool_augment")
             return out[0], out[1], out[2]
         picked = self.pool[self._ix_out]
         return (torch.cat([rays_o, picked[:, :3]], 0), torch.cat([rays_d, picked[:, 3:6]], 0),
@@ -224,9 +222,9 @@ class HardRayPool:
             (o, so), (d, sd), (t, st) = self._rows(rays_o), self._rows(rays_d), self._rows(target)
             hard = hard.contiguous()
             dst = self._ix_out[:n_in].contiguous() if self.full else None
-            p = lambda x: ctypes.c_void_p(x.data_ptr()) if x is not None else None
+            p = _lib.ptr
             _lib.check(lib.r2l_pool_store(p(o), p(d), p(t), so, sd, st, p(hard), p(self._store), p(dst), 0 if self.full else self._n,
-                                          n_in, ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "r2l_pool_store")
+                                          n_in, _lib.stream()), "r2l_pool_store")
             if self.full:
                 return
         else:
@@ -716,6 +714,96 @@ def lpips_field(misc):
 
 
 # ---------------------------------------------------------------------------------------------------------------
+def open_training_source(args, scene, H, W, focal, near, far, shards, start, rank, world, device, logger):
+    """The source of this rank's training batches, as the options say: a store the teacher fills (--r2l_online_kd, plain or
+    --r2l_compact_store), a store file (--r2l_store_load), a store the shard files are read into once (--r2l_device_store), or
+    the reader of the shard files.  shards: shard files per step of every rank; start: the iteration a resumed run starts
+    behind.  Returns (loader, files, filler): files — the names the run counts as its training files; filler — the
+    online_kd.TeacherFill while poses are still pending, else None."""
+    filler = None  # --r2l_online_kd: the teacher fill of the store (online_kd.TeacherFill), while poses are pending
+    if args.r2l_online_kd:
+        # no shard files: the teacher renders this rank's poses into a device-resident store (r2l_amd/online_kd.py), all of
+        # them before iteration 1 or — --r2l_kd_every K — the first flush group now and one more every K iterations (the
+        # reference's data arriving during training, --i_update_data, main.py:1218-1259, without the files).  The sampler
+        # draws with the shard count of the moment.
+        from .online_kd import TeacherFill, shards_needed
+        from .options import parse_teacher_config
+        from .raystore import RayStore
+        targs = parse_teacher_config(args.r2l_teacher_config, teacher_ckpt=args.teacher_ckpt)
+        targs.r2l_precision = args.r2l_precision  # one arithmetic switch per run: the teacher kernels follow the command line
+        n_pose = args.n_pose_kd if isinstance(args.n_pose_kd, int) else int(args.n_pose_kd[0])
+        cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
+        if cap < 1:
+            raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
+        if args.r2l_compact_store:
+            # 16 bytes a ray: rgb and the ray's number in its flush group; o, d are recomputed per draw from the group's poses
+            # (one pose-table slot per pose of this rank) and the batches are the plain store's bit for bit
+            from .online_kd import rank_poses
+            from .raystore import CompactRayStore
+            loader = CompactRayStore(cap, len(rank_poses(n_pose, rank, world)), H, W, device, seed=9973 * rank, logger=logger)
+        else:
+            loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
+        filler = TeacherFill(loader, targs, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
+                             rand_pose=scene.rand_pose, ndc=scene.ndc)
+        # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
+        # number, so these are the same rows bit for bit
+        n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
+        while not filler.done and (n_groups is None or filler.groups < n_groups):
+            filler.fill_group()
+        files = loader.files
+        if args.r2l_store_save:  # (--r2l_kd_every 0, checked at start-up: the fill is complete) render once, train many times
+            from .raystore import store_rank_path
+            loader.save(store_rank_path(args.r2l_store_save, rank, world), provenance=filler.provenance(), rank=rank, world=world)
+        if filler.done:
+            filler = None
+    elif args.r2l_store_load:
+        # the store a run with --r2l_store_save (or utils/create_data.py) wrote: plain or compact as the file says, its digests
+        # recomputed on the device before a row of it is trained on
+        from .raystore import load_store, read_store_header, store_rank_path
+        path = store_rank_path(args.r2l_store_load, rank, world)
+        hdr = read_store_header(path)
+        if (hdr["rank"], hdr["world"]) != (rank, world):
+            raise ValueError("--r2l_store_load %s: written by rank %d of %d, this is rank %d of %d" %
+                             (path, hdr["rank"], hdr["world"], rank, world))
+        if hdr["kind"] == 1 and (hdr["H"], hdr["W"]) != (H, W):
+            raise ValueError("--r2l_store_load %s: a compact store of %d x %d frames, the scene is %d x %d" %
+                             (path, hdr["H"], hdr["W"], H, W))
+        if hdr["n_shards"] < shards[rank]:
+            raise ValueError("--r2l_store_load %s: %d shards, one step of this rank draws %d (--N_rand %d over %d ranks)" %
+                             (path, hdr["n_shards"], shards[rank], args.N_rand, world))
+        if hdr["kind"] == 1 and args.r2l_fused_iter:
+            raise ValueError("--r2l_store_load %s: a compact store hands out batches through its own kernel: not with "
+                             "--r2l_fused_iter, which reads the 36-byte rows of the plain store" % path)
+        logger.info("ray store file %s: provenance %s" % (path, json.dumps(hdr["provenance"], sort_keys=True)))
+        loader = load_store(path, device, seed=9973 * rank, logger=logger)
+        files = loader.files
+    elif args.r2l_device_store:
+        # the shard files are read ONCE into device memory; no reader threads, no per-step host-to-device copy
+        from .raystore import RayStore
+        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
+        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
+        mine = D.shard_for_rank(files, rank, world)
+        if not mine:
+            raise ValueError("rank %d got no ray shards (have %d files, world %d)" % (rank, len(files), world))
+        rows, cols = ctypes.c_int64(), ctypes.c_int64()
+        from . import _lib
+        _lib.check(_lib.load().r2l_npy_shape(mine[0].encode(), ctypes.byref(rows), ctypes.byref(cols)), "r2l_npy_shape")
+        loader = RayStore(len(mine), device, rays_per_shard=rows.value, seed=9973 * rank, logger=logger)
+        loader.append_files(mine, threads=max(1, min(args.num_workers, 16)))
+    else:
+        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
+        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
+        loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
+                                  threads=max(1, min(args.num_workers, 16)))
+    if args.r2l_online_kd or args.r2l_device_store or args.r2l_store_load:
+        loader.n_files = shards[rank]
+        logger.info("ray store: %s" % loader.describe())
+        if start > 0:  # --resume: the sampler is a pure function of (seed, shard count, draw): only the counter is restored
+            loader.seek(start * shards[rank])
+            logger.info("ray store: resuming at draw %d (start iteration %d x %d shards per step)" % (loader.draw, start, shards[rank]))
+    return loader, files, filler
+
+
 def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
@@ -839,87 +927,7 @@ def main(argv=None):
         shards = split_shards(args.N_rand, world)
     except ValueError as e:
         raise SystemExit(str(e))
-    filler = None  # --r2l_online_kd: the teacher fill of the store (online_kd.TeacherFill), while poses are pending
-    if args.r2l_online_kd:
-        # no shard files: the teacher renders this rank's poses into a device-resident store (r2l_amd/online_kd.py), all of
-        # them before iteration 1 or — --r2l_kd_every K — the first flush group now and one more every K iterations (the
-        # reference's data arriving during training, --i_update_data, main.py:1218-1259, without the files).  The sampler
-        # draws with the shard count of the moment.
-        from .online_kd import TeacherFill, shards_needed
-        from .options import parse_teacher_config
-        from .raystore import RayStore
-        targs = parse_teacher_config(args.r2l_teacher_config, teacher_ckpt=args.teacher_ckpt)
-        targs.r2l_precision = args.r2l_precision  # one arithmetic switch per run: the teacher kernels follow the command line
-        n_pose = args.n_pose_kd if isinstance(args.n_pose_kd, int) else int(args.n_pose_kd[0])
-        cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
-        if cap < 1:
-            raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
-        if args.r2l_compact_store:
-            # 16 bytes a ray: rgb and the ray's number in its flush group; o, d are recomputed per draw from the group's poses
-            # (one pose-table slot per pose of this rank) and the batches are the plain store's bit for bit
-            from .online_kd import rank_poses
-            from .raystore import CompactRayStore
-            loader = CompactRayStore(cap, len(rank_poses(n_pose, rank, world)), H, W, device, seed=9973 * rank, logger=logger)
-        else:
-            loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
-        filler = TeacherFill(loader, targs, H, W, float(hwf[2]), near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                             rand_pose=scene.rand_pose, ndc=scene.ndc)
-        # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
-        # number, so these are the same rows bit for bit
-        n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
-        while not filler.done and (n_groups is None or filler.groups < n_groups):
-            filler.fill_group()
-        files = loader.files
-        if args.r2l_store_save:  # (--r2l_kd_every 0, checked at start-up: the fill is complete) render once, train many times
-            from .raystore import store_rank_path
-            loader.save(store_rank_path(args.r2l_store_save, rank, world), provenance=filler.provenance(), rank=rank, world=world)
-        if filler.done:
-            filler = None
-    elif args.r2l_store_load:
-        # the store a run with --r2l_store_save (or utils/create_data.py) wrote: plain or compact as the file says, its digests
-        # recomputed on the device before a row of it is trained on
-        from .raystore import load_store, read_store_header, store_rank_path
-        path = store_rank_path(args.r2l_store_load, rank, world)
-        hdr = read_store_header(path)
-        if (hdr["rank"], hdr["world"]) != (rank, world):
-            raise ValueError("--r2l_store_load %s: written by rank %d of %d, this is rank %d of %d" %
-                             (path, hdr["rank"], hdr["world"], rank, world))
-        if hdr["kind"] == 1 and (hdr["H"], hdr["W"]) != (H, W):
-            raise ValueError("--r2l_store_load %s: a compact store of %d x %d frames, the scene is %d x %d" %
-                             (path, hdr["H"], hdr["W"], H, W))
-        if hdr["n_shards"] < shards[rank]:
-            raise ValueError("--r2l_store_load %s: %d shards, one step of this rank draws %d (--N_rand %d over %d ranks)" %
-                             (path, hdr["n_shards"], shards[rank], args.N_rand, world))
-        if hdr["kind"] == 1 and args.r2l_fused_iter:
-            raise ValueError("--r2l_store_load %s: a compact store hands out batches through its own kernel: not with "
-                             "--r2l_fused_iter, which reads the 36-byte rows of the plain store" % path)
-        logger.info("ray store file %s: provenance %s" % (path, json.dumps(hdr["provenance"], sort_keys=True)))
-        loader = load_store(path, device, seed=9973 * rank, logger=logger)
-        files = loader.files
-    elif args.r2l_device_store:
-        # the shard files are read ONCE into device memory; no reader threads, no per-step host-to-device copy
-        from .raystore import RayStore
-        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
-        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
-        mine = D.shard_for_rank(files, rank, world)
-        if not mine:
-            raise ValueError("rank %d got no ray shards (have %d files, world %d)" % (rank, len(files), world))
-        rows, cols = ctypes.c_int64(), ctypes.c_int64()
-        from . import _lib
-        _lib.check(_lib.load().r2l_npy_shape(mine[0].encode(), ctypes.byref(rows), ctypes.byref(cols)), "r2l_npy_shape")
-        loader = RayStore(len(mine), device, rays_per_shard=rows.value, seed=9973 * rank, logger=logger)
-        loader.append_files(mine, threads=max(1, min(args.num_workers, 16)))
-    else:
-        datadir_kd = args.datadir_kd.split(":")[1] if ":" in args.datadir_kd else args.datadir_kd
-        files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
-        loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
-                                  threads=max(1, min(args.num_workers, 16)))
-    if args.r2l_online_kd or args.r2l_device_store or args.r2l_store_load:
-        loader.n_files = shards[rank]
-        logger.info("ray store: %s" % loader.describe())
-        if start > 0:  # --resume: the sampler is a pure function of (seed, shard count, draw): only the counter is restored
-            loader.seek(start * shards[rank])
-            logger.info("ray store: resuming at draw %d (start iteration %d x %d shards per step)" % (loader.draw, start, shards[rank]))
+    loader, files, filler = open_training_source(args, scene, H, W, float(hwf[2]), near, far, shards, start, rank, world, device, logger)
     uneven = len(set(shards)) > 1
     if uneven:
         logger.info("--N_rand %d over %d ranks: %s shard files per rank and step; gradients weighted by ray share" %

@@ -10,6 +10,7 @@ import ctypes
 import torch
 
 from . import _lib
+from ._lib import ptr as _ptr, stream as _stream  # (tests and tools import the two from here)
 
 W = 256
 N_SAMPLE = 16
@@ -56,14 +57,6 @@ def arithmetic(cfg=None):
     else:
         dw = "exact" if on("R2L_DW_EXACT") else "fp16"
     return {"precision": prec, "dw_mode": dw}
-
-
-def _ptr(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else ctypes.c_void_p(0)
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
 
 
 def supported_reason(module):

@@ -15,14 +15,11 @@ nothing to seek on a resume.
 window_ids() and host_batch() restate in numpy / torch what the kernel computes; they are the specification the tests hold it to,
 and the CPU path of the training loop.
 """
-import ctypes
-
 import numpy as np
-import torch
 
-from . import raystore
-from .pixel_batch import _check, _p, host_rows
-from .raystore import M64
+from . import _lib
+from .keyed_perm import M64, epoch_key, perm_at
+from .pixel_batch import PixelSource, _check, host_rows
 
 DRAW_SALT = 0x696D675F6D6F6465  # "img_mode"
 
@@ -32,8 +29,8 @@ def image_draw(seed, i, n_img):
     i, n_img = int(i), int(n_img)
     if i < 1 or n_img < 1:
         raise ValueError("image_draw: need iteration >= 1 and n_img >= 1, got %d and %d" % (i, n_img))
-    z = raystore.epoch_key((int(seed) & M64) ^ DRAW_SALT, i)
-    return ((z >> 40) * n_img) >> 24, raystore.epoch_key(z, 0)
+    z = epoch_key((int(seed) & M64) ^ DRAW_SALT, i)
+    return ((z >> 40) * n_img) >> 24, epoch_key(z, 0)
 
 
 def crop_window(H, W, frac):
@@ -61,7 +58,7 @@ def window_ids(H, W, img, window, key, n_draw):
     """Pixel ids of the draws 0 .. n_draw - 1 (what r2l_image_batch writes to ids_out): int64[n_draw], (img*H + row)*W + col."""
     n_draw = int(n_draw)
     row0, col0, win_h, win_w = _check_window(H, W, window, n_draw)
-    q = raystore.perm_at(int(key) & M64, win_h * win_w, np.arange(n_draw, dtype=np.uint64))
+    q = perm_at(int(key) & M64, win_h * win_w, np.arange(n_draw, dtype=np.uint64))
     return (int(img) * H + row0 + q // win_w) * W + col0 + q % win_w
 
 
@@ -73,57 +70,33 @@ def host_batch(images, poses, H, W, focal, ndc, img, window, key, n_draw):
     return host_rows(images, poses, H, W, focal, ndc, window_ids(H, W, img, window, key, n_draw))
 
 
-class ImageBatcher:
+class ImageBatcher(PixelSource):
     """The training images and poses, and next(i, n, window): the (rays_o, rays_d, viewdirs, target) of iteration i, each [n, 3] —
     n distinct pixels of the window (row0, col0, win_h, win_w; None = the whole frame) of image image_draw(seed, i, n_img).
 
     On a ROCm device the images [n_img,H,W,3] (fp32, after Scene.rgb_images) and poses are uploaded once and a batch is one
     r2l_image_batch launch on the CURRENT stream into one of two alternating sets of output buffers: the tensors handed out stay
     valid until the second-next call, and nothing synchronises (PixelBatcher's contract).  On the CPU next() answers from
-    host_batch.  next() is a pure function of (seed, i): there is no draw counter.  last_ids holds the pixel ids of the last batch
-    (int64), last_img its image."""
+    host_rows at window_ids.  next() is a pure function of (seed, i): there is no draw counter.  last_ids holds the pixel ids of
+    the last batch (int64), last_img its image."""
 
-    def __init__(self, images, poses, H, W, focal, ndc, device, seed=0):
-        images, poses, self.H, self.W, self.focal = _check(images, poses, H, W, focal)
-        self.device = torch.device(device)
-        self.ndc, self.seed = int(bool(ndc)), int(seed) & M64
-        self.n_img = images.shape[0]
-        self.nbytes = self.n_img * self.H * self.W * 12 + self.n_img * 48
-        self.last_ids = self.last_img = None
-        self._buf, self._k = [None, None], 0
-        if self.device.type == "cuda":
-            from . import _lib
-            if self.device.index is None:
-                self.device = torch.device("cuda", torch.cuda.current_device())
-            free, _total = torch.cuda.mem_get_info(self.device)
-            if self.nbytes > 0.8 * free:
-                raise MemoryError("ImageBatcher: %d images of %d x %d need %.2f GB, more than 80 %% of the %.2f GB free on %s" %
-                                  (self.n_img, self.H, self.W, self.nbytes / 1e9, free / 1e9, self.device))
-            self._lib, self._L = _lib, _lib.load()
-        self.images = images.to(self.device).contiguous()
-        self.poses = poses.to(self.device).contiguous()
+    last_img = None
 
     def describe(self):
         return "%d images %d x %d, %.3f GB on %s" % (self.n_img, self.H, self.W, self.nbytes / 1e9, self.device)
 
-    def next(self, i, n, window=None):
+    def _draw(self, i, n, window=None):
         n = int(n)
         window = _check_window(self.H, self.W, full_window(self.H, self.W) if window is None else window, n)
-        img, key = image_draw(self.seed, i, self.n_img)
-        if self.device.type != "cuda":
-            o, d, v, t, ids = host_batch(self.images, self.poses, self.H, self.W, self.focal, self.ndc, img, window, key, n)
-        else:
-            k = self._k
-            if self._buf[k] is None or self._buf[k][0].shape[0] != n:
-                # (new tensors: the ones handed out two calls ago stay the caller's; the allocator is stream-ordered)
-                self._buf[k] = tuple(torch.empty(n, 3, dtype=torch.float32, device=self.device) for _ in range(4)) + (
-                    torch.empty(n, dtype=torch.int64, device=self.device),)
-            o, d, v, t, ids = self._buf[k]
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            with torch.cuda.device(self.device):
-                self._lib.check(self._L.r2l_image_batch(_p(self.images), _p(self.poses), self.n_img, self.H, self.W, self.focal,
-                                                        self.ndc, img, window[0], window[1], window[2], window[3], key, n, _p(o),
-                                                        _p(d), _p(v), _p(t), _p(ids), stream), "r2l_image_batch")
-            self._k ^= 1
-        self.last_ids, self.last_img = ids, img
-        return o, d, v, t
+        return n, image_draw(self.seed, i, self.n_img) + (window,)
+
+    def _ids(self, n, which):
+        img, key, window = which
+        return window_ids(self.H, self.W, img, window, key, n)
+
+    def _launch(self, n, which, out, st):
+        img, key, window = which
+        _lib.check(self._L.r2l_image_batch(*self._frames, img, *window, key, n, *out, st), "r2l_image_batch")
+
+    def _drawn(self, n, which):
+        self.last_img = which[0]

@@ -1,6 +1,5 @@
 """Small numeric helpers shared by the drivers (reference: utils/run_nerf_raybased_helpers.py:14-20) and the
 test-set SSIM (utils/ssim_torch.py) and FLIP (utils/flip_loss.py)."""
-import ctypes
 import math
 
 import numpy as np
@@ -54,7 +53,7 @@ def ssim(img, ref):
         partial = torch.empty(L.r2l_ssim_partial_count(H, W, C), device=a.device)
         out = torch.empty(1, device=a.device)
         _lib.check(L.r2l_ssim(a.data_ptr(), b.data_ptr(), H, W, C, win.data_ptr(), partial.data_ptr(), out.data_ptr(),
-                              ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_ssim")
+                              _lib.stream(a.device)), "r2l_ssim")
         return out[0]
     import torch.nn.functional as F
     a, b = img.float().permute(2, 0, 1)[None], ref.float().permute(2, 0, 1)[None]
@@ -178,7 +177,7 @@ def flip(img, ref, pixels_per_degree=None, rescale=None, return_map=False):
         assert ext is None or ext.numel() == 4
         _lib.check(L.r2l_flip(a.data_ptr(), b.data_ptr(), K, H, W, ppd, ext.data_ptr() if ext is not None else None,
                               partial.data_ptr(), fmap.data_ptr() if return_map else None, out.data_ptr(),
-                              ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_flip")
+                              _lib.stream(a.device)), "r2l_flip")
     else:
         a, b = (img[None], ref[None]) if single else (img, ref)
         a, b = (a, b.to(a.dtype)) if a.dtype == torch.float64 else (a.float(), b.float())
@@ -317,7 +316,7 @@ def _lpips_stream(L, params, device):
     flat = params.detach().to(device).float().contiguous()
     wpack = torch.empty(L.r2l_lpips_pack_floats(), device=device)
     from . import _lib
-    _lib.check(L.r2l_lpips_pack(flat.data_ptr(), wpack.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+    _lib.check(L.r2l_lpips_pack(flat.data_ptr(), wpack.data_ptr(), _lib.stream(device)),
                "r2l_lpips_pack")
     while len(_LPIPS_PACKED) >= 4:
         _LPIPS_PACKED.pop(next(iter(_LPIPS_PACKED)))
@@ -355,7 +354,7 @@ def lpips(img, ref, params, rescale=None, normalize=False, return_layers=False, 
         _lib.check(L.r2l_lpips(a.data_ptr(), b.data_ptr(), K, H, W, ext.data_ptr() if ext is not None else None, wpack.data_ptr(),
                                work.data_ptr(), layers.data_ptr() if return_layers else None,
                                flat.data_ptr() if return_maps else None, out.data_ptr(),
-                               ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_lpips")
+                               _lib.stream(a.device)), "r2l_lpips")
         maps, o = [], 0
         for ho, wo in (lpips_sizes(H, W) if return_maps else ()):
             maps.append(flat[:, o:o + ho * wo].view(K, ho, wo))
@@ -506,7 +505,7 @@ def _lpips_vgg_stream(L, params, device):
     flat = params.detach().to(device).float().contiguous()
     wpack = torch.empty(L.r2l_lpips_vgg_pack_floats(), device=device)
     from . import _lib
-    _lib.check(L.r2l_lpips_vgg_pack(flat.data_ptr(), wpack.data_ptr(), ctypes.c_void_p(torch.cuda.current_stream(device).cuda_stream)),
+    _lib.check(L.r2l_lpips_vgg_pack(flat.data_ptr(), wpack.data_ptr(), _lib.stream(device)),
                "r2l_lpips_vgg_pack")
     while len(_LPIPS_VGG_PACKED) >= 4:
         _LPIPS_VGG_PACKED.pop(next(iter(_LPIPS_VGG_PACKED)))
@@ -544,7 +543,7 @@ def lpips_vgg(img, ref, params, rescale=None, normalize=False, return_layers=Fal
         _lib.check(L.r2l_lpips_vgg(a.data_ptr(), b.data_ptr(), K, H, W, ext.data_ptr() if ext is not None else None,
                                    wpack.data_ptr(), work.data_ptr(), layers.data_ptr() if return_layers else None,
                                    flat.data_ptr() if return_maps else None, out.data_ptr(),
-                                   ctypes.c_void_p(torch.cuda.current_stream(a.device).cuda_stream)), "r2l_lpips_vgg")
+                                   _lib.stream(a.device)), "r2l_lpips_vgg")
         maps, o = [], 0
         for ho, wo in (lpips_vgg_sizes(H, W) if return_maps else ()):
             maps.append(flat[:, o:o + ho * wo].view(K, ho, wo))

@@ -6,19 +6,20 @@ computed when it is drawn: with M = n_img*H*W, draw t takes pixel
 
     g = perm(epoch_key(seed, t // M), M)[t % M],        g = (img*H + row)*W + col
 
-— the ray store's sampler (r2l_amd/raystore.py) on pixels: a fresh permutation per epoch, without replacement inside one, a pure
-function of (seed, M, t).  There is no bank of rays and no sampler state; a resumed run seeks to its draw number.
+— the ray store's sampler (draw_ids of r2l_amd/keyed_perm.py) on pixels: a fresh permutation per epoch, without replacement
+inside one, a pure function of (seed, M, t).  There is no bank of rays and no sampler state; a resumed run seeks to its draw
+number.
 
 pixel_ids() and host_batch() restate in numpy / torch what the kernel computes; they are the specification the tests hold it to,
 and the CPU path of the training loop.
 """
-import ctypes
-
 import numpy as np
 import torch
 
-from . import raystore
-from .raystore import M64
+from . import _lib
+from ._lib import ptr, stream
+from .device_source import DeviceSource, DrawCounter
+from .keyed_perm import M64, draw_ids
 from .render import get_rays, ndc_rays
 
 M_MAX = 2**31 - 1
@@ -26,14 +27,7 @@ M_MAX = 2**31 - 1
 
 def pixel_ids(seed, M, draw0, n_draw):
     """Pixel ids of the draws draw0 .. draw0 + n_draw - 1 (what r2l_pixel_batch writes to ids_out): int64[n_draw]."""
-    out = np.empty(n_draw, dtype=np.int64)
-    t, j = int(draw0), 0
-    while j < n_draw:
-        e, r = divmod(t, M)
-        n = min(M - r, n_draw - j)
-        out[j:j + n] = raystore.perm_at(raystore.epoch_key(seed, e), M, np.arange(r, r + n, dtype=np.uint64))
-        t, j = t + n, j + n
-    return out
+    return draw_ids(seed, M, draw0, n_draw)
 
 
 def _check(images, poses, H, W, focal):
@@ -86,39 +80,51 @@ def host_rows(images, poses, H, W, focal, ndc, ids):
     return o, d, viewdirs, target, ids
 
 
-def _p(t):
-    return ctypes.c_void_p(t.data_ptr()) if t is not None else None
+class PixelSource(DeviceSource):
+    """What the pixel samplers of batching and images mode share: the training images [n_img,H,W,3] (fp32, after Scene.rgb_images)
+    and poses, uploaded once, and next(): the (rays_o, rays_d, viewdirs, target) of a batch, each [n, 3], pixel ids in last_ids
+    (int64).  On a ROCm device a batch is one launch on the CURRENT stream into one of two alternating sets of output buffers:
+    the tensors handed out stay valid until the second-next call, and nothing synchronises (RayStore.next's contract).  On the
+    CPU next() answers from host_rows.
+
+    A class supplies _draw(its own arguments of next) -> (n, which draws), _ids(n, which) — their pixel ids, for the CPU —
+    _launch(n, which, pointers of (o, d, v, t, ids), stream), _drawn(n, which) and describe()."""
+
+    def __init__(self, images, poses, H, W, focal, ndc, device, seed=0):
+        images, poses, self.H, self.W, self.focal = _check(images, poses, H, W, focal)
+        self.ndc, self.seed = int(bool(ndc)), int(seed) & M64
+        self.n_img = images.shape[0]
+        self.M = self.n_img * self.H * self.W  # pixels
+        self._open(device, self.M * 12 + self.n_img * 48,
+                   "%s: %d images of %d x %d" % (type(self).__name__, self.n_img, self.H, self.W))
+        self.images = images.to(self.device).contiguous()
+        self.poses = poses.to(self.device).contiguous()
+        self._frames = (ptr(self.images), ptr(self.poses), self.n_img, self.H, self.W, self.focal, self.ndc)  # what every launch starts with
+
+    def _new_slot(self, n):
+        return tuple(torch.empty(n, 3, dtype=torch.float32, device=self.device) for _ in range(4)) + (
+            torch.empty(n, dtype=torch.int64, device=self.device),)
+
+    def next(self, *args, **kwargs):
+        n, which = self._draw(*args, **kwargs)
+        if self.device.type != "cuda":
+            o, d, v, t, ids = host_rows(self.images, self.poses, self.H, self.W, self.focal, self.ndc, self._ids(n, which))
+        else:
+            (o, d, v, t, ids), out = self._take(n)
+            with torch.cuda.device(self.device):
+                self._launch(n, which, out, stream(self.device))
+        self._drawn(n, which)
+        self.last_ids = ids
+        return o, d, v, t
 
 
-class PixelBatcher:
+class PixelBatcher(DrawCounter, PixelSource):
     """The training pixels and poses, and next(n): the (rays_o, rays_d, viewdirs, target) of the next n draws, each [n, 3].
 
     On a ROCm device the images [n_img,H,W,3] (fp32, after Scene.rgb_images) and poses are uploaded once and a batch is one
     r2l_pixel_batch launch on the CURRENT stream into one of two alternating sets of output buffers: the tensors handed out stay
     valid until the second-next call, and nothing synchronises (RayStore.next's contract).  On the CPU next() answers from
-    host_batch.  seek(draw) sets the number of the next draw; last_ids holds the pixel ids of the last batch (int64)."""
-
-    def __init__(self, images, poses, H, W, focal, ndc, device, seed=0):
-        images, poses, self.H, self.W, self.focal = _check(images, poses, H, W, focal)
-        self.device = torch.device(device)
-        self.ndc, self.seed = int(bool(ndc)), int(seed) & M64
-        self.n_img = images.shape[0]
-        self.M = self.n_img * self.H * self.W
-        self.nbytes = self.M * 12 + self.n_img * 48
-        self.draw = 0
-        self.last_ids = None
-        self._buf, self._k = [None, None], 0
-        if self.device.type == "cuda":
-            from . import _lib
-            if self.device.index is None:
-                self.device = torch.device("cuda", torch.cuda.current_device())
-            free, _total = torch.cuda.mem_get_info(self.device)
-            if self.nbytes > 0.8 * free:
-                raise MemoryError("PixelBatcher: %d images of %d x %d need %.2f GB, more than 80 %% of the %.2f GB free on %s" %
-                                  (self.n_img, self.H, self.W, self.nbytes / 1e9, free / 1e9, self.device))
-            self._lib, self._L = _lib, _lib.load()
-        self.images = images.to(self.device).contiguous()
-        self.poses = poses.to(self.device).contiguous()
+    host_rows at pixel_ids.  seek(draw) sets the number of the next draw; last_ids holds the pixel ids of the last batch (int64)."""
 
     def describe(self):
         return "%d pixels of %d images %d x %d, %.3f GB on %s" % (self.M, self.n_img, self.H, self.W, self.nbytes / 1e9, self.device)
@@ -127,28 +133,14 @@ class PixelBatcher:
         """The epoch the next draw belongs to."""
         return self.draw // self.M
 
-    def seek(self, draw):
-        if draw < 0:
-            raise ValueError("PixelBatcher.seek: negative draw")
-        self.draw = int(draw)
+    def _draw(self, n):
+        return int(n), self.draw
 
-    def next(self, n):
-        n = int(n)
-        if self.device.type != "cuda":
-            o, d, v, t, ids = host_batch(self.images, self.poses, self.H, self.W, self.focal, self.ndc, self.seed, self.draw, n)
-        else:
-            k = self._k
-            if self._buf[k] is None or self._buf[k][0].shape[0] != n:
-                # (new tensors: the ones handed out two calls ago stay the caller's; the allocator is stream-ordered)
-                self._buf[k] = tuple(torch.empty(n, 3, dtype=torch.float32, device=self.device) for _ in range(4)) + (
-                    torch.empty(n, dtype=torch.int64, device=self.device),)
-            o, d, v, t, ids = self._buf[k]
-            stream = ctypes.c_void_p(torch.cuda.current_stream(self.device).cuda_stream)
-            with torch.cuda.device(self.device):
-                self._lib.check(self._L.r2l_pixel_batch(_p(self.images), _p(self.poses), self.n_img, self.H, self.W, self.focal,
-                                                        self.ndc, self.draw, n, self.seed, _p(o), _p(d), _p(v), _p(t), _p(ids),
-                                                        stream), "r2l_pixel_batch")
-            self._k ^= 1
-        self.draw += n
-        self.last_ids = ids
-        return o, d, v, t
+    def _ids(self, n, draw0):
+        return pixel_ids(self.seed, self.M, draw0, n)
+
+    def _launch(self, n, draw0, out, st):
+        _lib.check(self._L.r2l_pixel_batch(*self._frames, draw0, n, self.seed, *out, st), "r2l_pixel_batch")
+
+    def _drawn(self, n, draw0):
+        self.draw = draw0 + n

@@ -5,8 +5,6 @@ select_spec() restates in numpy what the kernel computes — the per-row error w
 and the tie rule; it is the specification the tests hold the kernel to.  select() is the ctypes wrapper HardRayPool's
 device_select path goes through.
 """
-import ctypes
-
 import numpy as np
 
 
@@ -69,8 +67,7 @@ def select(rgb, target, k):
     if work is None or work.numel() < need:
         work = _work[rgb.device] = torch.empty(need, dtype=torch.uint8, device=rgb.device)
     hard = torch.empty(k, dtype=torch.int64, device=rgb.device)
-    p = lambda x: ctypes.c_void_p(x.data_ptr())
+    p = _lib.ptr
     with torch.cuda.device(rgb.device):
-        _lib.check(lib.r2l_pool_select(p(a), p(b), sa, sb, B, k, p(hard), None, p(work),
-                                       ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)), "r2l_pool_select")
+        _lib.check(lib.r2l_pool_select(p(a), p(b), sa, sb, B, k, p(hard), None, p(work), _lib.stream()), "r2l_pool_select")
     return hard

@@ -15,7 +15,7 @@ import torch.nn.functional as F
 
 from . import _lib
 from . import engine as _engine
-from .engine import _ptr, _stream
+from ._lib import ptr as _ptr, stream as _stream
 
 # ---------------------------------------------------------------------------------------------------------------
 # rays + embedders

@@ -14,7 +14,7 @@ import torch
 
 from . import _lib
 from . import render
-from .engine import _ptr, _stream
+from ._lib import ptr as _ptr, stream as _stream
 from .metrics import img2mse, mse2psnr
 
 MAX_SAMPLES = 256  # r2l_raw2outputs_backward stages one ray's samples in LDS

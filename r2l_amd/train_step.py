@@ -19,7 +19,8 @@ import torch.distributed as dist
 
 from . import _lib
 from .dist_utils import GradAllReducer, bucket_plan, sync_parameters
-from .engine import N_SAMPLE, W, _ptr, _stream, get_engine
+from ._lib import ptr as _ptr, stream as _stream
+from .engine import N_SAMPLE, W, get_engine
 
 STATUS_LAG = 4  # a segmented step's validity word is looked at exactly this many steps later (on every rank alike)
 
@@ -134,8 +135,7 @@ class R2LTrainer:
             self._bwd_packed[layout] = ver
 
     # ---- the launches of a step (everything else in this class is host logic) --------------------------------------------------
-    def _stream(self):
-        return _stream()
+    _stream = staticmethod(_stream)  # (through self: a trainer without a GPU overrides it)
 
     def _launch_backward(self, args, parts, layer_lo, layer_hi, what="r2l_backward_part"):
         """One call of the staged backward (include/r2l_hip.h r2l_backward_part_cfg) on the step's argument tuple."""
