@@ -219,6 +219,27 @@ int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, const float*
 int r2l_chain_segments_ok_cfg(int64_t N, int n_block, const r2l_config* cfg);
 const unsigned* r2l_backward_status_word(const float* wstream_bwd, int n_block);
 
+/* The gradient with respect to the student's INPUT (what autograd gives the reference's plain module for free: pose
+ * refinement, localisation against a trained light field).  Call order of a step:
+ *     r2l_forward_rays* / r2l_forward_emb* with the stash  ->  r2l_backward* whose parts include R2L_BWD_CHAIN  ->  this call,
+ * on the same stream.  gx is that backward's gx: its slot 0 holds dL/d(head pre-activation) [N,256] once the chain has run (in
+ * every kernel family: fp32, unscaled, row-major; rows >= N are padding and are not read).  params as given to that backward;
+ * gx and params 16-byte aligned.
+ *   d_emb    [N,1008] or NULL:  d_emb[r][k] = sum_o gh[r][o] * head.0.weight[o][k]   (exact fp32 products on the matrix pipe)
+ *   d_rays_o, d_rays_d  [N,3] each, both or neither; they need the ray form (rays_o, rays_d, ztab as given to the forward;
+ *            t_rand NULL when the forward had none):  with z = z_lower[s] + z_span[s] * t_rand[r,s], x = o + d z,
+ *            d_pts[r][s][a] = sum_f d_emb[r][(3 s + a) 21 + f] * phi'_f(x)  (2^f cos(2^f x) for the sin columns, -2^f sin(2^f x)
+ *            for the cos columns, 1 for x itself),  d_rays_o[a] = sum_s d_pts[s][a],  d_rays_d[a] = sum_s z_s d_pts[s][a].
+ *            The jitter t_rand and the table ztab get no gradient.  Without d_emb the [N,1008] product never reaches memory.
+ * Outputs are OVERWRITTEN (unlike `grads`), no row >= N is written, no atomics: two calls give the same bits.
+ * After a step whose range guard fell back, gx is valid once the fallback kernels have run: they are stream-ordered in front of
+ * this launch, nothing to do.  A R2L_BWD_NOFALLBACK step whose status word was raised has no valid gradient here either.
+ * Errors (non-zero, r2l_last_error names them): no output requested; d_rays_* without rays_o / rays_d / ztab; one of the two
+ * d_rays_* alone; N < 1; n_block out of range; gx / params NULL or misaligned. */
+int r2l_backward_input(const float* gx, const float* params, int n_block, const float* rays_o, const float* rays_d,
+                       const float* t_rand, const float* ztab, float* d_emb, float* d_rays_o, float* d_rays_d, int64_t N,
+                       void* stream);
+
 /* ---- gradient all-reduce for hosts without torch.distributed ----------------------------------------------------------
  * The one exchange of data-parallel training (replaces nn.DataParallel's ReduceAddCoalesced + parameter broadcast,
  * main.py:37-42,472-479): in-place SUM of grads[n] over the ranks, RCCL over xGMI, enqueued on the caller's stream.  RCCL

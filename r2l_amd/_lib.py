@@ -117,6 +117,7 @@ SIGNATURES = {
     "r2l_adam_step_packed": (_i, [_p, _p, _p, _p, _i, _f, _f, _f, _f, _i, _f, _p, _p, _p, _p]),
     "r2l_chain_segments_ok_cfg": (_i, [_l, _i, _cfgp]),
     "r2l_backward_status_word": (_p, [_p, _i]),
+    "r2l_backward_input": (_i, [_p, _p, _i, _p, _p, _p, _p, _p, _p, _p, _l, _p]),
     "r2l_forward_status_words": (_p, [_p, _i]),
     "r2l_backward_status_words": (_p, [_p, _i]),
     "r2l_teacher_status_words": (_p, [_p]),

@@ -226,6 +226,8 @@ class R2LEngine:
     # ---- sampler tables ---------------------------------------------------------------------------------------
     def ztab(self, z_vals, perturb):
         """[32] = z_lower[16] ++ z_span[16] for PointSampler.z_vals (model/nerf_raybased.py:115-123), on device."""
+        if self.device is None:  # not flattened yet: the table would stay on the CPU, be cached, and reach a kernel as a host pointer
+            self.ensure_packed()
         key = (z_vals.data_ptr(), bool(perturb > 0), z_vals._version)
         tab = self._ztab_cache.get(key)
         if tab is None:
@@ -314,6 +316,23 @@ class R2LEngine:
             self.lib.r2l_forward_emb_cfg(_ptr(emb), _ptr(self.wstream), _ptr(self.flat), self.n_block, _ptr(rgb), _ptr(sx),
                                          _ptr(st), n, _ptr(x0), _stream(), self._cfg()), "r2l_forward_emb")
         return rgb
+
+    # ---- gradient with respect to the input ---------------------------------------------------------------------------------
+    def backward_input(self, gx, n, rays=None, want_emb=False, want_rays=False):
+        """r2l_backward_input (include/r2l_hip.h) behind an r2l_backward* call whose R2L_BWD_CHAIN stage filled gx, on the current
+        stream: (d_emb [n,1008] or None, d_rays_o, d_rays_d [n,3] or None).  rays = (rays_o, rays_d, t_rand or None, ztab): the
+        tensors the forward was given, needed for want_rays.  r2l_amd/input_grad.py restates the arithmetic."""
+        if not (want_emb or want_rays):
+            raise ValueError("backward_input: nothing asked for")
+        f = dict(dtype=torch.float32, device=gx.device)
+        d_emb = torch.empty(n, INPUT_DIM, **f) if want_emb else None
+        d_o = torch.empty(n, 3, **f) if want_rays else None
+        d_d = torch.empty(n, 3, **f) if want_rays else None
+        o, d, u, ztab = rays if rays is not None else (None, None, None, None)
+        _lib.check(
+            self.lib.r2l_backward_input(_ptr(gx), _ptr(self.flat), self.n_block, _ptr(o), _ptr(d), _ptr(u), _ptr(ztab), _ptr(d_emb),
+                                        _ptr(d_o), _ptr(d_d), int(n), _stream()), "r2l_backward_input")
+        return d_emb, d_o, d_d
 
 
 def get_engine(module):

@@ -191,7 +191,8 @@ class NeRF_v3_2(nn.Module):
             x = x.permute(0, 2, 3, 1)
         if not x.is_cuda:
             return self._forward_torch(x)
-        if torch.is_grad_enabled() and any(p.requires_grad for p in self.parameters()):
+        # (an input that requires grad takes the autograd route too, parameters frozen or not: pose refinement / localisation)
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
             from .autograd import R2LEmbFunction
             return R2LEmbFunction.apply(self, x, *list(self.parameters()))
         lead = x.shape[:-1]
@@ -199,10 +200,15 @@ class NeRF_v3_2(nn.Module):
 
     # -- fused entry points (what the build's own drivers call) -----------------------------------------------------
     def forward_rays(self, rays_o, rays_d, point_sampler, perturb=0., t_rand=None):
-        """rgb[N,3] = self(embed(point_sampler.sample_train(o, d, perturb))) with sampling + encoding fused in-kernel."""
+        """rgb[N,3] = self(embed(point_sampler.sample_train(o, d, perturb))) with sampling + encoding fused in-kernel.
+        Rays that require grad (grad mode on) get their gradient, and the parameters that ask for one theirs, through
+        R2LRaysFunction; the jitter t_rand gets none.  Plain tensors take the forward-only launch and build no graph."""
         if not rays_o.is_cuda:
             pe = PositionalEmbedder(_engine.L_PE, device=rays_o.device)
             return self._forward_torch(pe(point_sampler.sample_train(rays_o, rays_d, perturb, t_rand)))
+        if torch.is_grad_enabled() and (rays_o.requires_grad or rays_d.requires_grad):
+            from .autograd import R2LRaysFunction
+            return R2LRaysFunction.apply(self, rays_o, rays_d, t_rand, point_sampler.z_vals, perturb, *list(self.parameters()))
         return self.engine().forward_rays(rays_o, rays_d, point_sampler.z_vals, perturb, t_rand)
 
     def render_pose(self, c2w, point_sampler):
