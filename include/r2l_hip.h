@@ -704,6 +704,92 @@ int r2l_student_train_step(const r2l_student_step_desc* d, const float* store, f
                            float* loss_out /* dev [2]: loss, psnr */, float* rgb_out /* dev [N,3] or NULL */, float* work,
                            void* stream);
 
+/* ---- pose refinement against a trained student -------------------------------------------------------------------------------
+ * Localising P observed images against a frozen student (the use r2l_backward_input names): per iteration n pixels of every image,
+ * their rays under the current pose estimates, one forward and one dX chain, the ray gradients reduced to a 6-vector per pose, Adam
+ * on it and a retraction onto SE(3).  (The reference has no counterpart; iNeRF-style loops do this through autograd.)  P poses, n
+ * rays per pose, N = P n; ray p n + j belongs to pose p.  csrc/r2l_pose.hip; r2l_amd/pose_refine.py restates every stage in torch.
+ *
+ * r2l_pose_key: the key of pose p's pixel bijection at an iteration, host integer arithmetic only (no device work, no stream), with
+ * epoch_key exactly as specified for r2l_store_batch above:
+ *   z = epoch_key(seed ^ 0x706F73655F726566, iteration)        *key_out = epoch_key(z, p)          (iteration >= 1, p >= 0)
+ *
+ * r2l_pose_batch: row p n + j of rays_o / rays_d / target / ids_out is, bit for bit, row j of what r2l_image_batch writes for
+ * n_img = P, img = p, the whole frame as window, ndc = 0 and the key of r2l_pose_key(seed, iteration, p): pixel pi(key, H W)(j) of
+ * image p, its world ray under c2w[p] (pixel_ray of csrc/r2l_pixel_ray.h, the one definition), its colour, and its id
+ * (p H + row) W + col.  n <= H W: the pixels of a pose are distinct.  One launch, arguments checked before it; n == 0 or P == 0 is a
+ * successful no-op.  hipErrorInvalidValue (with r2l_last_error): a NULL required pointer (all but ids_out), P < 0, H / W < 1,
+ * focal <= 0, iteration < 1, n < 0 or n > H W, P H W > 2^31 - 1.
+ *
+ * r2l_pose_grad: the segmented reduction, all inputs [N,3]:
+ *   grad[p][0:3] = sum_j rays_d[p n + j] x d_rays_d[p n + j]    (d/dw at 0 of R <- exp([w]x) R: the rotation is about the camera
+ *                                                                centre, rays_o does not move with it)
+ *   grad[p][3:6] = sum_j d_rays_o[p n + j]
+ *   loss[p]      = sum_j |rgb - target|^2 / (3 n)                (loss may be NULL; the divisor is the fp32 value of 3 n)
+ * Outputs are OVERWRITTEN; nothing but grad, loss and work is written; no float atomics, a fixed order: two calls give the same
+ * bits.  Segments need not be aligned to anything.  Every product and every difference is rounded separately (no FMA); the sums are
+ * trees: four rays per lane pairwise, six shuffle levels per wave of 256 rays, then waves over 64 partials each until one is left.
+ * fp32 additions on the longest path of a term: 1 + 2 + 6 + 6 ceil(log64(ceil(n / 256))) — 9 for n <= 256, 15 for n <= 16 384, 21 for
+ * n <= 2^20, at most 33.  Every input is read once (16-byte loads when n % 4 == 0 and the inputs are 16-byte aligned).
+ * work: r2l_pose_grad_work_floats(P, n) floats, 16-byte aligned (0 floats, and work may be NULL, for n <= 256).
+ * hipErrorInvalidValue: a NULL required pointer, P < 0, n < 1 (with P > 0), P n >= 2^31, a NULL / misaligned work with n > 256.
+ *
+ * r2l_pose_update: per pose, with g = grad[p] and u = 2^-24:
+ *   not all six g finite: pose, exp_avg and exp_avg_sq of p keep their bits (one bad query does not poison the batch).  Else
+ *   m' = m + (g - m)(1 - beta1)   v' = v beta2 + g^2 (1 - beta2)   delta = -(lr / (1 - beta1^step)) (m' / (sqrt(v') / sqrt(1 - beta2^step) + eps))
+ *   — torch.optim.Adam's update of a zero 6-vector, evaluated as r2l_adam_step evaluates it — lr = lr_rot for delta[0:3] = dw,
+ *   lr_trans for delta[3:6] = dv;  R <- exp([dw]x) R = R + A [dw]x R + B [dw]x [dw]x R,  A = sin(th) / th = 2 sin(th/2) cos(th/2) / th,
+ *   B = (1 - cos(th)) / th^2 = 2 sin^2(th/2) / th^2, and below th^2 < 1e-4 (th < 0.01) by their series A = 1 - th^2/6 + th^4/120,
+ *   B = 1/2 - th^2/24 + th^4/720;  one modified Gram-Schmidt pass over the columns of R in the order 0, 1, 2;  t <- t + dv.
+ *   dw == 0 exactly (a zero gradient on zero moments): R keeps its bits — the Gram-Schmidt pass belongs to the rotation.
+ * c2w [P,3,4] in place; exp_avg, exp_avg_sq, grad [P,6].  hipErrorInvalidValue: a NULL pointer, P < 0, step < 1.
+ *
+ * r2l_pose_refine_step: one iteration for all P poses in one call — the same kernels with the same arguments in this order on
+ * `stream`, no allocation, no synchronisation, no state (the mould of r2l_student_train_step):
+ *   1. r2l_pose_batch at (seed, iteration)
+ *   2. pack == 1: r2l_pack_forward_layout / r2l_pack_backward_layout in the layouts r2l_forward_layout_for_cfg(N, 1, cfg) and
+ *      r2l_backward_layout_for_cfg(N, cfg) name (the weights are frozen: a host packs once and passes 0 afterwards)
+ *   3. r2l_forward_rays_cfg with the stash, t_rand = NULL; ztab is the test-time table (z_lower = PointSampler.z_vals, z_span = 0)
+ *   4. r2l_backward_part_cfg, parts = R2L_BWD_CHAIN, MSE mode, grad_scale = 2 / (3 n) — every pose's loss is its own mean; no weight-
+ *      gradient stage, no slab, `grads` is not touched (dpre stands in for the pointer)
+ *   5. r2l_backward_input in the ray form, without d_emb          6. r2l_pose_grad -> grad, loss_out
+ *   7. r2l_pose_update with step = iteration
+ * loss_out: device [P] (the host passes another row per iteration and reads them when it likes).  images: device [P,H,W,3];
+ * c2w, exp_avg, exp_avg_sq as r2l_pose_update; wstream / wstream_bwd zero-filled once after allocation.
+ * work: 16-byte aligned, r2l_pose_refine_work_floats(d) floats (-1 with r2l_last_error for an invalid descriptor); every part is
+ * rounded up to a multiple of 1024 floats, so that every part starts on a 4 KiB boundary; with slot = r2l_stash_slot_floats(N):
+ *   rays_o, rays_d, target, rgb [N,3] each; save_x (n_block + 1 slots), save_t (max(n_block, 1) slots), gx, gt likewise; dpre [N,3];
+ *   sqerr (r2l_num_tiles(N)); d_rays_o, d_rays_d [N,3]; grad [P,6]; the scratch of r2l_pose_grad.
+ * hipErrorInvalidValue (r2l_last_error names the field or pointer) before any launch: a NULL required pointer, n_block out of
+ * range, an invalid r2l_config, P < 1, n < 1, H / W < 1, n > H W, P H W or N >= 2^31, iteration < 1, focal <= 0, pack not 0 or 1,
+ * non-zero reserved, a work buffer that is not 16-byte aligned.  Range control and the bf16x3 fallback live inside the forward and
+ * backward entry points.  r2l_amd/pose_refine.py (PoseRefiner.fused_step) is the worked example. */
+int r2l_pose_key(uint64_t seed, int64_t iteration /*>= 1*/, int64_t p, uint64_t* key_out);
+int r2l_pose_batch(const float* images /*dev [P,H,W,3]*/, const float* c2w /*dev [P,3,4]*/, int P, int H, int W, float focal,
+                   uint64_t seed, int64_t iteration, int64_t n, float* rays_o, float* rays_d, float* target /*each [P*n,3]*/,
+                   int64_t* ids_out /*[P*n] or NULL*/, void* stream);
+int64_t r2l_pose_grad_work_floats(int64_t P, int64_t n);   /* -1: P or n negative, or P n >= 2^31 */
+int r2l_pose_grad(const float* rays_d, const float* d_rays_o, const float* d_rays_d, const float* rgb, const float* target,
+                  int64_t P, int64_t n, float* grad /*[P,6]*/, float* loss /*[P] or NULL*/, float* work, void* stream);
+int r2l_pose_update(float* c2w /*[P,3,4]*/, float* exp_avg, float* exp_avg_sq, const float* grad /*[P,6] each*/, int P,
+                    float lr_rot, float lr_trans, float beta1, float beta2, float eps, int64_t step /*>= 1*/, void* stream);
+typedef struct r2l_pose_refine_step_desc {
+    int n_block;
+    int pack;                         /* 0 | 1 */
+    const r2l_config* cfg;            /* dispatch of every launch of the step; NULL = AUTO */
+    int P, H, W;                      /* poses = observed images, each H x W */
+    float focal;
+    int64_t n;                        /* rays per pose and iteration, 1 <= n <= H W */
+    uint64_t seed;
+    int64_t iteration;                /* 1-based: names the pixels and is Adam's step count; 1 <= iteration < 2^60 */
+    float lr_rot, lr_trans, beta1, beta2, eps;
+    int reserved[4];                  /* must be 0 */
+} r2l_pose_refine_step_desc;
+int64_t r2l_pose_refine_work_floats(const r2l_pose_refine_step_desc* d);   /* -1: invalid descriptor */
+int r2l_pose_refine_step(const r2l_pose_refine_step_desc* d, const float* images /*dev [P,H,W,3]*/, float* c2w /*dev [P,3,4]*/,
+                         float* exp_avg, float* exp_avg_sq /*dev [P,6] each*/, const float* ztab, const float* params,
+                         float* wstream, float* wstream_bwd, float* loss_out /*dev [P]*/, float* work, void* stream);
+
 /* ---- pixel sampler of teacher training (batching mode without a bank of rays) ----------------------------------------------
  * The reference's use_batching mode (main.py:1137-1162, 1199-1210) builds the rays of every pixel of every training image,
  * shuffles that bank and hands out N_rand rows per step.  Here one draw is one pixel and its ray is computed when it is drawn:

@@ -69,6 +69,16 @@ class CompactStoreDesc(ctypes.Structure):
 _cstorep = ctypes.POINTER(CompactStoreDesc)
 
 
+class PoseRefineDesc(ctypes.Structure):
+    """r2l_pose_refine_step_desc of include/r2l_hip.h (r2l_pose_refine_step)."""
+    _fields_ = [("n_block", _i), ("pack", _i), ("cfg", _cfgp), ("P", _i), ("H", _i), ("W", _i), ("focal", _f), ("n", _l),
+                ("seed", ctypes.c_uint64), ("iteration", _l), ("lr_rot", _f), ("lr_trans", _f), ("beta1", _f), ("beta2", _f),
+                ("eps", _f), ("reserved", _i * 4)]
+
+
+_posep = ctypes.POINTER(PoseRefineDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -173,6 +183,13 @@ SIGNATURES = {
     "r2l_pixel_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _l, _l, ctypes.c_uint64, _p, _p, _p, _p, _p, _p]),
     "r2l_image_batch": (_i, [_p, _p, _i, _i, _i, _f, _i, _i, _i, _i, _i, _i, ctypes.c_uint64, _l, _p, _p, _p, _p, _p, _p]),
     "r2l_image_draw": (_i, [ctypes.c_uint64, _l, _i, _p, _p]),
+    "r2l_pose_key": (_i, [ctypes.c_uint64, _l, _l, _p]),
+    "r2l_pose_batch": (_i, [_p, _p, _i, _i, _i, _f, ctypes.c_uint64, _l, _l, _p, _p, _p, _p, _p]),
+    "r2l_pose_grad_work_floats": (_l, [_l, _l]),
+    "r2l_pose_grad": (_i, [_p, _p, _p, _p, _p, _l, _l, _p, _p, _p, _p]),
+    "r2l_pose_update": (_i, [_p, _p, _p, _p, _i, _f, _f, _f, _f, _f, _l, _p]),
+    "r2l_pose_refine_work_floats": (_l, [_posep]),
+    "r2l_pose_refine_step": (_i, [_posep] + [_p] * 11),
     "r2l_teacher_step_work_floats": (_l, [_stepp]),
     "r2l_teacher_train_step": (_i, [_stepp] + [_p] * 15),
     "r2l_png_writer_open": (_i, [_i, _i, _p]),

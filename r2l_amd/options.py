@@ -105,6 +105,13 @@ FLAGS = {
     # plays no part in it): one path or two joined by ':' (torchvision's VGG-16 checkpoint and the lpips package's vgg.pth, or a
     # saved lpips.LPIPS(net='vgg').state_dict(): metrics.lpips_vgg_params).  None are shipped; '' = no VGG work at all
     "r2l_lpips_vgg_weights": (str, ""),
+    # pose refinement against a trained student (utils/refine_pose.py; r2l_amd/pose_refine.py, r2l_pose_refine_step): iterations,
+    # pixels per view and iteration, the start — a file of poses [P,3,4] / [P,4,4], one per test view, or the true poses turned by
+    # DEG degrees about a random axis and shifted by DIST in a random direction (seeded) —, Adam's two learning rates ROT,TRANS
+    # and the .npy the refined poses go to ('' = refined_poses.npy in the experiment's log folder).  main.py,
+    # utils/create_data.py and utils/train_nerf.py ignore them
+    "r2l_pose_iters": (int, 200), "r2l_pose_rays": (int, 4096), "r2l_pose_init": (str, ""), "r2l_pose_noise": (str, "2,0.05"),
+    "r2l_pose_lr": (str, "2e-3,5e-3"), "r2l_pose_out": (str, ""),
     # new-architecture switches (dotted group)
     "trial.ON": ("flag", False), "trial.body_arch": (str, "mlp"), "trial.res_scale": (float, 1.),
     "trial.n_learnable": (int, 2), "trial.inact": (str, "relu"), "trial.outact": (str, "none"),
