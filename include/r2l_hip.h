@@ -431,8 +431,14 @@ int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_dev, int K, 
  * out[0] = SSIM(img1, img2): utils/ssim_torch.py:28-56,86-94 as called at main.py:46,254,334 (11x11 Gaussian sigma 1.5,
  * zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over every pixel and channel), fused into one kernel + a fixed-order
  * finish.  img1/img2: device [H, W, C] fp32 (the layout render_path holds, no permute).  window_host: host pointer to
- * the 121 window values (ssim_torch.py:19-25) or NULL to have them computed here.  partial: device scratch of
- * r2l_ssim_partial_count(H, W, C) floats. */
+ * the 121 window values (ssim_torch.py:19-25; any 121 floats, row-major [i][j] with i along H) or NULL to have the reference's
+ * computed here, bit for bit.  partial: device buffer of r2l_ssim_partial_count(H, W, C) = tilesY * tilesX * C floats with
+ * tilesY = ceil(H / 16), tilesX = ceil(W / 16).  Every entry is written (none is accumulated into) on every call:
+ *   partial[(c * tilesY + ty) * tilesX + tx] = sum of the SSIM map over the pixels of the 16 x 16 tile (ty, tx) of channel c
+ *                                             that lie inside the image (rows 16 ty .., columns 16 tx ..)
+ *   out[0] = (sum of the partials in a fixed order) * (1 / (H W C))
+ * The tile sums are the finest thing this entry point exposes; tests/ssim_util.py holds each of them to an fp64 yardstick.
+ * H, W, C >= 1 and C <= 65535, otherwise an error before anything is launched. */
 int64_t r2l_ssim_partial_count(int H, int W, int C);
 int r2l_ssim(const float* img1, const float* img2, int H, int W, int C, const float* window_host, float* partial,
              float* out, void* stream);

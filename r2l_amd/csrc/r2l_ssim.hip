@@ -92,12 +92,16 @@ int r2l_ssim(const float* img1, const float* img2, int H, int W, int C, const fl
     if (window_host) {
         for (int i = 0; i < SS_WIN * SS_WIN; ++i) win.w[i] = window_host[i];
     } else {  // ssim_torch.py:11-25: fp32 Gaussian (sigma 1.5) normalised in fp32, outer product in fp32
-        float g[SS_WIN], sum = 0.f;
+        // The sum of the eleven fp32 values is formed in double and rounded once: that is the number torch's pairwise fp32 sum
+        // gives here (3.7592328; adding them in index order in fp32 ends one ulp below, which moves 117 of the 121 taps by an ulp
+        // and the window's sum by 1.5e-7 — on a flat region s - mu^2 = S (1 - S) carries that straight into the map).
+        float g[SS_WIN];
+        double sum = 0.0;
         for (int x = 0; x < SS_WIN; ++x) {
             g[x] = (float)exp(-(double)((x - SS_R) * (x - SS_R)) / (2.0 * 1.5 * 1.5));
             sum += g[x];
         }
-        for (int x = 0; x < SS_WIN; ++x) g[x] /= sum;
+        for (int x = 0; x < SS_WIN; ++x) g[x] /= (float)sum;
         for (int i = 0; i < SS_WIN; ++i)
             for (int j = 0; j < SS_WIN; ++j) win.w[i * SS_WIN + j] = g[i] * g[j];
     }
