@@ -327,6 +327,36 @@ int64_t r2l_teacher_train_work_floats(int64_t P);
 int r2l_teacher_backward(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                          const float* tparams, const float* stash, const float* draw, float* grads, float* work, int64_t R,
                          int S, void* stream);
+/* r2l_raw2outputs_backward with the seed exposed (r2l_raw2outputs_backward IS this call with g = NULL, d_len = NULL and
+ * grad_scale = (float)(2.0 / (3.0 * R)), bit for bit):
+ *   g == NULL: dL/drgb_map = grad_scale * (rgb_map - target), sqerr[R] written as above;
+ *   g[R,3] given: it IS dL/drgb_map; target, grad_scale and sqerr play no part (may be NULL / anything).
+ * d_len[R], optional: dL/d|rays_d| (raw2outputs multiplies the intervals by |rays_d|), formed from a dL/dalpha of the kernel's
+ * own as sum_s dL/dalpha_s * relu(sigma_s + noise_s) * (z_{s+1} - z_s) * exp(..), summed from the last sample to the first.
+ * That dL/dalpha runs the same suffix recurrence on alpha = -expm1(-x) and t = exp(-x) + 1e-10 (x = relu(sigma) dist): the
+ * reference's fp32 1 - alpha, which draw keeps bit for bit, leaves three digits of the transmittance behind a nearly opaque
+ * sample, and d_len of such a ray consists of those terms.  Asking for d_len changes no bit of draw or sqerr. */
+int r2l_raw2outputs_backward_scaled(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
+                                    const float* target, const float* g, float grad_scale, float* draw, float* sqerr,
+                                    float* d_len, int64_t R, int S, void* stream);
+/* Scratch floats of r2l_teacher_backward_input for P points (-1 for P < 0). */
+int64_t r2l_teacher_input_grad_work_floats(int64_t P);
+/* The teacher's backward to its RAYS (frozen weights): the dX chain of r2l_teacher_backward with no weight-gradient product,
+ * then d_pe_xyz = G_0 W_0 + G_5 W_5[:, 0:63] and d_pe_dir = G_views W_views[:, 256:283], the derivative of the encoder
+ * (helpers:24-74; L = 10 at the fp32 points o + d*z, L = 4 at viewdirs; sin / cos by the forward's own function) and the sums
+ * over each ray's samples:
+ *   d_pts[R,S,3]      = dL/d(o + d z)              d_rays_o[R,3] = sum_s d_pts        d_viewdirs[R,3] = sum_s d_dir
+ *   d_rays_d[R,3]     = sum_s z_s d_pts  (+ d_len[r] rays_d/|rays_d| when d_len[R] is given: the term of raw2outputs' interval
+ *                        scaling)  (+ (d_viewdirs - (d_viewdirs . v) v) / |rays_d| with fold_viewdirs = 1, for viewdirs v =
+ *                        rays_d/|rays_d|; d_viewdirs is then formed whether or not it is returned)
+ * z is a constant (the fine samples are detached, as the reference detaches z_samples).  stash: r2l_teacher_mlp_train's on the
+ * same points; draw[R,S,4]; work: r2l_teacher_input_grad_work_floats(R*S) floats.  d_rays_o / d_rays_d: both or neither; each
+ * of d_viewdirs, d_pts may be NULL; at least one output.  Outputs are overwritten, no row >= R is written, no atomics, fixed
+ * summation order (bit-reproducible).  R == 0 is a successful no-op; 1 <= S <= 256. */
+int r2l_teacher_backward_input(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                               const float* tparams, const float* stash, const float* draw, const float* d_len,
+                               int fold_viewdirs, float* d_rays_o, float* d_rays_d, float* d_viewdirs, float* d_pts, float* work,
+                               int64_t R, int S, void* stream);
 
 /* z_out[R,S] = near*(1-t)+far*t, with stratified jitter when t_rand[R,S] != NULL (create_data.py:457-482).
  * near/far: per-ray values read at near[r*nf_stride], far[r*nf_stride]; ttab[2S] = t_vals ++ (1 - t_vals).

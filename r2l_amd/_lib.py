@@ -142,6 +142,9 @@ SIGNATURES = {
     "r2l_raw2outputs_backward": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "r2l_teacher_train_work_floats": (_l, [_l]),
     "r2l_teacher_backward": (_i, [_p] * 9 + [_l, _i, _p]),
+    "r2l_raw2outputs_backward_scaled": (_i, [_p, _p, _p, _p, _i, _p, _p, _f, _p, _p, _p, _l, _i, _p]),
+    "r2l_teacher_input_grad_work_floats": (_l, [_l]),
+    "r2l_teacher_backward_input": (_i, [_p] * 8 + [_i] + [_p] * 5 + [_l, _i, _p]),
     "r2l_stratified_z": (_i, [_p, _p, _i, _p, _p, _p, _l, _i, _p]),
     "r2l_raw2outputs": (_i, [_p, _p, _p, _p, _i, _p, _p, _p, _p, _p, _l, _i, _p]),
     "r2l_sample_pdf_sort": (_i, [_p, _p, _p, _l, _p, _p, _p, _l, _i, _i, _p]),

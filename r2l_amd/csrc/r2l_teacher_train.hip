@@ -3,6 +3,8 @@
 //   r2l_raw2outputs_backward : loss seed 2 (rgb_map - target) / (3R) and autograd of raw2outputs (main.py:556-621) -> draw
 //   r2l_teacher_backward     : dX chain and weight / bias gradients of NeRF(D=8, W=256, 63+27, skips=[4], use_viewdirs)
 //                              (model/nerf_raybased.py:357-401) from draw and the stash of r2l_teacher_mlp_train
+//   r2l_raw2outputs_backward_scaled : the first with the seed scale (or dL/drgb_map itself) an argument, and dL/d|rays_d|
+//   r2l_teacher_backward_input      : the same dX chain with no weight product, on to rays_o / rays_d / viewdirs (end of file)
 // The products are fp32-input MFMA (v_mfma_f32_32x32x2_f32) in one LDS-tiled GEMM kernel with loader / epilogue functors:
 // the dX products G_{l-1} = (G_l W_l) * relu'(h_{l-1}) (weights read row-major, no transposed stream needed) and the weight
 // products dW_l = G_l^T A_l reduced over the points in fixed-size chunks into partial slabs, summed in a fixed order by a second
@@ -27,9 +29,16 @@
 __global__ __launch_bounds__(256) void r2l_raw2outputs_bwd_kernel(const float* __restrict__ raw, const float* __restrict__ z,
                                                                   const float* __restrict__ rays_d,
                                                                   const float* __restrict__ noise, int white,
-                                                                  const float* __restrict__ target, float* __restrict__ draw,
-                                                                  float* __restrict__ sqerr, int64_t R, int S, float gscale) {
+                                                                  const float* __restrict__ target,
+                                                                  const float* __restrict__ gseed, float* __restrict__ draw,
+                                                                  float* __restrict__ sqerr, float* __restrict__ d_len, int64_t R,
+                                                                  int S, float gscale) {
     __shared__ float s_a[4][TT_RB_MAXS], s_t[4][TT_RB_MAXS], s_da[4][TT_RB_MAXS], s_e[4][TT_RB_MAXS], s_T[4][TT_RB_MAXS];
+    // Only when d_len is asked for: s_dn = d a / d |d| = relu(sigma) (z_{i+1} - z_i) exp(..), and a second, accurate pair
+    // (a', t') = (-expm1(-x), exp(-x) + 1e-10) for d_len's own dL/da.  The pair above is the reference's fp32 arithmetic, whose
+    // 1 - a keeps three digits of t behind a nearly opaque sample (a within 1e-4 of 1): draw, measured against the ray's
+    // largest entry, does not notice, but d_len of such a ray IS those small terms.
+    __shared__ float s_dn[4][TT_RB_MAXS], s_ap[4][TT_RB_MAXS], s_tp[4][TT_RB_MAXS];
     __shared__ float s_rgb[4][TT_RB_MAXS][3];
     __shared__ float s_g[4][3];
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63;
@@ -41,13 +50,20 @@ __global__ __launch_bounds__(256) void r2l_raw2outputs_bwd_kernel(const float* _
     const float* rr = raw + rc * S * 4;
     const float* zr = z + rc * S;
     for (int i = lane; i < S && live; i += 64) {
-        const float dist = (i + 1 < S ? zr[i + 1] - zr[i] : 1e10f) * dn;
+        const float dz = i + 1 < S ? zr[i + 1] - zr[i] : 1e10f;
+        const float dist = dz * dn;
         const float sig = noise ? rr[4 * i + 3] + noise[rc * S + i] : rr[4 * i + 3];
-        const float ex = expf(-fmaxf(sig, 0.f) * dist);
+        const float xx = fmaxf(sig, 0.f) * dist;
+        const float ex = expf(-xx);
         const float a = 1.0f - ex;
         s_a[wave][i] = a;
         s_t[wave][i] = (1.0f - a) + 1e-10f;
         s_da[wave][i] = sig > 0.f ? dist * ex : 0.f;  // d a / d raw3 (relu'(0) = 0, as torch)
+        if (d_len) {
+            s_dn[wave][i] = sig > 0.f ? (sig * dz) * ex : 0.f;
+            s_ap[wave][i] = -expm1f(-xx);
+            s_tp[wave][i] = ex + 1e-10f;
+        }
 #pragma unroll
         for (int c = 0; c < 3; ++c) s_rgb[wave][i][c] = 1.0f / (1.0f + expf(-rr[4 * i + c]));
     }
@@ -62,24 +78,44 @@ __global__ __launch_bounds__(256) void r2l_raw2outputs_bwd_kernel(const float* _
             for (int c = 0; c < 3; ++c) m[c] += w * s_rgb[wave][i][c];
             T *= s_t[wave][i];
         }
+        if (d_len) {  // s_dn <- T' d a / d |d| with the accurate transmittance T' = prod t'
+            float Tp = 1.0f;
+            for (int i = 0; i < S; ++i) {
+                s_dn[wave][i] *= Tp;
+                Tp *= s_tp[wave][i];
+            }
+        }
         float g[3], se = 0.f, gsum = 0.f;
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float rgb = white ? m[c] + (1.0f - acc) : m[c];
-            const float diff = rgb - target[r * 3 + c];
-            se += diff * diff;
-            g[c] = gscale * diff;  // d img2mse / d rgb_map = 2 (rgb - target) / (3 R)
+            if (gseed) {
+                g[c] = gseed[r * 3 + c];  // dL/drgb_map itself: no target, no loss
+            } else {
+                const float diff = rgb - target[r * 3 + c];
+                se += diff * diff;
+                g[c] = gscale * diff;  // d img2mse / d rgb_map = 2 (rgb - target) / (3 R) at the default scale
+            }
             gsum += g[c];
             s_g[wave][c] = g[c];
         }
-        sqerr[r] = se;
-        float U = 0.f;
+        if (!gseed) sqerr[r] = se;
+        float U = 0.f, Up = 0.f, dl = 0.f;
         for (int k = S - 1; k >= 0; --k) {
             const float e = g[0] * s_rgb[wave][k][0] + g[1] * s_rgb[wave][k][1] + g[2] * s_rgb[wave][k][2] -
                             (white ? gsum : 0.f);
             s_e[wave][k] = s_T[wave][k] * (e - U);  // dL/da_k
-            U = e * s_a[wave][k] + s_t[wave][k] * U;
+            if (d_len) {  // fixed order: last sample first; dL/da'_k = T'_k (e_k - U'_k)
+                dl += (e - Up) * s_dn[wave][k];
+                float eap = e * s_ap[wave][k];
+                r2l_no_pack(eap);
+                Up = eap + s_tp[wave][k] * Up;
+            }
+            float ea = e * s_a[wave][k];
+            r2l_no_pack(ea);  // (the two products would pair into a v_pk_mul_f32 + a swizzled v_pk_add_f32: build.py's ISA audit)
+            U = ea + s_t[wave][k] * U;
         }
+        if (d_len) d_len[r] = dl;
     }
     __syncthreads();
     if (!live) return;
@@ -98,15 +134,33 @@ __global__ __launch_bounds__(256) void r2l_raw2outputs_bwd_kernel(const float* _
     }
 }
 
+static int tt_raw2outputs_backward(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
+                                   const float* target, const float* g, float grad_scale, float* draw, float* sqerr,
+                                   float* d_len, int64_t R, int S, hipStream_t st) {
+    hipLaunchKernelGGL(r2l_raw2outputs_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, raw, z, rays_d, noise,
+                       white_bkgd, target, g, draw, sqerr, d_len, R, S, grad_scale);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
 extern "C" int r2l_raw2outputs_backward(const float* raw, const float* z, const float* rays_d, const float* noise, int white_bkgd,
                                         const float* target, float* draw, float* sqerr, int64_t R, int S, void* stream) {
     R2L_REQUIRE(R >= 0 && S >= 1 && S <= TT_RB_MAXS, "r2l_raw2outputs_backward: need R >= 0 and 1 <= S <= 256");
     if (R == 0) return 0;
     R2L_REQUIRE(raw && z && rays_d && target && draw && sqerr, "r2l_raw2outputs_backward: a required pointer is NULL");
-    hipLaunchKernelGGL(r2l_raw2outputs_bwd_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, (hipStream_t)stream, raw, z,
-                       rays_d, noise, white_bkgd, target, draw, sqerr, R, S, (float)(2.0 / (3.0 * (double)R)));
-    R2L_CHECK(hipGetLastError());
-    return 0;
+    return tt_raw2outputs_backward(raw, z, rays_d, noise, white_bkgd, target, nullptr, (float)(2.0 / (3.0 * (double)R)), draw,
+                                   sqerr, nullptr, R, S, (hipStream_t)stream);
+}
+
+extern "C" int r2l_raw2outputs_backward_scaled(const float* raw, const float* z, const float* rays_d, const float* noise,
+                                               int white_bkgd, const float* target, const float* g, float grad_scale,
+                                               float* draw, float* sqerr, float* d_len, int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0 && S >= 1 && S <= TT_RB_MAXS, "r2l_raw2outputs_backward_scaled: need R >= 0 and 1 <= S <= 256");
+    if (R == 0) return 0;
+    R2L_REQUIRE(raw && z && rays_d && draw, "r2l_raw2outputs_backward_scaled: a required pointer is NULL");
+    R2L_REQUIRE(g || (target && sqerr), "r2l_raw2outputs_backward_scaled: without g, target and sqerr are required");
+    return tt_raw2outputs_backward(raw, z, rays_d, noise, white_bkgd, target, g, grad_scale, draw, sqerr, d_len, R, S,
+                                   (hipStream_t)stream);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -368,4 +422,170 @@ extern "C" int r2l_teacher_backward(const float* rays_o, const float* rays_d, co
     }
     // layer 0: dW over PE(xyz)
     return tt_weight_grad(cur, T_W, T_W, act(nullptr, T_XYZ, 0, 0), T_XYZ, P, slab, grads, off.w[0], off.b[0], st);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// Backward to the rays (a frozen teacher: iNeRF-style localisation, density normals).  The dX chain above with no weight
+// product and no slab, then the three input-side products
+//   d_pe_xyz[P,63] = G_0 W_0 + G_5 W_5[:, 0:63]        d_pe_dir[P,27] = G_views W_views[:, 256:283]
+// through the same GEMM, then one wave per ray: the encoder's derivative per point
+//   d_x = g_x + sum_k 2^k (cos(2^k x) g_sin_k - sin(2^k x) g_cos_k)      (r2l_sincos at the frequency itself, as the forward)
+// and the sums over the ray's samples (lane l takes samples l, l + 64, .. in order, then a fixed xor tree over the lanes).
+// The per-ray pass reads whole rays, so a ray that straddles GEMM tiles needs no special case and nothing is atomic.
+// ------------------------------------------------------------------------------------------------------------------
+// accumulating epilogue: out[m*ld + n] += v (one thread per entry)
+struct EpDXAdd {
+    float* out;
+    int ld;
+    int64_t M;
+    int N;
+    __device__ void operator()(int64_t m, int n, float v, int) const {
+        if (m >= M || n >= N) return;
+        out[m * ld + n] += v;
+    }
+};
+
+template <int L>
+__device__ __forceinline__ void tt_pe_backward(const float (&x)[3], const float* __restrict__ g, float (&dx)[3]) {
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        float acc = g[ax];
+#pragma unroll
+        for (int k = 0; k < L; ++k) {
+            const float f = (float)(1 << k);
+            float sn, cs;
+            r2l_sincos(x[ax] * f, sn, cs);
+            acc += f * (cs * g[3 + 6 * k + ax] - sn * g[3 + 6 * k + 3 + ax]);
+        }
+        dx[ax] = acc;
+    }
+}
+
+__device__ __forceinline__ float tt_wave_sum(float v) {
+#pragma unroll
+    for (int m = 32; m >= 1; m >>= 1) v += __shfl_xor(v, m, 64);
+    return v;
+}
+
+__global__ __launch_bounds__(256) void tt_input_reduce_kernel(const float* __restrict__ rays_o, const float* __restrict__ rays_d,
+                                                              const float* __restrict__ viewdirs, const float* __restrict__ z,
+                                                              const float* __restrict__ dpe_x, const float* __restrict__ dpe_d,
+                                                              const float* __restrict__ d_len, int fold,
+                                                              float* __restrict__ d_rays_o, float* __restrict__ d_rays_d,
+                                                              float* __restrict__ d_viewdirs, float* __restrict__ d_pts, int64_t R,
+                                                              int S) {
+    const int lane = threadIdx.x & 63;
+    const int64_t r = (int64_t)blockIdx.x * 4 + (threadIdx.x >> 6);
+    if (r >= R) return;  // (whole waves leave: the shuffles below are wave-wide)
+    const float o[3] = {rays_o[r * 3], rays_o[r * 3 + 1], rays_o[r * 3 + 2]};
+    const float d[3] = {rays_d[r * 3], rays_d[r * 3 + 1], rays_d[r * 3 + 2]};
+    float so[3] = {0.f, 0.f, 0.f}, sd[3] = {0.f, 0.f, 0.f}, sv[3] = {0.f, 0.f, 0.f};
+    const bool want_x = dpe_x != nullptr;
+    float vd[3] = {0.f, 0.f, 0.f};
+    if (dpe_d) {
+        vd[0] = viewdirs[r * 3]; vd[1] = viewdirs[r * 3 + 1]; vd[2] = viewdirs[r * 3 + 2];
+    }
+    for (int s = lane; s < S; s += 64) {
+        const int64_t p = r * S + s;
+        if (want_x) {
+            const float zz = z[p];
+            float x[3], dx[3];
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) x[ax] = o[ax] + d[ax] * zz;  // as the forward: mul / add rounded separately
+            tt_pe_backward<10>(x, dpe_x + p * T_XYZ, dx);
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) {
+                if (d_pts) d_pts[p * 3 + ax] = dx[ax];
+                so[ax] += dx[ax];
+                sd[ax] += zz * dx[ax];
+            }
+        }
+        if (dpe_d) {
+            float dv[3];
+            tt_pe_backward<4>(vd, dpe_d + p * T_DIR, dv);
+#pragma unroll
+            for (int ax = 0; ax < 3; ++ax) sv[ax] += dv[ax];
+        }
+    }
+#pragma unroll
+    for (int ax = 0; ax < 3; ++ax) {
+        so[ax] = tt_wave_sum(so[ax]);
+        sd[ax] = tt_wave_sum(sd[ax]);
+        sv[ax] = tt_wave_sum(sv[ax]);
+    }
+    if (lane != 0) return;
+    if (d_viewdirs)
+        for (int ax = 0; ax < 3; ++ax) d_viewdirs[r * 3 + ax] = sv[ax];
+    if (!d_rays_d) return;
+    if (d_len || fold) {
+        const float dn = sqrtf(d[0] * d[0] + d[1] * d[1] + d[2] * d[2]);
+        if (d_len) {
+            const float dl = d_len[r];
+            for (int ax = 0; ax < 3; ++ax) sd[ax] += dl * (d[ax] / dn);
+        }
+        if (fold) {  // viewdirs = rays_d / |rays_d|: the normalisation's Jacobian (I - v v^T) / |d|
+            const float dot = sv[0] * vd[0] + sv[1] * vd[1] + sv[2] * vd[2];
+            for (int ax = 0; ax < 3; ++ax) sd[ax] += (sv[ax] - dot * vd[ax]) / dn;
+        }
+    }
+    for (int ax = 0; ax < 3; ++ax) {
+        d_rays_o[r * 3 + ax] = so[ax];
+        d_rays_d[r * 3 + ax] = sd[ax];
+    }
+}
+
+extern "C" int64_t r2l_teacher_input_grad_work_floats(int64_t P) {
+    if (P < 0) return -1;
+    return 2 * P * T_W + P * T_VIEWS + P * T_XYZ + P * T_DIR;  // G ping, G pong, G of the views layer, d_pe_xyz, d_pe_dir
+}
+
+extern "C" int r2l_teacher_backward_input(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                          const float* tparams, const float* stash, const float* draw, const float* d_len,
+                                          int fold_viewdirs, float* d_rays_o, float* d_rays_d, float* d_viewdirs, float* d_pts,
+                                          float* work, int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0 && S >= 1 && S <= TT_RB_MAXS, "r2l_teacher_backward_input: need R >= 0 and 1 <= S <= 256");
+    R2L_REQUIRE(d_rays_o || d_rays_d || d_viewdirs || d_pts, "r2l_teacher_backward_input: no output requested");
+    R2L_REQUIRE((d_rays_o != nullptr) == (d_rays_d != nullptr),
+                "r2l_teacher_backward_input: d_rays_o and d_rays_d are given together or not at all");
+    if (R == 0) return 0;
+    R2L_REQUIRE(rays_o && rays_d && viewdirs && z && tparams && stash && draw && work,
+                "r2l_teacher_backward_input: a required pointer is NULL");
+    const TOff off = t_offsets();
+    const int64_t P = R * (int64_t)S;
+    const hipStream_t st = (hipStream_t)stream;
+    const float* W = tparams;
+    float* ga = work;
+    float* gb = ga + P * T_W;
+    float* gv = gb + P * T_W;
+    float* dpx = gv + P * T_VIEWS;
+    float* dpd = dpx + P * T_XYZ;
+    auto slot = [&](int l) { return T_STASH_SLOT(stash, (int64_t)l, P); };
+    const bool want_x = d_rays_d || d_pts;
+    const bool want_dir = d_viewdirs || (d_rays_d && fold_viewdirs);  // the folding term needs d_viewdirs, returned or not
+    int rc;
+    hipLaunchKernelGGL(tt_rgb_head_dx_kernel, dim3((unsigned)((P * T_VIEWS + 255) / 256 < 65536 ? (P * T_VIEWS + 255) / 256 : 65536)),
+                       dim3(256), 0, st, draw, W + off.rgb_w, slot(T_STASH_VIEWS), gv, P);
+    R2L_CHECK(hipGetLastError());
+    if (want_dir &&
+        (rc = tt_dx(gv, T_VIEWS, T_VIEWS, W + off.views_w, T_W + T_DIR, T_W, T_DIR, dpd, nullptr, nullptr, nullptr, P, st)))
+        return rc;
+    if (want_x) {
+        if ((rc = tt_dx(gv, T_VIEWS, T_VIEWS, W + off.views_w, T_W + T_DIR, 0, T_W, ga, nullptr, nullptr, nullptr, P, st))) return rc;
+        if ((rc = tt_dx(ga, T_W, T_W, W + off.feat_w, T_W, 0, T_W, gb, slot(7), draw + 3, W + off.alpha_w, P, st))) return rc;
+        float* cur = gb;
+        float* nxt = ga;
+        for (int l = 7; l >= 1; --l) {
+            const int nx = l == 5 ? T_XYZ : 0;
+            if (nx && (rc = tt_dx(cur, T_W, T_W, W + off.w[l], nx + T_W, 0, T_XYZ, dpx, nullptr, nullptr, nullptr, P, st))) return rc;
+            if ((rc = tt_dx(cur, T_W, T_W, W + off.w[l], nx + T_W, nx, T_W, nxt, slot(l - 1), nullptr, nullptr, P, st))) return rc;
+            float* t = cur; cur = nxt; nxt = t;
+        }
+        const EpDXAdd ep{dpx, T_XYZ, P, T_XYZ};  // + G_0 W_0 onto layer 5's share
+        if ((rc = tt_gemm(LdRowA{cur, T_W}, LdWeightB{W + off.w[0], T_XYZ, 0}, ep, P, T_XYZ, T_W, T_W, nullptr, st))) return rc;
+    }
+    hipLaunchKernelGGL(tt_input_reduce_kernel, dim3((unsigned)((R + 3) / 4)), dim3(256), 0, st, rays_o, rays_d, viewdirs, z,
+                       want_x ? dpx : (const float*)nullptr, want_dir ? dpd : (const float*)nullptr, d_len, fold_viewdirs,
+                       d_rays_o, d_rays_d, d_viewdirs, d_pts, R, S);
+    R2L_CHECK(hipGetLastError());
+    return 0;
 }
