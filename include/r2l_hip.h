@@ -597,6 +597,23 @@ int r2l_store_append(const float* rows_in, int64_t n_rows, float* store, int64_t
                      int64_t rays_per_shard, uint64_t key, int shuffle, int64_t* n_written_out, void* stream);
 int r2l_store_batch(const float* store, int64_t n_shards, int64_t rays_per_shard, int64_t draw0, int64_t n_draw, uint64_t seed,
                     float* batch, int32_t* ids_out, void* stream);
+/*   r2l_store_append_images: the REAL training rays of a scene as store rows, from K images and their K poses (the converters
+ *     utils/convert_original_data_to_rays_*.py without the files).  With n_rows = K*H*W and m = floor(n_rows / rays_per_shard),
+ *     output row i < m * rays_per_shard, counted from shard first_shard, is [o, d, rgb] of ray r = pi(key, n_rows)(i) — pi as
+ *     specified for r2l_store_append above; shuffle = 0: r = i —, r = (k*H + row)*W + col:  (o, d) = the ray of pixel (row, col)
+ *     under c2w_dev[k] and focal_dev[k] (NULL: focal for all) in the arithmetic pinned under r2l_frame_rays above (pixel_ray of
+ *     csrc/r2l_pixel_ray.h), rgb = images[r] copied.  The tail of the permuted sequence is dropped, *n_written_out = m (host
+ *     arithmetic).  BIT FOR BIT what r2l_frame_rays(rows) -> a copy of images into columns 6..8 -> r2l_store_append gives, in one
+ *     launch and without the [n_rows, 9] intermediate: 12 bytes gathered and 36 written a ray.  Stateless; one kernel on `stream`,
+ *     no synchronisation, 64-bit offsets; m == 0 enqueues nothing.  Refused before the launch (hipErrorInvalidValue, r2l_last_error
+ *     names the argument): a NULL images / c2w_dev / store / n_written_out, K, H or W < 1, K*H*W > 2^58, focal <= 0 with a NULL
+ *     focal_dev, rays_per_shard not a positive multiple of 4, a negative first_shard, first_shard + m > capacity_shards, a store
+ *     that is not 16-byte aligned, images [K,H,W,3] that overlap the capacity_shards * rays_per_shard rows of the store.
+ *     r2l_amd/raystore.py (append_images_spec) restates it in numpy. */
+int r2l_store_append_images(const float* images /*dev [K,H,W,3]*/, const float* c2w_dev /*[K,3,4]*/,
+                            const float* focal_dev /*[K] or NULL*/, float focal, int K, int H, int W,
+                            float* store, int64_t capacity_shards, int64_t first_shard, int64_t rays_per_shard,
+                            uint64_t key, int shuffle, int64_t* n_written_out, void* stream);
 
 /* ---- compact ray store (16 bytes a ray; o and d recomputed per draw) ------------------------------------------------------------
  * A store that the TEACHER fills is redundant at 36 bytes a ray: every row of a flush group comes from r2l_teacher_frames_cfg,

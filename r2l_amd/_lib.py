@@ -177,6 +177,7 @@ SIGNATURES = {
     "r2l_pool_select": (_i, [_p, _p, _l, _l, _l, _l, _p, _p, _p, _p]),
     "r2l_store_append": (_i, [_p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_store_batch": (_i, [_p, _l, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
+    "r2l_store_append_images": (_i, [_p, _p, _p, _f, _i, _i, _i, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_cstore_append": (_i, [_cstorep, _p, _l, _p, _p, _f, _i, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_cstore_batch": (_i, [_cstorep, _l, _l, _l, ctypes.c_uint64, _p, _p, _p]),
     "r2l_words_digest": (_i, [_p, _l, _l, ctypes.c_uint64, _p, _p]),

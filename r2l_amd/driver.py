@@ -18,7 +18,8 @@ from .checkpoint import load_ckpt, load_weights_v2, parse_expid_iter, save_ckpt
 from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
-from .options import parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_store_file
+from .options import (parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_image_store,
+                      validate_store_file)
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -716,8 +717,8 @@ def lpips_field(misc):
 # ---------------------------------------------------------------------------------------------------------------
 def open_training_source(args, scene, H, W, focal, near, far, shards, start, rank, world, device, logger):
     """The source of this rank's training batches, as the options say: a store the teacher fills (--r2l_online_kd, plain or
-    --r2l_compact_store), a store file (--r2l_store_load), a store the shard files are read into once (--r2l_device_store), or
-    the reader of the shard files.  shards: shard files per step of every rank; start: the iteration a resumed run starts
+    --r2l_compact_store), a store of the scene's real training rays (--r2l_image_store, alone or behind the teacher's), a store
+    file (--r2l_store_load), a store the shard files are read into once (--r2l_device_store), or the reader of the shard files.  shards: shard files per step of every rank; start: the iteration a resumed run starts
     behind.  Returns (loader, files, filler): files — the names the run counts as its training files; filler — the
     online_kd.TeacherFill while poses are still pending, else None."""
     filler = None  # --r2l_online_kd: the teacher fill of the store (online_kd.TeacherFill), while poses are pending
@@ -735,6 +736,11 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
         if cap < 1:
             raise ValueError("--r2l_online_kd: rank %d of %d gets no shard from --n_pose_kd %d" % (rank, world, n_pose))
+        real = None  # --r2l_image_store: the real training rays go behind the teacher's groups, into the same store
+        if args.r2l_image_store:
+            from .image_store import fill_store_from_images, image_shards, training_frames
+            real = training_frames(scene, args.white_bkgd)
+            cap += image_shards(real[0].shape[0], H, W, rank, world)[1]
         if args.r2l_compact_store:
             # 16 bytes a ray: rgb and the ray's number in its flush group; o, d are recomputed per draw from the group's poses
             # (one pose-table slot per pose of this rank) and the batches are the plain store's bit for bit
@@ -750,12 +756,39 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
         while not filler.done and (n_groups is None or filler.groups < n_groups):
             filler.fill_group()
+        provenance = filler.provenance()
+        if real is not None:  # (--r2l_kd_every 0, checked at start-up: the teacher's fill is complete)
+            n_teacher = loader.n_shards
+            n_real = fill_store_from_images(loader, real[0], real[1], focal, rank, world, logger=logger)
+            # the sampler draws shards uniformly: the real share of the training set is a shard count, not a schedule
+            logger.info("ray store: %d teacher shards + %d real shards = %d: real share %.4f of every epoch (the sampler draws shards "
+                        "uniformly; --pseudo_ratio is not consulted)" %
+                        (n_teacher, n_real, loader.n_shards, n_real / max(loader.n_shards, 1)))
+            provenance.update({"real_frames": int(real[0].shape[0]), "real_shards": n_real})
+            real = None
         files = loader.files
         if args.r2l_store_save:  # (--r2l_kd_every 0, checked at start-up: the fill is complete) render once, train many times
             from .raystore import store_rank_path
-            loader.save(store_rank_path(args.r2l_store_save, rank, world), provenance=filler.provenance(), rank=rank, world=world)
+            loader.save(store_rank_path(args.r2l_store_save, rank, world), provenance=provenance, rank=rank, world=world)
         if filler.done:
             filler = None
+    elif args.r2l_image_store:
+        # no shard files and no teacher: the training images and poses the loader holds become the store's rows in one launch
+        # (r2l_amd/image_store.py) — README step 5 without step 4.  A pure function of the scene and R2L_SEED: a resumed run
+        # rebuilds the same rows bit for bit
+        from .image_store import fill_store_from_images, image_shards, training_frames
+        from .raystore import RayStore
+        real = training_frames(scene, args.white_bkgd)
+        loader = RayStore(max(image_shards(real[0].shape[0], H, W, rank, world)[1], 1), device, seed=9973 * rank, logger=logger)
+        n_real = fill_store_from_images(loader, real[0], real[1], focal, rank, world, logger=logger)
+        real = None
+        files = loader.files
+        if args.r2l_store_save:
+            from .raystore import store_rank_path
+            loader.save(store_rank_path(args.r2l_store_save, rank, world),
+                        provenance={"image_store": args.datadir, "real_frames": len(scene.i_train), "real_shards": n_real, "H": H, "W": W,
+                                    "focal": focal, "white_bkgd": bool(args.white_bkgd), "R2L_SEED": os.environ.get("R2L_SEED", "0")},
+                        rank=rank, world=world)
     elif args.r2l_store_load:
         # the store a run with --r2l_store_save (or utils/create_data.py) wrote: plain or compact as the file says, its digests
         # recomputed on the device before a row of it is trained on
@@ -795,7 +828,7 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         files = D.list_ray_shards(datadir_kd, args.pseudo_ratio, args.pseudo_data_hold_ratio)
         loader = D.RayShardLoader(files, shards[rank], rank=rank, world=world, device=device,
                                   threads=max(1, min(args.num_workers, 16)))
-    if args.r2l_online_kd or args.r2l_device_store or args.r2l_store_load:
+    if args.r2l_online_kd or args.r2l_device_store or args.r2l_store_load or args.r2l_image_store:
         loader.n_files = shards[rank]
         logger.info("ray store: %s" % loader.describe())
         if start > 0:  # --resume: the sampler is a pure function of (seed, shard count, draw): only the counter is restored
@@ -807,6 +840,7 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
 def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
+    validate_image_store(args)
     validate_fused_iter(args)
     validate_compact_store(args)
     validate_store_file(args)
@@ -911,10 +945,15 @@ def main(argv=None):
         return {"ms_per_frame": per * 1e3, "logger": logger}
 
     # ---------------- distillation training (data_mode rays) ----------------
-    if not (args.r2l_online_kd or args.r2l_store_load) and (args.data_mode != "rays" or not args.datadir_kd):
+    if not (args.r2l_online_kd or args.r2l_store_load or args.r2l_image_store) and (args.data_mode != "rays" or not args.datadir_kd):
         raise NotImplementedError("training on the accelerated path needs --data_mode rays --datadir_kd <dir of "
                                   "[4096,9] .npy ray shards> (README step 3/5), or --r2l_online_kd (the teacher renders into a "
                                   "device-resident ray store)")
+    if args.r2l_image_store:
+        # what the real group will hold is arithmetic on the loaded split: named, and checked against one step's draw, before
+        # anything is allocated (and before a run without a GPU is turned away below)
+        from .image_store import plan_image_store
+        plan_image_store(args, len(i_train), H, W, rank, world, logger)
     if device.type != "cuda":
         raise RuntimeError("R2L training runs on the HIP path and needs a ROCm GPU")
     # --N_rand is the GLOBAL batch in shard files per step, as in the reference (its DataLoader builds one batch that

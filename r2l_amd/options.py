@@ -71,6 +71,12 @@ FLAGS = {
     # r2l_store_load: a third source of main.py's training beside r2l_online_kd and r2l_device_store; the kind comes from the
     # file.  The name is the path at world size 1, <path>.rank<r>of<w> otherwise.  utils/train_nerf.py ignores both
     "r2l_store_save": (str, ""), "r2l_store_load": (str, ""),
+    # r2l_image_store: the store holds the REAL training rays of --datadir — the images and poses the loader already has, turned
+    # into shuffled [o, d, rgb] rows on the device (r2l_amd/image_store.py, r2l_store_append_images): the fine-tuning stage
+    # (README step 5) without the converter's files and without --datadir_kd.  With r2l_online_kd (r2l_kd_every 0) the real
+    # group goes behind the teacher's groups: one store of real and pseudo rows.  Not with r2l_device_store / r2l_store_load
+    # (one more source of rays), r2l_compact_store or r2l_kd_every > 0.  utils/create_data.py / utils/train_nerf.py ignore it
+    "r2l_image_store": ("flag", False),
     # forward-facing LLFF scenes (--dataset_type llff: --factor, --llffhold, --no_ndc; NDC rays through r2l_ndc_rays); opt-in —
     # without the switch --dataset_type llff is refused as it always was.  configs/fern.txt and its kin carry it
     "r2l_llff": ("flag", False),
@@ -273,6 +279,23 @@ def validate_compact_store(args):
         raise ValueError("--r2l_compact_store needs --r2l_online_kd (the teacher fills the store)")
 
 
+def validate_image_store(args):
+    """--r2l_image_store (main.py only; the sibling entry points accept and ignore it): the real training rays as a flush group
+    of a plain store, alone or behind the teacher's groups.  Names the other flag, before anything is loaded."""
+    if not args.r2l_image_store:
+        return
+    for other in ("r2l_device_store", "r2l_store_load"):
+        if getattr(args, other):
+            raise ValueError("--r2l_image_store fills the store from the training images of --datadir: not with --%s (--r2l_online_kd "
+                             "may fill the same store; a third source of rays may not: give one)" % other)
+    if args.r2l_compact_store:
+        raise ValueError("--r2l_image_store writes plain 36-byte rows: not with --r2l_compact_store, whose rows carry the rays of "
+                         "teacher frames")
+    if args.r2l_kd_every > 0:
+        raise ValueError("--r2l_image_store appends the real rays behind a COMPLETE teacher fill: not with --r2l_kd_every %d (give "
+                         "--r2l_kd_every 0)" % args.r2l_kd_every)
+
+
 def validate_store_file(args):
     """--r2l_store_save / --r2l_store_load as main.py takes them (utils/create_data.py has its own use of --r2l_store_save,
     utils/train_nerf.py ignores both).  Names the other flag, before anything is loaded."""
@@ -282,7 +305,7 @@ def validate_store_file(args):
                 raise ValueError("--r2l_store_load takes the store from a file: not with --%s (one source of rays per run, and a "
                                  "loaded store is not saved again)" % other)
     if args.r2l_store_save:
-        if not args.r2l_online_kd:
+        if not (args.r2l_online_kd or args.r2l_image_store):
             raise ValueError("--r2l_store_save writes the store the teacher fills: it needs --r2l_online_kd (or "
                              "utils/create_data.py --create_data rand, which renders into a store and writes the file)")
         if args.r2l_kd_every > 0:
@@ -295,7 +318,7 @@ def validate_fused_iter(args, world=1, device_type="cuda"):
     the pool's rows itself, on one GPU.  Names what is missing before anything is loaded."""
     if not args.r2l_fused_iter:
         return
-    if not (args.r2l_device_store or args.r2l_online_kd or args.r2l_store_load):
+    if not (args.r2l_device_store or args.r2l_online_kd or args.r2l_store_load or args.r2l_image_store):
         raise ValueError("--r2l_fused_iter draws its batches from a ray store: it needs --r2l_device_store or --r2l_online_kd")
     if args.hard_ratio and not args.r2l_device_pool:
         raise ValueError("--r2l_fused_iter with --hard_ratio needs --r2l_device_pool (the hard rays are ranked inside the call)")

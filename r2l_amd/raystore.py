@@ -77,6 +77,23 @@ def cstore_append_spec(rgb, rays_per_shard, key, shuffle=True):
     return np.ascontiguousarray(rgb[src]), src.astype(np.uint32)
 
 
+def append_images_spec(images, c2ws, focals, rays_per_shard, key, shuffle=True):
+    """What r2l_store_append_images writes into its new shards, in numpy: images [K, H, W, 3], c2ws [K, 3, 4], focals [K] or one
+    number -> float32[m * rays_per_shard, 9] with m = K*H*W // rays_per_shard: row i is [o, d, rgb] of ray r = perm(key, K*H*W)[i],
+    (o, d) = pixel_ray_spec of pose r // (H*W) at pixel ((r % (H*W)) // W, r % W), rgb = images.reshape(-1, 3)[r]; the tail of
+    the permuted sequence is dropped.  shuffle=False: the identity."""
+    images = np.asarray(images, dtype=np.float32)
+    K, H, W = images.shape[:3]
+    c2ws = np.asarray(c2ws, dtype=np.float32).reshape(K, 3, 4)
+    focals = np.broadcast_to(np.asarray(focals, dtype=np.float32).reshape(-1), (K,))
+    n_rows, hw = K * H * W, H * W
+    n_out = n_rows // int(rays_per_shard) * int(rays_per_shard)
+    src = perm_at(key, n_rows, np.arange(n_out, dtype=np.uint64)) if shuffle else np.arange(n_out, dtype=np.int64)
+    k, pix = src // hw, src % hw
+    o, d = pixel_ray_spec(c2ws[k], focals[k], H, W, pix // W, pix % W)
+    return np.concatenate([o, d, images.reshape(-1, 3)[src]], 1)
+
+
 def cstore_batch_spec(rgb_rows, ids, pose_c2w, pose_focal, shard_pose0, H, W, n_shards, rays_per_shard, draw0, n_draw, seed):
     """What r2l_cstore_batch writes, in numpy: (batch float32[n_draw * rays_per_shard, 9], shard ids int32[n_draw]).  rgb_rows
     [>= n_shards * rays_per_shard, 3] and ids (uint32, same length) are the store's rows, pose_c2w [n_pose, 3, 4] / pose_focal
@@ -203,6 +220,55 @@ class RayStore(_Store):
                                             self.rows_per_file, int(key) & M64, int(bool(shuffle)), ctypes.byref(m),
                                             _stream(self.device)), "r2l_store_append")
         return self._appended(m.value)
+
+    def append_images(self, images, c2ws, focals, key, shuffle=True):
+        """Append the real rays of K whole frames as ONE flush group (r2l_store_append_images): images [K, H, W, 3] fp32, c2ws
+        [K, 3|4, 4], focals [K] fp32 tensor or one number for all K.  floor(K*H*W / rays_per_shard) shards of rows [o, d, rgb],
+        o, d the pixels' rays in r2l_frame_rays' arithmetic, shuffled by perm(key, K*H*W) as append() shuffles.  Images on the
+        store's device go through the kernel; images on the CPU go through append_images_spec and the rows are uploaded.  Returns
+        the number of shards written."""
+        if self.data is None:
+            raise RuntimeError("RayStore is closed")
+        c2ws = torch.as_tensor(c2ws, dtype=torch.float32)
+        if c2ws.dim() != 3 or c2ws.shape[0] < 1 or c2ws.shape[1] not in (3, 4) or c2ws.shape[2] != 4:
+            raise ValueError("RayStore.append_images: need c2ws [K, 3|4, 4], K >= 1")
+        K = c2ws.shape[0]
+        if (not torch.is_tensor(images) or images.dtype != torch.float32 or images.dim() != 4 or images.shape[0] != K
+                or images.shape[3] != 3 or images.shape[1] < 1 or images.shape[2] < 1):
+            raise ValueError("RayStore.append_images: need images [K, H, W, 3] = [%d, H, W, 3] fp32" % K)
+        on_host = images.device.type == "cpu"
+        if not on_host and images.device != self.device:
+            raise ValueError("RayStore.append_images: images are on %s, the store on %s (CPU images go through the numpy "
+                             "restatement)" % (images.device, self.device))
+        H, W = int(images.shape[1]), int(images.shape[2])
+        fdev, f = None, 0.
+        if torch.is_tensor(focals):
+            if focals.dtype != torch.float32 or tuple(focals.shape) != (K,):
+                raise ValueError("RayStore.append_images: need focals [K] fp32, or one number")
+            fdev = focals
+        else:
+            f = float(focals)
+            if not f > 0.:
+                raise ValueError("RayStore.append_images: need focal > 0 (got %r)" % (focals,))
+        rps = self.rows_per_file
+        m = K * H * W // rps
+        if self.n_shards + m > self.capacity:
+            raise ValueError("RayStore.append_images: %d shards of %d x %d x %d pixels do not fit behind %d shards in a store of %d" %
+                             (m, K, H, W, self.n_shards, self.capacity))
+        if on_host:
+            rows = append_images_spec(images.numpy(), c2ws[:, :3, :4].cpu().numpy(), fdev.cpu().numpy() if fdev is not None else f,
+                                      rps, int(key) & M64, shuffle)
+            self.data[self.n_shards * rps:(self.n_shards + m) * rps].copy_(torch.from_numpy(rows))
+            return self._appended(m)
+        images = images.contiguous()
+        c2ws = c2ws.to(self.device)[:, :3, :4].contiguous()
+        if fdev is not None:
+            fdev = fdev.to(self.device).contiguous()
+        n = ctypes.c_int64()
+        _lib.check(self._L.r2l_store_append_images(_p(images), _p(c2ws), _p(fdev), f, K, H, W, _p(self.data), self.capacity,
+                                                   self.n_shards, rps, int(key) & M64, int(bool(shuffle)), ctypes.byref(n),
+                                                   _stream(self.device)), "r2l_store_append_images")
+        return self._appended(n.value)
 
     def append_files(self, files, threads=4):
         """Read every listed [rays_per_shard, 9] .npy shard ONCE, in list order, through two pinned group buffers into the

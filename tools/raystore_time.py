@@ -12,7 +12,10 @@ python tools/raystore_time.py [loop] [draw] [files] [fill] [--reps 3] [--poses 1
 python tools/raystore_time.py --compact [--reps 3] [--poses 100]   the compact store (CompactRayStore, 16 B/ray) against the plain
          one: next(20) / next(1), a flush group of fill_group, memory after the fill -> profiles/cstore.txt (compact() below)
 python tools/raystore_time.py --file [--reps 3] [--poses 100]   the store file: r2l_words_digest against a device copy, save and
-         load of a plain and a compact store -> profiles/store_file.txt (store_file() below)"""
+         load of a plain and a compact store -> profiles/store_file.txt (store_file() below)
+python tools/raystore_time.py --images [--reps 3] [--poses 100]   the real rays of --poses frames at 400 x 400 into a store:
+         RayStore.append_images (one launch) against r2l_frame_rays + rgb copy + r2l_store_append, and against the converter's files
+         read back by append_files -> profiles/image_store.txt (images() below)"""
 import argparse
 import os
 import shutil
@@ -308,6 +311,107 @@ def store_file(reps, n_pose, out_path):
         f.write("\n".join(lines) + "\n")
 
 
+def images(reps, n_frames, out_path):
+    """--images: the real training rays of n_frames frames at 400 x 400 as store rows, all in this process, `reps` rounds
+    alternating the routes; medians and the spread (max - min) between the rounds of the same route.
+      one launch     RayStore.append_images (r2l_store_append_images): device events around 10 calls; GB/s against 48 B a ray
+                     (12 gathered, 36 written)
+      three launches r2l_frame_rays(rows) + the rgb copy into columns 6..8 + r2l_store_append, the [n, 9] intermediate allocated
+                     once outside the timing; the same 48 B a ray as the yardstick (it moves 24 + 24 + 72 B more)
+      files          data.convert_images_to_ray_shards on the same frames as PNGs (wall time, reading the PNGs included) plus
+                     RayStore.append_files of what it wrote: the route of the parent commit"""
+    import ctypes
+    import json
+    from PIL import Image
+    from r2l_amd import _lib
+    H = W = 400
+    K, focal, key = n_frames, 555.5555155968841, 0x1234567
+    lines = ["tools/raystore_time.py --images --reps %d --poses %d   (%s)" % (reps, K, torch.cuda.get_device_name(0))]
+    say = lambda s: (lines.append(s), print(s))
+    rng = np.random.RandomState(0)
+    png = (rng.rand(K, H, W, 4) * 255).astype(np.uint8)
+    poses = torch.stack([data.get_rand_pose(rng) for _ in range(K)], 0).float()
+    rgba = torch.from_numpy(png.astype(np.float32) / 255.)
+    imgs = (rgba[..., :3] * rgba[..., -1:] + (1. - rgba[..., -1:])).cuda().contiguous()  # the loader's composite on white
+    c2ws = poses[:, :3, :4].cuda().contiguous()
+    n, cap = K * H * W, K * H * W // 4096
+    L, lib = _lib, _lib.load()
+    p = lambda t: ctypes.c_void_p(t.data_ptr())
+    st = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    new, old = RayStore(cap, "cuda"), RayStore(cap, "cuda")
+    rows = torch.empty(n, 9, device="cuda")
+
+    def reset(s):
+        s.n_shards, s.files = 0, []
+
+    def one():
+        reset(new)
+        new.append_images(imgs, c2ws, focal, key)
+
+    def three():
+        reset(old)
+        L.check(lib.r2l_frame_rays(p(c2ws), None, focal, K, H, W, None, None, None, p(rows), st), "r2l_frame_rays")
+        rows[:, 6:9] = imgs.view(-1, 3)
+        old.append(rows, key)
+
+    one()
+    three()
+    assert torch.equal(new.shards(), old.shards())  # the same store bit for bit
+    ms = {"one": [], "three": []}
+    for r in range(reps):
+        ms["one"].append(_ms_per_call(one, calls=10))
+        ms["three"].append(_ms_per_call(three, calls=10))
+    a, b = np.array(ms["one"]), np.array(ms["three"])
+    say("%d frames at %dx%d = %d rays -> %d shards of 4096 (%.3f GB of rows), %d rounds alternating, 10 calls a round, device events" %
+        (K, H, W, n, cap, cap * 4096 * 36 / 1e9, reps))
+    say("one launch (r2l_store_append_images):                   %s ms (median %.3f, spread %.3f) = %.0f GB/s at 48 B a ray" %
+        (np.round(a, 3).tolist(), np.median(a), a.max() - a.min(), n * 48 / np.median(a) / 1e6))
+    say("three launches (r2l_frame_rays + rgb copy + r2l_store_append): %s ms (median %.3f, spread %.3f) = %.0f GB/s at 48 B a ray" %
+        (np.round(b, 3).tolist(), np.median(b), b.max() - b.min(), n * 48 / np.median(b) / 1e6))
+    say("one - three = %+.3f ms (spread of the three-launch route %.3f ms): the one launch is %s" %
+        (np.median(a) - np.median(b), b.max() - b.min(),
+         "not slower beyond that spread" if np.median(a) - np.median(b) <= b.max() - b.min() else "SLOWER beyond that spread"))
+    old.close()
+    del rows, old
+    torch.cuda.empty_cache()
+    # ---- the file route of the parent commit ----
+    tmp = tempfile.mkdtemp(prefix="r2l_images_")
+    scene = os.path.join(tmp, "scene")
+    os.makedirs(os.path.join(scene, "train"))
+    t0 = time.perf_counter()
+    for i in range(K):
+        Image.fromarray(png[i]).save(os.path.join(scene, "train", "r_%d.png" % i), compress_level=1)
+    with open(os.path.join(scene, "transforms_train.json"), "w") as f:
+        json.dump({"camera_angle_x": 0.6911112070083618,
+                   "frames": [{"file_path": "./train/r_%d" % i, "transform_matrix": poses[i].tolist()} for i in range(K)]}, f)
+    t_png = time.perf_counter() - t0
+    conv, load = [], []
+    for r in range(reps):
+        t0 = time.perf_counter()
+        kd, n_files = data.convert_images_to_ray_shards(scene, full_res=True, white_bkgd=True, rng=np.random.RandomState(r))
+        conv.append(time.perf_counter() - t0)
+        paths = [os.path.join(kd, "train_%d.npy" % (k + 1)) for k in range(n_files)]
+        reset(new)
+        torch.cuda.synchronize()
+        t0 = time.perf_counter()
+        new.append_files(paths, threads=8)
+        torch.cuda.synchronize()
+        load.append(time.perf_counter() - t0)
+        shutil.rmtree(kd)
+    c, l = np.array(conv), np.array(load)
+    say("files (utils/convert_original_data_to_rays_blender.py's work + --r2l_device_store's load), %d files: converter %s s (median "
+        "%.2f, spread %.2f; it reads the %d PNGs, written here in %.1f s) + append_files %s s (median %.3f) = %.2f s against %.3f ms" %
+        (cap, np.round(c, 2).tolist(), np.median(c), c.max() - c.min(), K, t_png, np.round(l, 3).tolist(), np.median(l),
+         np.median(c) + np.median(l), np.median(a)))
+    say("the file system is a temporary directory of the machine (%s): the load reads what the converter just wrote (page cache); "
+        "every route also decodes the PNGs once (the loader does for the one launch); not measured: 800x800 frames" % tempfile.gettempdir())
+    new.close()
+    shutil.rmtree(tmp)
+    os.makedirs(os.path.dirname(out_path), exist_ok=True)
+    with open(out_path, "w") as f:
+        f.write("\n".join(lines) + "\n")
+
+
 if __name__ == "__main__":
     ap = argparse.ArgumentParser()
     ap.add_argument("what", nargs="*", default=["draw", "files", "loop", "fill"])
@@ -316,9 +420,15 @@ if __name__ == "__main__":
     ap.add_argument("--chunk", type=int, default=50)
     ap.add_argument("--compact", action="store_true", help="compact store against the plain one -> profiles/cstore.txt")
     ap.add_argument("--file", action="store_true", help="store file: digest, save and load rates -> profiles/store_file.txt")
-    ap.add_argument("--out", default=None, help="default: profiles/cstore.txt (--compact), profiles/store_file.txt (--file)")
+    ap.add_argument("--images", action="store_true", help="real rays from images: one launch against three and against files -> "
+                    "profiles/image_store.txt")
+    ap.add_argument("--out", default=None, help="default: profiles/cstore.txt (--compact), profiles/store_file.txt (--file), "
+                    "profiles/image_store.txt (--images)")
     a = ap.parse_args()
-    a.out = a.out or os.path.join(ROOT, "profiles", "store_file.txt" if a.file else "cstore.txt")
+    a.out = a.out or os.path.join(ROOT, "profiles", "image_store.txt" if a.images else "store_file.txt" if a.file else "cstore.txt")
+    if a.images:
+        images(a.reps, a.poses, a.out)
+        sys.exit(0)
     if a.file:
         store_file(a.reps, a.poses, a.out)
         sys.exit(0)
