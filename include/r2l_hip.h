@@ -457,6 +457,69 @@ int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_dev, int K, 
                            float* rows /*[K*H*W,9] o,d,rgb or NULL*/, float* rgb, float* disp, float* acc, float* depth,
                            float* rgb0 /*each [K*H*W(,3)] or NULL*/, float* work, void* stream, const r2l_config* cfg);
 
+/* ---- occupancy grid of the teacher's render (skip the samples that lie in empty space) ------------------------------------------
+ * In a bounded scene most sample points of a ray lie where the trained sigma pre-activation is negative; r2l_raw2outputs turns
+ * those into alpha = 0 exactly, so they add exactly nothing to a frame.  A grid of one bit per cell over a box records where sigma
+ * can be positive; the samples of a launch whose cell is empty are left out of the point network (csrc/r2l_occupancy.hip):
+ *   r2l_occ_compact -> r2l_teacher_mlp_cfg on the M live samples as M rows with S = 1 -> r2l_occ_scatter -> r2l_raw2outputs.
+ * No point-network kernel is involved beyond being called.  All calls are stateless, check their arguments before any launch
+ * (hipErrorInvalidValue, r2l_last_error names the argument), enqueue on `stream`, never synchronise and use no atomics: every
+ * output position comes from a scan, and the same arguments give the same bits.  r2l_amd/occupancy.py (build_spec, compact_spec,
+ * scatter_spec) restates the three calls in numpy.
+ *
+ * The grid is CALLER-OWNED.  bits: device, r2l_occ_bits_words(G) = ceil(G^3 / 32) words; cell (cx, cy, cz) is bit (i & 31) of word
+ * (i >> 5), i = (cz*G + cy)*G + cx; the padding bits of the last word are zero.  r2l_occ_grid_init fills the fields in host fp32:
+ *   inv[a] = (float)G / (hi[a] - lo[a]);   step[a] = (hi[a] - lo[a]) / (float)(G*k)      (hi - lo rounded first)
+ * and refuses G < 1, G > 512, k < 1, k > 4, lo[a] >= hi[a], a value that is not finite and NULL pointers.
+ * The cell of a point p is c[a] = (int)floorf((p[a] - lo[a]) * inv[a]), difference and product rounded separately (no FMA).  The
+ * point is inside iff 0 <= c[a] < G on all three axes; a NaN or infinite coordinate is outside.  A point outside the box is
+ * ALWAYS LIVE; a point inside is live iff its cell's bit is set.  (A point at hi[a] is outside whenever (hi - lo) * inv rounds to
+ * G, which holds for the boxes whose side and G are powers of two; the rule above decides, not the real-number box.) */
+typedef struct r2l_occ_grid {
+    uint32_t* bits;
+    int G;
+    float lo[3], inv[3], step[3];
+    int reserved[2];               /* must be 0 */
+} r2l_occ_grid;
+int64_t r2l_occ_bits_words(int G);   /* -1 outside 1 .. 512 */
+int r2l_occ_grid_init(r2l_occ_grid* grid, uint32_t* bits, int G, int k, const float* lo /*host [3]*/, const float* hi /*host [3]*/);
+
+/* Fills grid->bits from the network (wstream, tparams: as r2l_teacher_mlp_cfg; cfg picks the kernel family, NULL = default).
+ * Probe (c, j), c < G, j < k, of axis a sits at lo[a] + ((float)(c*k + j) + 0.5f) * step[a] (sum, product, sum rounded separately);
+ * probe (px, py, pz), p = c*k + j, has the place (pz*G*k + py)*G*k + px in PROBE ORDER.  The sigma pre-activation (raw[..., 3]) of
+ * all (G k)^3 probes comes from r2l_teacher_mlp_cfg on rows with S = 1: rays_o = probe, rays_d = 0, z = 0 (the point is the probe,
+ * bit for bit), viewdirs = (0, 0, 1) — sigma does not depend on the view direction.  They run in slabs of whole cells through
+ * `work` (16-byte aligned, r2l_occ_build_work_floats(G, k) floats; -1 for a G or k out of range), a point's sigma does not depend
+ * on the slab it is in.  A cell is occupied iff any of its k^3 probes has sigma > sigma_thresh (a NaN sigma is not above
+ * anything).  The bits are then dilated by `dilate` cells: a cell's bit is the maximum over the (2 dilate + 1)^3 box of cells around
+ * it, clipped at the grid's faces (three one-axis passes).  sigma_out, optional: [(G k)^3] floats in probe order, the very
+ * values the bits were made from.  k must be the k given to r2l_occ_grid_init (it set step).
+ * Refused: a NULL grid / bits / wstream / tparams / work, G < 1, G > 512, k < 1, k > 4, dilate < 0, a NaN sigma_thresh, inv or step
+ * not positive and finite (lo >= hi), non-zero reserved, work not 16-byte aligned, an invalid cfg. */
+int64_t r2l_occ_build_work_floats(int G, int k);
+int r2l_occ_build(r2l_occ_grid* grid, int k, int dilate, float sigma_thresh, const float* wstream, const float* tparams,
+                  const r2l_config* cfg, float* work, float* sigma_out /*[(G k)^3] or NULL*/, void* stream);
+
+/* The live samples of rays [R] with depths z[R,S].  Sample n = r*S + s is live iff the fp32 point rays_o[r] + rays_d[r] * z[n]
+ * (product and sum rounded separately, exactly as r2l_teacher_mlp_cfg forms it) is live by the rule above.  *count_out (device
+ * int64) = the number M of live samples; idx_out[0..M) = their n in ASCENDING order; row i < M of out_o / out_d / out_v [.,3] and
+ * out_z [.] = rays_o[r], rays_d[r], viewdirs[r] and z[n] of sample idx_out[i], copied: the arguments of r2l_teacher_mlp_cfg with
+ * R = M, S = 1.  All outputs have capacity R*S; rows >= M are not written.  work: r2l_occ_compact_work_bytes(R*S) bytes (-1 for
+ * R*S < 0 or >= 2^31), 4-byte aligned.  Three launches: count per 2048 samples, scan of the counts, placement.
+ * R == 0 is a successful no-op that sets *count_out = 0.  Refused: a NULL grid / pointer, R < 0, S < 1, R*S >= 2^31, a grid that
+ * r2l_occ_build would refuse. */
+int64_t r2l_occ_compact_work_bytes(int64_t n_samples);
+int r2l_occ_compact(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                    int64_t R, int S, float* out_o, float* out_d, float* out_v, float* out_z, int64_t* idx_out,
+                    int64_t* count_out, void* work, void* stream);
+
+/* raw_out[R,S,4] = 0 everywhere (a memset: sigma = +0 -> alpha = 0), then raw_out[idx[i]] = raw_live[i] for i < M (idx: distinct
+ * sample numbers in [0, R*S), as r2l_occ_compact writes them; a number outside that range writes nothing).  M == 0 leaves the zero
+ * fill alone; R == 0 is a successful no-op.  raw_live and raw_out 16-byte aligned.  Refused: R < 0, S < 1, R*S >= 2^31, M < 0,
+ * M > R*S, a NULL or misaligned pointer. */
+int r2l_occ_scatter(const float* raw_live /*[M,4]*/, const int64_t* idx /*[M]*/, int64_t M, float* raw_out, int64_t R, int S,
+                    void* stream);
+
 /* ---- test-set metric ------------------------------------------------------------------------------------------------
  * out[0] = SSIM(img1, img2): utils/ssim_torch.py:28-56,86-94 as called at main.py:46,254,334 (11x11 Gaussian sigma 1.5,
  * zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over every pixel and channel), fused into one kernel + a fixed-order

@@ -79,6 +79,14 @@ class PoseRefineDesc(ctypes.Structure):
 _posep = ctypes.POINTER(PoseRefineDesc)
 
 
+class OccGridDesc(ctypes.Structure):
+    """r2l_occ_grid of include/r2l_hip.h (r2l_occ_build / r2l_occ_compact): 56 bytes."""
+    _fields_ = [("bits", _p), ("G", _i), ("lo", _f * 3), ("inv", _f * 3), ("step", _f * 3), ("reserved", _i * 2)]
+
+
+_occp = ctypes.POINTER(OccGridDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -154,6 +162,13 @@ SIGNATURES = {
     "r2l_frame_rays": (_i, [_p, _p, _f, _i, _i, _i, _p, _p, _p, _p, _p]),
     "r2l_teacher_frames_work_floats": (_l, [_descp]),
     "r2l_teacher_frames_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 14 + [_cfgp]),
+    "r2l_occ_bits_words": (_l, [_i]),
+    "r2l_occ_grid_init": (_i, [_occp, _p, _i, _i, _p, _p]),
+    "r2l_occ_build_work_floats": (_l, [_i, _i]),
+    "r2l_occ_build": (_i, [_occp, _i, _i, _f, _p, _p, _cfgp, _p, _p, _p]),
+    "r2l_occ_compact_work_bytes": (_l, [_l]),
+    "r2l_occ_compact": (_i, [_occp] + [_p] * 4 + [_l, _i] + [_p] * 8),
+    "r2l_occ_scatter": (_i, [_p, _p, _l, _p, _l, _i, _p]),
     "r2l_ssim_partial_count": (_l, [_i, _i, _i]),
     "r2l_ssim": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "r2l_flip_partial_count": (_l, [_i, _i, _i]),

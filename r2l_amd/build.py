@@ -27,10 +27,11 @@ FLAGS = EXTRA + ["--offload-arch=gfx950", "-O3", "-std=c++17", "-fPIC", "-ffp-co
 # whose rounding order is part of the interface; nothing there is worth packing.  r2l_cstore.hip: the compact ray store recomputes
 # those very rays (csrc/r2l_pixel_ray.h) and must give the same bits, so it is built exactly as r2l_teacher_frame.hip is; so is
 # r2l_pose.hip, whose r2l_pose_batch writes the rows of r2l_image_batch through the same pixel_ray, and r2l_image_store.hip, whose
-# rows are those of r2l_frame_rays bit for bit.
+# rows are those of r2l_frame_rays bit for bit.  r2l_occupancy.hip: three independent per-axis chains (probe positions, cell of a
+# point) with a pinned rounding order and nothing worth packing.
 FILE_FLAGS = {"r2l_flip.hip": ["-fno-slp-vectorize"], "r2l_teacher_frame.hip": ["-fno-slp-vectorize"],
               "r2l_cstore.hip": ["-fno-slp-vectorize"], "r2l_pose.hip": ["-fno-slp-vectorize"],
-              "r2l_image_store.hip": ["-fno-slp-vectorize"]}
+              "r2l_image_store.hip": ["-fno-slp-vectorize"], "r2l_occupancy.hip": ["-fno-slp-vectorize"]}
 
 
 def _sources():

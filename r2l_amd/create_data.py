@@ -23,7 +23,7 @@ from .checkpoint import load_weights
 from .driver import _runs, apply_arithmetic, init_distributed, sync
 from .logger import Logger
 from .nerf_raybased import NeRF
-from .options import parse_args, validate_accelerated
+from .options import parse_args, validate_accelerated, validate_occupancy
 from .render import get_embedder, get_rays, render, render_frames, run_network
 
 
@@ -113,6 +113,10 @@ def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device
 def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
+    validate_occupancy(args)
+    if args.r2l_occupancy and args.r2l_store_save:
+        raise ValueError("--r2l_occupancy: not with --r2l_store_save, which renders through the fused frames call (no host read of "
+                         "the live count)")
     if args.create_data != "rand":
         raise NotImplementedError("only --create_data rand (the README pipeline) is on the accelerated path")
     rank, world, device = init_distributed()
@@ -135,6 +139,10 @@ def main(argv=None):
     coarse, fine = create_teacher(args, device)
     apply_arithmetic(args, device, logger, teachers=(coarse, fine))  # --r2l_precision: the teacher kernels' arithmetic
     kwargs = teacher_render_kwargs(args, coarse, fine, ndc=ndc)
+    occ_pair = None
+    if args.r2l_occupancy:  # both grids once, behind --r2l_precision: every per-pose render below skips the empty samples
+        from .occupancy import build_pair, log_live
+        occ_pair = kwargs["occupancy"] = build_pair(args, coarse, fine, near, far, logger)
     if args.test_teacher:
         # "Testing teacher..." (create_data.py:723-741): the test views through render_path with render_kwargs_test (perturb =
         # --perturb_test, raw_noise_std = 0), Loss / PSNR logged before any data is generated; frames sharded over the ranks
@@ -265,4 +273,6 @@ def main(argv=None):
     th.join()
     if errors:
         raise errors[0]
+    if occ_pair is not None:
+        log_live(occ_pair, logger)
     return {"n_rays": n_rays, "datadir": datadir_new, "logger": logger}

@@ -19,7 +19,7 @@ from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import (parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_image_store,
-                      validate_store_file)
+                      validate_occupancy, validate_store_file)
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -850,6 +850,8 @@ def main(argv=None):
         raise NotImplementedError("--model_name nerf: the accelerated path renders a pretrained teacher (--render_only, with or "
                                   "without --render_test / --test_pretrained) and uses it in utils/create_data.py; TRAINING "
                                   "the teacher runs through utils/train_nerf.py")
+    if is_teacher:
+        validate_occupancy(args, raw_noise_std=0.)  # (the teacher's test render runs without noise; student runs ignore the switch)
     rank, world, device = init_distributed()
     if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
         raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
@@ -886,6 +888,9 @@ def main(argv=None):
                        fused=args.r2l_fused_frames)
         history = {"start": 0, "best_psnr": 0, "best_psnr_step": 0}
         r2l_config = apply_arithmetic(args, device, logger, teachers=(model, kwargs_test["network_fine"]))
+        if args.r2l_occupancy:  # both grids once, behind --r2l_precision
+            from .occupancy import build_pair
+            kwargs_test["occupancy"] = build_pair(args, model, kwargs_test["network_fine"], near, far, logger)
     else:
         model, embedder, history, ckpt = create_r2l(args, device, logger)
         point_sampler = PointSampler(H, W, focal, args.n_sample_per_ray, near, far, device=device)
@@ -922,6 +927,9 @@ def main(argv=None):
         dt = time.time() - t_
         logger.info("Rendered %d frames (%d rays) in %.2fs on rank %d = %.0f rays/s incl. I/O; frames in %s" %
                     (rgbs.shape[0], n_rays, dt, rank, n_rays / max(dt, 1e-9), logger.gen_img_path))
+        if teacher is not None and "occupancy" in teacher["render_kwargs"]:
+            from .occupancy import log_live
+            log_live(teacher["render_kwargs"]["occupancy"], logger)
         # (the reference writes the video of whichever frames it rendered — test views too, main.py:1096-1097)
         video_path = save_video(rgbs, logger, expid, iter_, args.video_tag, rank, world, device)
         if "errors" in misc:  # (main.py:1098-1102: the |rgb - gt| frames as a second video)

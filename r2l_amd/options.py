@@ -54,6 +54,13 @@ FLAGS = {
     # teacher frames (create_data, the teacher's test render) through ONE library call per group of poses
     # (r2l_teacher_frames_cfg: rays, draws and all stages behind the C ABI) instead of render()'s per-pose assembly; opt-in
     "r2l_fused_frames": ("flag", False),
+    # occupancy grid of the teacher's per-pose render (r2l_amd/occupancy.py; r2l_occ_build / r2l_occ_compact / r2l_occ_scatter):
+    # the sample points in cells where the trained sigma is not positive skip the point network; opt-in.  r2l_occ_res: cells per
+    # axis; r2l_occ_bound: half side of the cube about the origin, 0 = 0.625 (far - near), 2.5 for the Blender scenes.  Honoured by
+    # utils/create_data.py --create_data rand, --test_teacher and main.py --model_name nerf --render_only; not with
+    # --r2l_fused_frames / --r2l_online_kd (the frames call has no host read of the live count), --dataset_type llff (NDC space
+    # needs its own box) or raw_noise_std > 0.  utils/train_nerf.py and student training ignore the three
+    "r2l_occupancy": ("flag", False), "r2l_occ_res": (int, 128), "r2l_occ_bound": (float, 0.),
     # device-resident ray store (r2l_amd/raystore.py): training draws its shards from HBM with one launch per step.
     # r2l_device_store: the shard files of --datadir_kd are read once into the store.  r2l_online_kd: no files at all, the
     # teacher (--teacher_ckpt, described by the config file --r2l_teacher_config) renders --n_pose_kd poses into the store, all
@@ -262,6 +269,30 @@ def validate_ray_store(args):
         raise ValueError("--r2l_kd_every needs --r2l_online_kd")
     if args.r2l_device_store and (args.data_mode != "rays" or not args.datadir_kd):
         raise ValueError("--r2l_device_store needs --data_mode rays and --datadir_kd")
+
+
+def validate_occupancy(args, raw_noise_std=None):
+    """--r2l_occupancy as the per-pose teacher renders take it (utils/create_data.py, main.py --model_name nerf --render_only;
+    training entry points accept and ignore it).  raw_noise_std: the value the renders will run with (default: --raw_noise_std;
+    the test renders pass 0).  Names the other flag, before anything is loaded."""
+    if not args.r2l_occupancy:
+        return
+    for other in ("r2l_fused_frames", "r2l_online_kd"):
+        if getattr(args, other):
+            raise ValueError("--r2l_occupancy skips samples after a host read of the live count: not with --%s, whose frames call "
+                             "enqueues every stage without one (a device-side count is the follow-up)" % other)
+    if args.dataset_type == "llff":
+        raise ValueError("--r2l_occupancy puts its box about the origin of a bounded scene: not with --dataset_type llff (NDC "
+                         "space needs a box of its own)")
+    if (args.raw_noise_std if raw_noise_std is None else raw_noise_std) > 0:
+        raise ValueError("--r2l_occupancy with raw_noise_std > 0: noise can lift a skipped sample above zero (pass "
+                         "--raw_noise_std 0)")
+    if not 1 <= args.r2l_occ_res <= 512:
+        raise ValueError("--r2l_occ_res must be in 1 .. 512, got %d" % args.r2l_occ_res)
+    if args.r2l_occ_bound < 0:
+        raise ValueError("--r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
+    if not args.use_viewdirs:
+        raise ValueError("--r2l_occupancy needs --use_viewdirs (the teacher kernels' network)")
 
 
 def validate_compact_store(args):

@@ -323,17 +323,29 @@ def _coarse_z(near, far, N_samples, lindisp, perturb, pytest, t_rand=None):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                t_rand=None, u=None):
+                t_rand=None, u=None, occupancy=None):
     """Volumetric rendering of ray_batch[R, 8|11] = [o, d, near, far, (viewdirs)]  (create_data.py:405-544).
     Returns the reference's dict: rgb_map, disp_map, acc_map, depth_map, (raw), and with N_importance > 0 also
-    rgb0, disp0, acc0, z_std.  t_rand / u override the random draws (tests)."""
+    rgb0, disp0, acc0, z_std.  t_rand / u override the random draws (tests).
+    occupancy = (grid_for_network_fn, grid_for_network_fine), two built r2l_amd.occupancy.OccupancyGrid: only the samples that are
+    live in the pass's grid go through the point network, the others keep raw = 0 (OccupancyGrid.query: compact, one 8-byte read
+    of the live count — the one synchronisation this adds per launch —, the network on the live rows, scatter); the grids count
+    live and total points.  Not with raw_noise_std > 0: noise can lift an empty sample above zero."""
     rays_o, rays_d = ray_batch[:, 0:3].contiguous(), ray_batch[:, 3:6].contiguous()
     viewdirs = ray_batch[:, -3:].contiguous() if ray_batch.shape[-1] > 8 else None
     near, far = ray_batch[:, 6:7].contiguous(), ray_batch[:, 7:8].contiguous()
+    if occupancy is not None:
+        if raw_noise_std > 0.:
+            raise ValueError("render_rays: occupancy with raw_noise_std > 0 — noise can lift a skipped sample above zero")
+        if viewdirs is None:
+            raise NotImplementedError("render_rays: occupancy needs use_viewdirs=True (the compacted rows carry viewdirs)")
+        grid_coarse, grid_fine = occupancy
     z_vals = _coarse_z(near, far, N_samples, lindisp, perturb, pytest, t_rand)
     on_gpu = ray_batch.is_cuda
 
-    def query(z, net):
+    def query(z, net, grid=None):
+        if grid is not None:
+            return grid.query(net, rays_o, rays_d, viewdirs, z, network_query_fn)
         if on_gpu:
             if viewdirs is None:
                 raise NotImplementedError("the teacher HIP path needs use_viewdirs=True")
@@ -341,14 +353,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
         return network_query_fn(pts, viewdirs, net)
 
-    raw = query(z_vals, network_fn)
+    raw = query(z_vals, network_fn, None if occupancy is None else grid_coarse)
     rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd,
                                                                  pytest=pytest)
     if N_importance > 0:
         rgb0, disp0, acc0 = rgb_map, disp_map, acc_map
         z_samples, z_vals, z_std = sample_pdf_sort(z_vals, weights, N_importance, det=(perturb == 0.), pytest=pytest,
                                                    u=u)
-        raw = query(z_vals, network_fn if network_fine is None else network_fine)
+        raw = query(z_vals, network_fn if network_fine is None else network_fine, None if occupancy is None else grid_fine)
         rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd,
                                                                      pytest=pytest, need_weights=False)
     ret = {"rgb_map": rgb_map, "disp_map": disp_map, "acc_map": acc_map, "depth_map": depth_map}

@@ -1,0 +1,115 @@
+"""The teacher's per-pose render in ms per 400x400 frame with and without the occupancy grid (render(..., occupancy=pair)), in
+ONE process: 64 + 128 samples, chunk 32 768, perturb 0, the tests' trained-like pair (tests/teacher_util.py: no lego teacher is at
+hand), boxes +-1.6 (the fitted box) and +-2.5 (the drivers' default for the Blender scenes).  After a warm-up of each path, three
+alternating rounds, device events around work that ends in a synchronise.  Also: the live share, the build time of the pair, the
+kernel times of compact and scatter on one chunk, max |d RGB| and PSNR between the two frames, and the share of rays that carry
+a skipped sample with sigma > 0 on the 2000 rays of tests/test_occupancy_gpu.py (test 5).
+
+    python tools/occupancy_time.py --out profiles/occupancy.txt
+"""
+import argparse
+import math
+import os
+import sys
+
+import torch
+
+ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
+sys.path.insert(0, ROOT)
+from oracle import r2l_oracle as O  # noqa: E402
+from r2l_amd import engine, occupancy as OC, render  # noqa: E402
+from r2l_amd.nerf_raybased import NeRF  # noqa: E402
+from tests.teacher_util import scene_rays, trained_like_pair  # noqa: E402
+
+
+def timed(fn):
+    e0, e1 = torch.cuda.Event(enable_timing=True), torch.cuda.Event(enable_timing=True)
+    e0.record()
+    out = fn()
+    e1.record()
+    torch.cuda.synchronize()
+    return e0.elapsed_time(e1), out
+
+
+def main():
+    ap = argparse.ArgumentParser()
+    ap.add_argument("--size", type=int, default=400)
+    ap.add_argument("--res", type=int, default=128, help="cells per axis")
+    ap.add_argument("--rounds", type=int, default=3)
+    ap.add_argument("--precision", default="auto", choices=["auto", "fp16x2", "bf16x3", "fp32_mfma"])
+    ap.add_argument("--out", default="")
+    a = ap.parse_args()
+    dev = "cuda:0"
+    nets = []
+    for sd in trained_like_pair():
+        m = NeRF(D=8, W=256, input_ch=63, output_ch=4, skips=[4], input_ch_views=27, use_viewdirs=True)
+        m.load_state_dict(sd)
+        for p in m.parameters():
+            p.requires_grad = False
+        m = m.to(dev).eval()
+        render.teacher_engine(m).set_config(precision=a.precision)
+        nets.append(m)
+    H = W = a.size
+    focal = 555.5555155968841 * a.size / 400.
+    c2w = torch.from_numpy(O.pose_spherical(35., -25., 4.)[:3, :4]).to(dev)
+    kw = dict(chunk=32768, c2w=c2w, ndc=False, near=2., far=6., use_viewdirs=True, network_fn=nets[0], network_fine=nets[1],
+              network_query_fn=None, N_samples=64, N_importance=128, perturb=0., white_bkgd=True)
+    frame = lambda occ: render.render(H, W, focal, occupancy=occ, **kw)[0]
+    med = lambda v: sorted(v)[len(v) // 2]
+    lines = ["teacher render(), %d x %d, 64+128 samples, chunk 32768, perturb 0, precision %s (%s), trained-like pair of tests/teacher_util.py, %s"
+             % (H, W, a.precision, engine.arithmetic(render.teacher_engine(nets[0]).cfg)["precision"], torch.cuda.get_device_name(0)),
+             "grid %d^3 cells x 2 probes per cell and axis x dilation 1; ms/frame by device events, rounds alternated full -> skipped" % a.res]
+    with torch.no_grad():
+        for box in (1.6, 2.5):
+            pair = tuple(OC.OccupancyGrid([-box] * 3, [box] * 3, G=a.res).build(n) for n in nets)
+            build_ms = [g.build_seconds * 1e3 for g in pair]
+            for occ in (None, pair):
+                frame(occ)  # warm-up: weight packing, allocator, the grids' buffers
+            for g in pair:
+                g.reset_counters()
+            ms = {"full": [], "skipped": []}
+            for _ in range(a.rounds):
+                t, full = timed(lambda: frame(None))
+                ms["full"].append(t)
+                t, skip = timed(lambda: frame(pair))
+                ms["skipped"].append(t)
+            live = sum(g.live_points for g in pair) / sum(g.total_points for g in pair)
+            diff = (full - skip).abs()
+            mse = float((diff.double()**2).mean())
+            # compact and scatter alone, on the fine pass of one chunk (32 768 rays x 192 samples)
+            rays = scene_rays(H * W, 0, H=H, W=W, focal=focal)[::max(H * W // 32768, 1)][:32768].to(dev)  # spread over the frame
+            o, d, vd = rays[:, 0:3].contiguous(), rays[:, 3:6].contiguous(), rays[:, 8:11].contiguous()
+            n = rays.shape[0]
+            z = torch.linspace(2., 6., 192, device=dev).expand(n, 192).contiguous()
+            pair[1].compact(o, d, vd, z)
+            tc = [timed(lambda: pair[1].compact(o, d, vd, z)) for _ in range(5)]
+            M, idx = tc[-1][1][0], tc[-1][1][1]
+            raw_live = torch.randn(M, 4, device=dev)
+            ts = [timed(lambda: OC.OccupancyGrid.scatter(raw_live, idx, n, 192))[0] for _ in range(5)]
+            lines.append("box +-%.1f: occupied cells %.1f %% (coarse net) / %.1f %% (fine net); build %.0f + %.0f ms (wall, %d probes each)"
+                         % (box, 100 * pair[0].occupied_share(), 100 * pair[1].occupied_share(), build_ms[0], build_ms[1], (2 * a.res)**3))
+            for k, v in ms.items():
+                lines.append("  %-8s %s   median %.2f, spread %.2f" % (k, "  ".join("%.2f" % x for x in v), med(v), max(v) - min(v)))
+            lines.append("  skipped / full %.3f (medians); live points %.1f %% of %d per frame" %
+                         (med(ms["skipped"]) / med(ms["full"]), 100 * live, H * W * 256))
+            lines.append("  max |d RGB| %.3e, PSNR between the frames %s dB" %
+                         (float(diff.max()), "inf" if mse == 0 else "%.2f" % (-10. * math.log10(mse))))
+            lines.append("  one chunk's fine pass (%d x 192 samples, %d live): compact (3 launches + the 8-byte read) %.3f ms, scatter "
+                         "(memset + 1 launch) %.3f ms (medians of 5)" % (n, M, med([t for t, _ in tc]), med(ts)))
+            if box == 1.6 and a.res >= 64:
+                g64 = pair if a.res == 64 else tuple(OC.OccupancyGrid([-box] * 3, [box] * 3, G=64).build(n) for n in nets)
+                spread = scene_rays(181 * 181, 0)[::181 * 181 // 2000][:2000].contiguous().to(dev)  # test 5's rays
+                rep = OC.miss_report(spread, nets[0], nets[1], g64, 64, 128)
+                n_miss = int((rep["misses"] > 0).sum())
+                drgb = (rep["skip"]["rgb"].double() - rep["full"]["rgb"].double()).abs().amax(-1)
+                lines.append("  tests/test_occupancy_gpu.py test 5 (2000 rays, grid 64^3 x 2 x dilation 1): %d rays (%.2f %%) carry a skipped "
+                             "sample with sigma > 0; largest |d RGB| among them %.3e" % (n_miss, n_miss / 20., float(drgb.max())))
+    text = "\n".join(lines)
+    print(text)
+    if a.out:
+        with open(os.path.abspath(a.out), "w") as f:
+            f.write(text + "\n")
+
+
+if __name__ == "__main__":
+    main()
