@@ -172,10 +172,10 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
     s.scale_dev = s.trio16 ? reinterpret_cast<const float*>(s.status + B2S_GSCALE) : nullptr;
 
     // 1. dX chain
+    const R2LLossIO loss{rgb, target, drgb, grad_scale, dpre, sqerr_partial};
     if (!(parts & R2L_BWD_CHAIN)) {
     } else if (plan.chain == R2L_CHAIN_COOP16) {
-        if (const int rc = r2l_coop16_backward(rgb, target, drgb, save_x, save_t, w.w16, params, n_block, grad_scale, dpre, gx, gt,
-                                               sqerr_partial, N, stream)) return rc;
+        if (const int rc = r2l_coop16_backward(loss, save_x, save_t, w.w16, params, n_block, gx, gt, N, stream)) return rc;
     } else if (s.split) {
         // one-wave-per-tile dX chain.  Default trio (MSE mode: scaled chain, values in fp16's range up to the guard): two-way fp16
         // splits, 3 fp16 products per fp32 product (r2l_bwd2.hip), stashing fp16 stage pieces for r2l_dw16.hip, with the
@@ -193,11 +193,10 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
             }
             // small launches: the cooperative chain (r2l_coopf_bwd.hip), same stream / stash / status word; only it is cut into segments
             const int rc2 = plan.tiling == R2L_TILING_COOPF
-                                ? r2l_coopf_backward(rgb, target, drgb, save_x, save_t, w.w2, params, n_block, grad_scale, dpre, gx, gt,
-                                                     sqerr_partial, N, stream, s.gscale, s.status, s.scale_dev, plan,
-                                                     s.chain_seg ? layer_hi / 2 - 1 : -1, s.chain_seg ? layer_lo / 2 : 0)
-                                : r2l_bwd2_backward(rgb, target, drgb, save_x, save_t, w.w2, params, n_block, grad_scale, dpre, gx, gt,
-                                                    sqerr_partial, N, stream, s.gscale, s.status, s.scale_dev, plan.stash_mid);
+                                ? r2l_coopf_backward(loss, save_x, save_t, w.w2, params, n_block, gx, gt, N, stream, s.gscale, s.status,
+                                                     s.scale_dev, plan, s.chain_seg ? layer_hi / 2 - 1 : -1, s.chain_seg ? layer_lo / 2 : 0)
+                                : r2l_bwd2_backward(loss, save_x, save_t, w.w2, params, n_block, gx, gt, N, stream, s.gscale, s.status,
+                                                    s.scale_dev, plan.stash_mid);
             if (rc2) return rc2;
             if (!s.no_fallback) {
                 // the fallback's stream is packed in front of it, and only when it will run
@@ -206,12 +205,11 @@ extern "C" int r2l_backward_part_cfg(const float* rays_o, const float* rays_d, c
             }
         }
         if (!(s.trio16 && s.no_fallback)) {
-            if (const int rc = r2l_bwd3_backward(rgb, target, drgb, save_x, save_t, w.w3, params, n_block, grad_scale, dpre, gx, gt,
-                                                 sqerr_partial, N, stream, s.gscale, s.trio16 ? s.status : nullptr, s.scale_dev)) return rc;
+            if (const int rc = r2l_bwd3_backward(loss, save_x, save_t, w.w3, params, n_block, gx, gt, N, stream, s.gscale,
+                                                 s.trio16 ? s.status : nullptr, s.scale_dev)) return rc;
         }
     } else {
-        if (const int rc = r2l_bwd32_backward(rgb, target, drgb, save_x, save_t, w.w32, params, n_block, grad_scale, dpre, gx, gt,
-                                              sqerr_partial, N, stream)) return rc;
+        if (const int rc = r2l_bwd32_backward(loss, save_x, save_t, w.w32, params, n_block, gx, gt, N, stream)) return rc;
     }
 
     // a call that does body and head of a small step: head + tail on the side stream (R2LSideStream)

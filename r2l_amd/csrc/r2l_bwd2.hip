@@ -10,11 +10,6 @@
 
 #define B3_RING 2  // mask pieces (one per block) per wave
 
-__host__ __device__ static inline int64_t b2_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t b2_off_tail_w(int n_block) { return b2_off_body_w(2 * n_block); }
-
 // =================================================================================================================
 // pack: stage order and element numbering of r2l_pack_bwd2_kernel, two fp16 splits per value, 16 KiB stages
 // =================================================================================================================
@@ -33,7 +28,7 @@ __global__ void r2l_pack_bwd2_kernel(const float* __restrict__ params, unsigned 
                 const int layer = r < 17 ? 2 * b + 1 : 2 * b, kb = r < 17 ? r - 1 : r - 18;
                 const int T = kb >> 1, rr = kb & 1;
                 const int in = 32 * T + 8 * (2 * rr + (s >> 2)) + 4 * h + (s & 3);
-                const float w = params[b2_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
+                const float w = params[r2l_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
                 const _Float16 hi = (_Float16)w;
                 const _Float16 mid = (_Float16)(w - (float)hi);
                 v0 = __builtin_bit_cast(unsigned short, hi);
@@ -119,70 +114,19 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd2_kernel(const B2Args a) {
     const int64_t rc = valid ? ray : a.N - 1;
     const int64_t Np = R2L_PAD_ROWS(a.N);
 
-    // ---- loss gradient through the sigmoid, per-tile squared error (as r2l_bwd_chain_kernel) ---------------------------
-    float dp[3], se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float r = a.rgb[rc * 3 + c];
-        float dl;
-        if (a.target != nullptr) {
-            const float e = r - a.target[rc * 3 + c];
-            se += e * e;
-            dl = a.grad_scale * e;
-        } else {
-            dl = a.drgb[rc * 3 + c];
-        }
-        dp[c] = valid ? dl * (r * (1.0f - r)) : 0.f;
-    }
-    if (!valid) se = 0.f;
-    if (valid && h == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.dpre[ray * 3 + c] = dp[c];
-    }
-    if (a.sqerr_partial != nullptr) {
-        float s = (h == 0) ? se : 0.f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) a.sqerr_partial[tile] = s;
-    }
-    // g = dy = Wt^T dpre   (tail Linear(256,3))
+    // ---- loss gradient through the sigmoid, per-tile squared error; g = dy = Wt^T (gscale dpre) (tail Linear(256,3)) ----
+    float dp[3];
+    const float se = r2l_loss_seed(a.rgb, a.target, a.drgb, a.grad_scale, rc, valid, dp);
+    if (valid && h == 0) r2l_dpre_store(a.dpre, ray, dp);
+    r2l_tile_sqerr(a.sqerr_partial, tile, se, h, lane);
     f32x16 g[R2L_NT], u[R2L_NT], dy[R2L_NT];
-    {
-        const float* tw = a.params + b2_off_tail_w(a.n_block);
+    r2l_tail_transposed<true>(g, a.params + r2l_off_tail_w(a.n_block) + 4 * h, dp, gscale);
 #pragma unroll
-        for (int T = 0; T < R2L_NT; ++T)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 wv[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(tw + c * R2L_W + 32 * T + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = wv[0][j] * (dp[0] * gscale);
-                    v = __builtin_fmaf(wv[1][j], dp[1] * gscale, v);
-                    v = __builtin_fmaf(wv[2][j], dp[2] * gscale, v);
-                    g[T][4 * q + j] = v;
-                    dy[T][4 * q + j] = v;
-                }
-            }
-    }
+    for (int T = 0; T < R2L_NT; ++T) dy[T] = g[T];
 
     // ---- weight staging (6 buffers of 16 KiB beside the 32 KiB mask ring) ------------------------------------------------------
     F2Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 4096u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-        P.amax = 0.f;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
 #pragma unroll
     for (int k = 0; k < F2_NBUF - 1; ++k) P.issue();  // stages 0 .. F2_NBUF-2
 #pragma unroll
@@ -212,10 +156,7 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd2_kernel(const B2Args a) {
 #pragma unroll 1
     for (int b = a.n_block - 1; b >= 0; --b) {
         // descriptor of save_t[b] (per block: 32-bit offsets inside the slot)
-        const unsigned long long ta = (unsigned long long)(a.save_t + (int64_t)b * slot);
-        const u32x4 trs = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ta),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ta >> 32)) & 0xffffu, 0xffffffffu,
-                           0x00020000u};
+        const u32x4 trs = r2l_buffer_rsrc(a.save_t + (int64_t)b * slot);
         float* const gxr = a.gx + (int64_t)(b + 1) * slot;
         float* const gtr = a.gt + (int64_t)b * slot;
         const unsigned hvoff = (unsigned)(lane_unit * 16);
@@ -386,18 +327,18 @@ int r2l_bwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t
     return 0;
 }
 
-int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                      const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                      float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                      const float* scale_dev, bool stash_mid) {
+int r2l_bwd2_backward(const R2LLossIO& loss, const float* save_x, const float* save_t, const float* wstream_bwd2,
+                      const float* params, int n_block, float* gx, float* gt, int64_t N, hipStream_t stream, float gscale,
+                      unsigned* status, const float* scale_dev, bool stash_mid) {
     B2Args a{};
+    r2l_set_loss(a, loss);
     a.status = status;
     a.scale_dev = scale_dev;
     a.fmt = reinterpret_cast<const unsigned*>(save_x) + R2L_STASH_FMT_WORD(n_block, R2L_PAD_ROWS(N));
     a.gscale = gscale; a.ginv = 1.0f / gscale;
-    a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t;
+    a.save_x = save_x; a.save_t = save_t;
     a.stream = reinterpret_cast<const unsigned char*>(wstream_bwd2); a.params = params; a.n_block = n_block;
-    a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt; a.sqerr_partial = sqerr_partial; a.N = N;
+    a.gx = gx; a.gt = gt; a.N = N;
     a.stash_mid = stash_mid ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     if (a.stash_mid != 0u) hipLaunchKernelGGL(r2l_bwd2_kernel<true>, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
@@ -411,7 +352,7 @@ int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, 
 // replay — ROCm 7.0 —, which sent every replayed step to the fallback kernels)
 int r2l_bwd2_open_step(unsigned* status, const float* params, int n_block, float grad_scale, const float* drgb, int64_t N,
                        hipStream_t stream) {
-    hipLaunchKernelGGL(r2l_bwd_prepare_kernel, dim3(1), dim3(64), 0, stream, status, params + b2_off_tail_w(n_block), grad_scale,
+    hipLaunchKernelGGL(r2l_bwd_prepare_kernel, dim3(1), dim3(64), 0, stream, status, params + r2l_off_tail_w(n_block), grad_scale,
                        drgb == nullptr ? 1 : 0);
     R2L_CHECK(hipGetLastError());
     if (drgb != nullptr) {

@@ -15,11 +15,6 @@
 #define B3_NBUF 6
 #define B3_RING 2  // mask pieces (one per block) per wave
 
-__host__ __device__ static inline int64_t b3_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t b3_off_tail_w(int n_block) { return b3_off_body_w(2 * n_block); }
-
 // =================================================================================================================
 // pack: stage g = 34 * slot + r, slot = n_block-1-b;  r = 0 / 17: zero stages;  r = 1..16: k-block r-1 of W2^T (layer 2b+1);
 // r = 18..33: k-block r-18 of W1^T (layer 2b).  Element (split, tile t, lane (i,h), slot s): (W^T)[32t+i][feature(kb,h,s)]
@@ -88,7 +83,7 @@ __global__ void r2l_pack_bwd3_kernel(const float* __restrict__ params, unsigned 
                 const int layer = r < 17 ? 2 * b + 1 : 2 * b, kb = r < 17 ? r - 1 : r - 18;
                 const int T = kb >> 1, rr = kb & 1;
                 const int in = 32 * T + 8 * (2 * rr + (s >> 2)) + 4 * h + (s & 3);
-                const float w = params[b3_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
+                const float w = params[r2l_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
                 v0 = f3_bf16_rne(w);
                 const float r1 = w - f3_bf16_to_f(v0);
                 v1 = f3_bf16_rne(r1);
@@ -170,70 +165,20 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd3_kernel(const B3Args a) {
     const int64_t rc = valid ? ray : a.N - 1;
     const int64_t Np = R2L_PAD_ROWS(a.N);
 
-    // ---- loss gradient through the sigmoid, per-tile squared error (as r2l_bwd_chain_kernel) ---------------------------
-    float dp[3], se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float r = a.rgb[rc * 3 + c];
-        float dl;
-        if (a.target != nullptr) {
-            const float e = r - a.target[rc * 3 + c];
-            se += e * e;
-            dl = a.grad_scale * e;
-        } else {
-            dl = a.drgb[rc * 3 + c];
-        }
-        dp[c] = valid ? dl * (r * (1.0f - r)) : 0.f;
-    }
-    if (!valid) se = 0.f;
-    if (valid && h == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.dpre[ray * 3 + c] = dp[c];
-    }
-    if (a.sqerr_partial != nullptr) {
-        float s = (h == 0) ? se : 0.f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) a.sqerr_partial[tile] = s;
-    }
-    // g = dy = Wt^T dpre   (tail Linear(256,3))
+    // ---- loss gradient through the sigmoid, per-tile squared error; g = dy = Wt^T (gscale dpre) (tail Linear(256,3)) ----
+    float dp[3];
+    const float se = r2l_loss_seed(a.rgb, a.target, a.drgb, a.grad_scale, rc, valid, dp);
+    if (valid && h == 0) r2l_dpre_store(a.dpre, ray, dp);
+    r2l_tile_sqerr(a.sqerr_partial, tile, se, h, lane);
     f32x16 g[R2L_NT], u[R2L_NT], dy[R2L_NT];
-    {
-        const float* tw = a.params + b3_off_tail_w(a.n_block);
+    r2l_tail_transposed<true>(g, a.params + r2l_off_tail_w(a.n_block) + 4 * h, dp, gscale);
 #pragma unroll
-        for (int T = 0; T < R2L_NT; ++T)
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                f32x4 wv[3];
-#pragma unroll
-                for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(tw + c * R2L_W + 32 * T + 8 * q + 4 * h);
-#pragma unroll
-                for (int j = 0; j < 4; ++j) {
-                    float v = wv[0][j] * (dp[0] * gscale);
-                    v = __builtin_fmaf(wv[1][j], dp[1] * gscale, v);
-                    v = __builtin_fmaf(wv[2][j], dp[2] * gscale, v);
-                    g[T][4 * q + j] = v;
-                    dy[T][4 * q + j] = v;
-                }
-            }
-    }
+    for (int T = 0; T < R2L_NT; ++T) dy[T] = g[T];
 
     // ---- weight staging (6 buffers beside the 8 KiB mask ring) ----------------------------------------------------------------
     typedef F3PipeT<B3_NBUF> Pipe;
     Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 6144u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
     P.issue(); P.issue(); P.issue(); P.issue(); P.issue();  // stages 0..4
 #pragma unroll
     for (int k = 0; k < 8; ++k) P.ones.h[k] = (__bf16)((h == 0 && k < 3) ? 1.0f : 0.0f);
@@ -262,10 +207,7 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd3_kernel(const B3Args a) {
 #pragma unroll 1
     for (int b = a.n_block - 1; b >= 0; --b) {
         // descriptor of save_t[b] (per block: 32-bit offsets inside the slot)
-        const unsigned long long ta = (unsigned long long)(a.save_t + (int64_t)b * slot);
-        const u32x4 trs = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ta),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ta >> 32)) & 0xffffu, 0xffffffffu,
-                           0x00020000u};
+        const u32x4 trs = r2l_buffer_rsrc(a.save_t + (int64_t)b * slot);
         float* gxs = a.gx + (int64_t)(b + 1) * slot + lane_off;
         float* gts = a.gt + (int64_t)b * slot + lane_off;
         const F3Dma no_dma{false, u32x4{0u, 0u, 0u, 0u}, 0u, 0u, 0u};
@@ -318,17 +260,17 @@ int r2l_bwd3_pack(const float* params, int n_block, float* wstream3, hipStream_t
     return 0;
 }
 
-int r2l_bwd3_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                      const float* wstream_bwd3, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                      float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, const unsigned* run_if,
-                      const float* scale_dev) {
+int r2l_bwd3_backward(const R2LLossIO& loss, const float* save_x, const float* save_t, const float* wstream_bwd3,
+                      const float* params, int n_block, float* gx, float* gt, int64_t N, hipStream_t stream, float gscale,
+                      const unsigned* run_if, const float* scale_dev) {
     B3Args a{};
+    r2l_set_loss(a, loss);
     a.run_if = run_if;
     a.gscale = gscale; a.ginv = 1.0f / gscale;
     a.scale_dev = scale_dev;
-    a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t;
+    a.save_x = save_x; a.save_t = save_t;
     a.stream = reinterpret_cast<const unsigned char*>(wstream_bwd3); a.params = params; a.n_block = n_block;
-    a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt; a.sqerr_partial = sqerr_partial; a.N = N;
+    a.gx = gx; a.gt = gt; a.N = N;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     hipLaunchKernelGGL(r2l_bwd3_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());

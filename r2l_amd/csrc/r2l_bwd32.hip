@@ -52,52 +52,15 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_chain_kernel(const R2LBwdArgs 
     ws.init(a.wstream, lane);
     const int64_t Np = R2L_PAD_ROWS(a.N);  // rows per stash / gradient slot
 
-    // loss gradient through the sigmoid: dpre = grad_scale*(rgb-target) * rgb*(1-rgb)
-    float dp[3], se = 0.f;
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float r = a.rgb[rc * 3 + c];
-        float dl;
-        if (a.target != nullptr) {
-            const float e = r - a.target[rc * 3 + c];
-            se += e * e;
-            dl = a.grad_scale * e;
-        } else {
-            dl = a.drgb[rc * 3 + c];
-        }
-        dp[c] = valid ? dl * (r * (1.0f - r)) : 0.f;
-    }
-    if (!valid) se = 0.f;
-    if (valid && h == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.dpre[ray * 3 + c] = dp[c];
-    }
-    // per-tile squared error (lanes 0..31 hold the 32 rays)
-    if (a.sqerr_partial != nullptr) {
-        float s = (h == 0) ? se : 0.f;
-#pragma unroll
-        for (int off = 32; off >= 1; off >>= 1) s += __shfl_xor(s, off);
-        if (lane == 0) a.sqerr_partial[tile] = s;
-    }
+    // loss gradient through the sigmoid: dpre = grad_scale*(rgb-target) * rgb*(1-rgb); per-tile squared error
+    float dp[3];
+    const float se = r2l_loss_seed(a.rgb, a.target, a.drgb, a.grad_scale, rc, valid, dp);
+    if (valid && h == 0) r2l_dpre_store(a.dpre, ray, dp);
+    r2l_tile_sqerr(a.sqerr_partial, tile, se, h, lane);
 
     // g = dy = Wt^T dpre   (tail Linear(256,3))
     f32x16 g[R2L_NT], u[R2L_NT];
-    const float* tw = a.params + b_off_tail_w(a.n_block);
-#pragma unroll
-    for (int T = 0; T < R2L_NT; ++T)
-#pragma unroll
-        for (int q = 0; q < 4; ++q) {
-            f32x4 wv[3];
-#pragma unroll
-            for (int c = 0; c < 3; ++c) wv[c] = *reinterpret_cast<const f32x4*>(tw + c * R2L_W + 32 * T + 8 * q + 4 * h);
-#pragma unroll
-            for (int j = 0; j < 4; ++j) {
-                float v = wv[0][j] * dp[0];
-                v = __builtin_fmaf(wv[1][j], dp[1], v);
-                v = __builtin_fmaf(wv[2][j], dp[2], v);
-                g[T][4 * q + j] = v;
-            }
-        }
+    r2l_tail_transposed<false>(g, a.params + r2l_off_tail_w(a.n_block) + 4 * h, dp, 1.0f);
 #pragma unroll
     for (int T = 0; T < R2L_NT; ++T)
 #pragma unroll
@@ -139,13 +102,12 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_chain_kernel(const R2LBwdArgs 
     store_frag(a.gx, ray, h, g);
 }
 
-int r2l_bwd32_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                       const float* wstream_bwd32, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream) {
+int r2l_bwd32_backward(const R2LLossIO& loss, const float* save_x, const float* save_t, const float* wstream_bwd32,
+                       const float* params, int n_block, float* gx, float* gt, int64_t N, hipStream_t stream) {
     R2LBwdArgs a{};
-    a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t; a.wstream = wstream_bwd32;
-    a.params = params; a.n_block = n_block; a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt;
-    a.sqerr_partial = sqerr_partial; a.N = N;
+    r2l_set_loss(a, loss);
+    a.save_x = save_x; a.save_t = save_t; a.wstream = wstream_bwd32;
+    a.params = params; a.n_block = n_block; a.gx = gx; a.gt = gt; a.N = N;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     hipLaunchKernelGGL(r2l_bwd_chain_kernel, dim3((unsigned)((tiles + 3) / 4)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());

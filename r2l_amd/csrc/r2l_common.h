@@ -58,6 +58,14 @@ typedef float f32x4 __attribute__((ext_vector_type(4)));
 // VGPR-address form (`global_load_dwordx4 v, v[addr:addr+1], off`) costs ~16 cycles of MFMA issue per load, this
 // form none — the largest single lever of round 1.
 typedef unsigned u32x4 __attribute__((ext_vector_type(4)));
+// The descriptor as four words for the kernels that hand it to inline assembly (LDS-DMA loads, r2l_f2.h / r2l_f3.h): base through
+// readfirstlane (wave-uniform by construction), 48 address bits, stride 0; num_records = 4 GiB - 1 (no clamping); 0x00020000: raw
+// buffer, 32-bit offsets
+__device__ __forceinline__ u32x4 r2l_buffer_rsrc(const void* base) {
+    const unsigned long long a = (unsigned long long)base;
+    return u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)a),
+                 (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(a >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
+}
 struct WPtr {
     __amdgpu_buffer_rsrc_t rsrc;  // buffer descriptor of the whole stream (4 SGPRs, wave-uniform by construction)
     unsigned voff;                // lane * 16
@@ -422,13 +430,6 @@ __host__ __device__ static inline int64_t r2l_fwd16_stream_floats(int n_block) {
 __host__ __device__ static inline int64_t r2l_bwd16_stream_floats(int n_block) {
     return (int64_t)(2 * n_block * R2L_C16_LAYER_GROUPS + R2L_C16_PAD_GROUPS) * R2L_C16_GROUP_FLOATS;
 }
-int r2l_coop16_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                       const float* c2w_host12, int H, int W, float focal, const float* wstream16, const float* params,
-                       int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream);
-int r2l_coop16_backward(const float* rgb, const float* target, const float* drgb, const float* save_x,
-                        const float* save_t, const float* wstream_bwd16, const float* params, int n_block,
-                        float grad_scale, float* dpre, float* gx, float* gt, float* sqerr_partial, int64_t N,
-                        hipStream_t stream);
 
 // ---- fp32-accurate forward on the bf16 matrix pipe (r2l_fwd3.hip): stage stream of bf16 (hi, mid, lo) weight triples ------
 #define R2L_F3_PAD_STAGES 8   // the staging pipelines request up to 7 stages past the one being consumed
@@ -476,33 +477,8 @@ enum { B2S_FLAG = 0, B2S_GSCALE = 4, B2S_GINV = 5, B2S_AMAX = 8, B2S_MAGIC = 9, 
 // save_x / save_t / N (fallback of a training step only): an fp16 forward stash is expanded to the chunked fp32 layout first
 int r2l_bwd3_pack(const float* params, int n_block, float* wstream3, hipStream_t stream, const unsigned* run_if = nullptr,
                   const float* save_x = nullptr, const float* save_t = nullptr, int64_t N = 0);
-int r2l_bwd3_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                      const float* wstream_bwd3, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                      float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale = 1.0f,
-                      const unsigned* run_if = nullptr, const float* scale_dev = nullptr);
-// the same chain on two-way fp16 splits (r2l_bwd2.hip); status: range-guard word (behind the bwd2 stream region)
-int r2l_bwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t stream);
-int r2l_bwd2_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                      const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                      float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                      const float* scale_dev, bool stash_mid);  // stash_mid: the step stashes the mid halves too (exact dW)
-// pose mode: the camera of ray rc and its pixel index.  One pose by value (c2w), or — one launch over several frames
-// (r2l_forward_poses: no tail round and no launch gap per frame) — a device table c2w_dev[K][12], frame = rc / (H * W)
-struct R2LPoseRay { float c[12]; int64_t pix; };
-__device__ __forceinline__ R2LPoseRay r2l_pose_of(const float (&c2w)[12], const float* c2w_dev, int64_t hw, int64_t rc) {
-    R2LPoseRay r;
-    r.pix = rc;
-    if (c2w_dev != nullptr) {
-        const int64_t p = rc / hw;
-        r.pix = rc - p * hw;
-#pragma unroll
-        for (int i = 0; i < 12; ++i) r.c[i] = c2w_dev[p * 12 + i];
-    } else {
-#pragma unroll
-        for (int i = 0; i < 12; ++i) r.c[i] = c2w[i];
-    }
-    return r;
-}
+int r2l_bwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t stream);  // (r2l_bwd2.hip: two-way fp16 splits)
+// (the launchers of the chains themselves: r2l_student_net.h)
 // argument checks of the C ABI: a bad pointer / size is an error code here, not a memory fault on the device
 #define R2L_REQUIRE(cond, msg)                            \
     do {                                                  \
@@ -513,22 +489,12 @@ __device__ __forceinline__ R2LPoseRay r2l_pose_of(const float (&c2w)[12], const 
     } while (0)
 #define R2L_MAX_BLOCKS 1024  // body blocks of a student net: the kernels address a weight stream (~0.57 MB per block) with 32-bit offsets
 int r2l_fwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t stream);
-int r2l_fwd2_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                     const float* c2w_host12, int H, int W, float focal, const float* wstream2, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const float* c2w_dev, bool stash_mid);  // c2w_dev: pose table of a multi-frame launch (r2l_pose_of), or nullptr
 int r2l_fwd3_pack(const float* params, int n_block, float* wstream3, hipStream_t stream, const unsigned* run_if = nullptr);
 // Behind every fp16x2 forward launch: returns at once (GO = 0) unless that launch raised FLAG; else packs the bf16x3 stream,
 // re-packs the scale-dependent stages of the fp16x2 stream for the next activation scale and commits it (GO = 1, FLAG = 0
 // unless the scale is exhausted): the r2l_fwd3_forward behind it (run_if = status + F2S_GO) redoes this launch, the next
 // launch is back on the fp16 kernels (r2l_f2.h: range control)
 int r2l_fwd2_fallback_pack(const float* params, int n_block, float* wstream3, float* wstream2, hipStream_t stream);
-// run_if: nullptr, or a device word — the launch returns at once while it is 0 (fallback behind r2l_fwd2_forward)
-int r2l_fwd3_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                     const float* c2w_host12, int H, int W, float focal, const float* wstream3, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const unsigned* run_if = nullptr, const float* x0_in = nullptr,  // x0_in: body + tail from a given X_0
-                     const float* c2w_dev = nullptr);
 
 // launches of at most this many rays take the cooperative fp16x2 kernels (compile-time knob; the rule: r2l_dispatch.hip)
 #ifndef R2L_COOPF_MAX_RAYS

@@ -12,7 +12,7 @@
 //     a lane computes exactly the 252 encoding values it feeds, 2 sincos per 16 MFMAs;
 //   * the bias of the next layer is prefetched while the current layer computes.
 // Semantics, stash layout and gradients are identical to the other variants (tests run all three).
-#include "r2l_common.h"
+#include "r2l_student_net.h"
 
 #define C16_RAYS 16
 #define C16_LD 260                          // LDS row pitch in floats: 16-byte skew per ray -> conflict-free b128 access
@@ -21,13 +21,6 @@
 
 typedef float f32x4v __attribute__((ext_vector_type(4)));
 
-__host__ __device__ static inline int64_t h_off_head_b() { return (int64_t)R2L_IN * R2L_W; }
-__host__ __device__ static inline int64_t h_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t h_off_body_b(int layer) { return h_off_body_w(layer) + R2L_W * R2L_W; }
-__host__ __device__ static inline int64_t h_off_tail_w(int n_block) { return h_off_body_w(2 * n_block); }
-__host__ __device__ static inline int64_t h_off_tail_b(int n_block) { return h_off_tail_w(n_block) + 3 * R2L_W; }
 #define C16_BIAS_STRIDE (R2L_W * R2L_W + R2L_W)
 
 // ---- weight ring of one wave: D groups x its 4 tiles ---------------------------------------------------------------------
@@ -201,7 +194,10 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
     const int64_t rc = valid ? ray : a.N - 1;
     const int64_t Np = R2L_PAD_ROWS(a.N);
 
-    float o[3], d[3];
+    float o[3], d[3], z[16];
+    // r2l_ray_of_row / r2l_ray_of_pixel<false> and r2l_depths of r2l_student_net.h, on this kernel's own lines: with o, d or z
+    // filled through a helper hipcc packs the point products o + d * z into v_pk_mul_f32 with the op_sel form the ISA audit of
+    // r2l_amd/build.py refuses (all three instances), and re-allocates 90 to 1700 instruction lines
     if constexpr (!POSE) {
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
@@ -218,7 +214,6 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
             o[k] = a.c2w[4 * k + 3];
         }
     }
-    float z[16];
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
         const f32x4 lo = *reinterpret_cast<const f32x4*>(a.ztab + 4 * q);
@@ -235,7 +230,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
     // ---- head ---------------------------------------------------------------------------------------------------------
     f32x4 acc[4], xo[4], x0[4], bn[4];
     {
-        const float* hb = a.params + h_off_head_b() + 64 * wave + 4 * kk;
+        const float* hb = a.params + r2l_off_head_b() + 64 * wave + 4 * kk;
 #pragma unroll
         for (int t = 0; t < 4; ++t) acc[t] = *reinterpret_cast<const f32x4*>(hb + 16 * t);
     }
@@ -324,7 +319,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
 
     // ---- body -----------------------------------------------------------------------------------------------------------
     f32x4 bop[16];
-    const float* bias = a.params + h_off_body_b(0) + 64 * wave + 4 * kk;  // own slice of the bias of layer (b, 0)
+    const float* bias = a.params + r2l_off_body_b(0) + 64 * wave + 4 * kk;  // own slice of the bias of layer (b, 0)
 #pragma unroll
     for (int t = 0; t < 4; ++t) bn[t] = *reinterpret_cast<const f32x4*>(bias + 16 * t);
 #pragma unroll 1
@@ -358,7 +353,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
     }
 
     // ---- tail: rgb = sigmoid(Wt (x + X_0) + bt): partial dots per lane, reduced over kk (shuffles) and waves (LDS) -------
-    const float* tw = a.params + h_off_tail_w(a.n_block) + 64 * wave + 4 * kk;
+    const float* tw = a.params + r2l_off_tail_w(a.n_block) + 64 * wave + 4 * kk;
     float p3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int t = 0; t < 4; ++t) {
@@ -387,7 +382,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_c16_kernel(const C16FwdArgs a)
 #pragma unroll
         for (int c = 0; c < 3; ++c) {
             const float v = ((tailred[0][j][c] + tailred[1][j][c]) + (tailred[2][j][c] + tailred[3][j][c])) +
-                            a.params[h_off_tail_b(a.n_block) + c];
+                            a.params[r2l_off_tail_b(a.n_block) + c];
             a.rgb[ray * 3 + c] = 1.0f / (1.0f + expf(-v));
         }
     }
@@ -447,16 +442,8 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_c16_kernel(const C16BwdArgs a)
     r8.init(a.wstream, 0, lane, wave);
 
     float dp[3];
-#pragma unroll
-    for (int c = 0; c < 3; ++c) {
-        const float r = a.rgb[rc * 3 + c];
-        const float dl = a.target != nullptr ? a.grad_scale * (r - a.target[rc * 3 + c]) : a.drgb[rc * 3 + c];
-        dp[c] = valid ? dl * (r * (1.0f - r)) : 0.f;
-    }
-    if (wave == 0 && kk == 0 && valid) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) a.dpre[ray * 3 + c] = dp[c];
-    }
+    r2l_loss_seed(a.rgb, a.target, a.drgb, a.grad_scale, rc, valid, dp);
+    if (wave == 0 && kk == 0 && valid) r2l_dpre_store(a.dpre, ray, dp);
     // squared-error partial of the 32-ray tile this 16-ray tile is the first half of (same slots as the other variants)
     if (a.sqerr_partial != nullptr && (tile & 1) == 0 && wave == 1) {
         const int64_t r32 = tile * C16_RAYS + (lane & 31);
@@ -475,7 +462,7 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_c16_kernel(const C16BwdArgs a)
     // own slice of g = dy = Wt^T dpre, kept also as dy for the outer-residual branch at the head
     f32x4 g[4], dy[4], u[4];
     {
-        const float* tw = a.params + h_off_tail_w(a.n_block) + 64 * wave + 4 * kk;
+        const float* tw = a.params + r2l_off_tail_w(a.n_block) + 64 * wave + 4 * kk;
 #pragma unroll
         for (int t = 0; t < 4; ++t) {
             f32x4 wv[3];
@@ -531,30 +518,28 @@ __global__ __launch_bounds__(256, 1) void r2l_bwd_c16_kernel(const C16BwdArgs a)
 // ------------------------------------------------------------------------------------------------------------------
 // launchers used by the C ABI entry points in r2l_forward.hip / r2l_backward.hip (host only; the fp32 chain: r2l_bwd32.hip)
 // ------------------------------------------------------------------------------------------------------------------
-int r2l_coop16_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                       const float* c2w_host12, int H, int W, float focal, const float* wstream16, const float* params,
-                       int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream) {
+int r2l_coop16_forward(const R2LRayIn& rays, const float* wstream16, const float* params, int n_block, float* rgb,
+                       float* save_x, float* save_t, int64_t N, hipStream_t stream) {
+    const bool pose = r2l_pose_mode(rays);
     C16FwdArgs a{};
-    a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab; a.wstream = wstream16; a.params = params;
-    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
-    if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
+    r2l_set_rays(a, rays);
+    a.wstream = wstream16; a.params = params;
+    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
     // every padded row is computed: the dW kernels read whole 32-row tiles of the stash
     const dim3 grid((unsigned)(R2L_PAD_ROWS(N) / C16_RAYS)), block(256);
-    if (c2w_host12) hipLaunchKernelGGL((r2l_fwd_c16_kernel<true, false>), grid, block, 0, stream, a);
+    if (pose) hipLaunchKernelGGL((r2l_fwd_c16_kernel<true, false>), grid, block, 0, stream, a);
     else if (save_x) hipLaunchKernelGGL((r2l_fwd_c16_kernel<false, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((r2l_fwd_c16_kernel<false, false>), grid, block, 0, stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }
 
-int r2l_coop16_backward(const float* rgb, const float* target, const float* drgb, const float* save_x,
-                        const float* save_t, const float* wstream_bwd16, const float* params, int n_block,
-                        float grad_scale, float* dpre, float* gx, float* gt, float* sqerr_partial, int64_t N,
-                        hipStream_t stream) {
+int r2l_coop16_backward(const R2LLossIO& loss, const float* save_x, const float* save_t, const float* wstream_bwd16,
+                        const float* params, int n_block, float* gx, float* gt, int64_t N, hipStream_t stream) {
     C16BwdArgs a{};
-    a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t; a.wstream = wstream_bwd16;
-    a.params = params; a.n_block = n_block; a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt;
-    a.sqerr_partial = sqerr_partial; a.N = N;
+    r2l_set_loss(a, loss);
+    a.save_x = save_x; a.save_t = save_t; a.wstream = wstream_bwd16;
+    a.params = params; a.n_block = n_block; a.gx = gx; a.gt = gt; a.N = N;
     const dim3 grid((unsigned)(R2L_PAD_ROWS(N) / C16_RAYS)), block(256);
     hipLaunchKernelGGL(r2l_bwd_c16_kernel, grid, block, 0, stream, a);
     R2L_CHECK(hipGetLastError());

@@ -7,10 +7,6 @@
 #include "r2l_coopf.h"
 #include <type_traits>
 
-__host__ __device__ static inline int64_t cb_off_tail_w(int n_block) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)2 * n_block * (R2L_W * R2L_W + R2L_W);
-}
-
 struct CfBwdArgs {
     const float* rgb;
     const float* target;
@@ -70,10 +66,13 @@ __device__ __forceinline__ void cf_bwd_body(const CfBwdArgs& a, const int64_t ti
     }
     const int64_t Np = R2L_PAD_ROWS(a.N);
     const int64_t slot = R2L_TRIO_SLOT(Np);
-    const float* tw = a.params + cb_off_tail_w(a.n_block);
+    const float* tw = a.params + r2l_off_tail_w(a.n_block);
     const bool first = a.b_start == a.n_block - 1, final = a.b_end == 0;
 
     // ---- loss gradient through the sigmoid, per-tile squared error (every wave computes it; wave 0 writes) -------------------
+    // r2l_loss_seed, r2l_dpre_store, r2l_tile_sqerr and r2l_tail_transposed4<true> (r2l_student_net.h), on this kernel's own lines:
+    // through the helpers the instances differ from before in 7 to 840 instruction lines, and the 4096-ray training step measured
+    // 0.25 % slower, beyond the parent's run-to-run spread of 0.10 % (profiles/student_net_ab.txt)
     float dp[NT][3];
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) {
@@ -154,7 +153,7 @@ __device__ __forceinline__ void cf_bwd_body(const CfBwdArgs& a, const int64_t ti
     FcRing<R> W;
     FcStream P;
     {
-        const unsigned long long sa = (unsigned long long)a.stream;
+        const unsigned long long sa = (unsigned long long)a.stream;  // (r2l_buffer_rsrc, r2l_common.h: its one extra s_mov re-orders this prologue)
         P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
                      (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
         P.voff = (unsigned)lane * 16u + (unsigned)wave * 2048u;
@@ -294,20 +293,20 @@ __global__ __launch_bounds__(256, 1) void r2l_coopf_bwd_mixed_kernel(const CfBwd
     else cf_bwd_body<1, MID>(a, (int64_t)a.n_two + b, bop_lds);
 }
 
-int r2l_coopf_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                       const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                       const float* scale_dev, const R2LPlan& plan, int b_start, int b_end) {
+int r2l_coopf_backward(const R2LLossIO& loss, const float* save_x, const float* save_t, const float* wstream_bwd2,
+                       const float* params, int n_block, float* gx, float* gt, int64_t N, hipStream_t stream, float gscale,
+                       unsigned* status, const float* scale_dev, const R2LPlan& plan, int b_start, int b_end) {
     CfBwdArgs a{};
+    r2l_set_loss(a, loss);
     a.b_start = b_start < 0 ? n_block - 1 : b_start;
     a.b_end = b_end;
     a.status = status;
     a.scale_dev = scale_dev;
     a.fmt = reinterpret_cast<const unsigned*>(save_x) + R2L_STASH_FMT_WORD(n_block, R2L_PAD_ROWS(N));
     a.gscale = gscale; a.ginv = 1.0f / gscale;
-    a.rgb = rgb; a.target = target; a.drgb = drgb; a.save_x = save_x; a.save_t = save_t;
+    a.save_x = save_x; a.save_t = save_t;
     a.stream = reinterpret_cast<const unsigned char*>(wstream_bwd2); a.params = params; a.n_block = n_block;
-    a.grad_scale = grad_scale; a.dpre = dpre; a.gx = gx; a.gt = gt; a.sqerr_partial = sqerr_partial; a.N = N;
+    a.gx = gx; a.gt = gt; a.N = N;
     a.mid_units = plan.stash_mid ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     static int solo_ok[2] = {0, 0};

@@ -7,12 +7,8 @@
 #include "r2l_coopf.h"
 #include <type_traits>
 
-__host__ __device__ static inline int64_t cf_off_tail_w(int n_block) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)2 * n_block * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t cf_off_tail_b(int n_block) { return cf_off_tail_w(n_block) + 3 * R2L_W; }
-
 struct CfFwdArgs {
+    // (the members of R2LRayIn, r2l_student_net.h, but for the pose table: one pose per launch)
     const float* rays_o;
     const float* rays_d;
     const float* t_rand;
@@ -65,6 +61,10 @@ __device__ __forceinline__ void cf_fwd_body(const CfFwdArgs& a, const int64_t ti
         const int pr = threadIdx.x & 31, grp = threadIdx.x >> 5;
         const int64_t ray = tile[rt] * R2L_TILE_RAYS + pr;
         const int64_t rc = ray < a.N ? ray : a.N - 1;
+        // r2l_ray_of_row / r2l_ray_of_pixel<false> and r2l_depths (r2l_student_net.h), on this kernel's own lines: through the helpers the
+        // one-tile instances differ from before in ~30 instruction lines of their prologue, and the 4096-ray training step measured
+        // 0.25 % slower, beyond the parent's run-to-run spread of 0.10 % (profiles/student_net_ab.txt).  The pixel ray is pixel_ray's,
+        // operation for operation (tests/test_student_forward_gpu.py holds the bits to those of r2l_frame_rays).
         float o[3], d[3];
         if constexpr (!POSE) {
 #pragma unroll
@@ -99,7 +99,7 @@ __device__ __forceinline__ void cf_fwd_body(const CfFwdArgs& a, const int64_t ti
     FcRing<R> W;
     FcStream P;
     {
-        const unsigned long long sa = (unsigned long long)a.stream;
+        const unsigned long long sa = (unsigned long long)a.stream;  // (r2l_buffer_rsrc, r2l_common.h: its one extra s_mov re-orders this prologue)
         P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
                      (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
         P.voff = (unsigned)lane * 16u + (unsigned)wave * 2048u;
@@ -270,7 +270,7 @@ __device__ __forceinline__ void cf_fwd_body(const CfFwdArgs& a, const int64_t ti
     f2_report_amax(a.status, amax, lane);  // range control (r2l_f2.h): AMAX, and FLAG if this launch belongs to the bf16x3 kernel
 
     // ---- tail: rgb = sigmoid(Wt (x + X_0) + bt): per-wave partial dot products over its 64 features, summed through LDS ----------
-    const float* tw = a.params + cf_off_tail_w(a.n_block) + 4 * h;
+    const float* tw = a.params + r2l_off_tail_w(a.n_block) + 4 * h;
 #pragma unroll
     for (int rt = 0; rt < NT; ++rt) {
         const int64_t ray = tile[rt] * R2L_TILE_RAYS + j;
@@ -352,7 +352,7 @@ __device__ __forceinline__ void cf_fwd_body(const CfFwdArgs& a, const int64_t ti
 #pragma unroll
             for (int c = 0; c < 3; ++c) {
                 const float v = ((red[rj][c] + red[NT * 32 + rj][c]) + (red[2 * NT * 32 + rj][c] + red[3 * NT * 32 + rj][c])) * act_s +
-                                a.params[cf_off_tail_b(a.n_block) + c];
+                                a.params[r2l_off_tail_b(a.n_block) + c];
                 a.rgb[ray * 3 + c] = 1.0f / (1.0f + expf(-v));
             }
         }
@@ -385,20 +385,19 @@ __global__ __launch_bounds__(256, 1) void r2l_coopf_fwd_mixed_kernel(const CfFwd
     else cf_fwd_body<false, SAVE, 1, MID>(a, (int64_t)a.n_two + b, bop_lds, pts, red);  // 2 n_two + (b - n_two)
 }
 
-int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab, const float* c2w_host12,
-                      int H, int W, float focal, const float* wstream2, const float* params, int n_block, float* rgb,
-                      float* save_x, float* save_t, int64_t N, hipStream_t stream, const R2LPlan& plan) {
+int r2l_coopf_forward(const R2LRayIn& rays, const float* wstream2, const float* params, int n_block, float* rgb, float* save_x,
+                      float* save_t, int64_t N, hipStream_t stream, const R2LPlan& plan) {
+    const bool pose = r2l_pose_mode(rays);
     CfFwdArgs a{};
-    a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
+    r2l_set_rays(a, rays);
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = params;
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + r2l_fwd2_status_offset(n_block));
-    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
-    if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
+    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
     a.mid_units = (save_x != nullptr && plan.stash_mid) ? R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) / 16 : 0;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     // up to one workgroup per CU: one ray tile each; beyond, two tiles per workgroup share every weight load; between one and
     // two tiles per CU: the mixed grid (explicit rays only: the single-pose render launches are far above this band)
-    if (const int n_two = plan.n_two; n_two > 0 && !c2w_host12) {
+    if (const int n_two = plan.n_two; n_two > 0 && !pose) {
         a.n_two = n_two;
         a.xcd_major = plan.xcd_major;
         const dim3 grid((unsigned)(tiles - n_two)), block(256);
@@ -411,7 +410,7 @@ int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_r
     const bool two = plan.coop_tiles == 2;
     const dim3 grid((unsigned)(two ? (tiles + 1) / 2 : tiles)), block(256);
     static int solo_ok[4] = {0, 0, 0, 0};  // one-tile kernels: at most one workgroup per CU, verified before the first launch
-    if (c2w_host12) {
+    if (pose) {
         if (two) hipLaunchKernelGGL((r2l_coopf_fwd_kernel<true, false, 2>), grid, block, 0, stream, a);
         else {
             if (int e = fc_check_solo(r2l_coopf_fwd_kernel<true, false, 1>, "r2l_coopf_fwd_kernel<pose>", &solo_ok[0])) return e;

@@ -84,13 +84,3 @@ static inline R2LStreams r2l_fwd_streams(const float* wstream, int n) {
 static inline R2LStreams r2l_bwd_streams(const float* wstream_bwd, int n) {
     return r2l_streams(wstream_bwd, r2l_bwd32_stream_floats(n), r2l_bwd16_stream_floats(n), r2l_bwd3_stream_floats(n), r2l_bwd2_status_offset(n));
 }
-
-// launchers of the cooperative fp16x2 chains (r2l_coopf_fwd.hip / r2l_coopf_bwd.hip), taken instead of r2l_fwd2_forward /
-// r2l_bwd2_backward when the plan's tiling is COOPF: tiles per workgroup, mixed grid and mid halves of the stash as the plan says
-int r2l_coopf_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab, const float* c2w_host12,
-                      int H, int W, float focal, const float* wstream2, const float* params, int n_block, float* rgb,
-                      float* save_x, float* save_t, int64_t N, hipStream_t stream, const R2LPlan& plan);
-int r2l_coopf_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                       const float* wstream_bwd2, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream, float gscale, unsigned* status,
-                       const float* scale_dev, const R2LPlan& plan, int b_start = -1, int b_end = 0);  // blocks b_start (-1: the last) down to b_end

@@ -3,16 +3,7 @@
 // work list and the per-workgroup partial-sum slab; the head gradient's arguments and encoding columns; and the launchers of
 // the backward's stages that r2l_backward.hip (host only) calls.
 #pragma once
-#include "r2l_common.h"
-
-// ---- flat parameter offsets (same as r2l_forward.hip) ---------------------------------------------------------
-__host__ __device__ static inline int64_t b_off_head_b() { return (int64_t)R2L_IN * R2L_W; }
-__host__ __device__ static inline int64_t b_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t b_off_body_b(int layer) { return b_off_body_w(layer) + R2L_W * R2L_W; }
-__host__ __device__ static inline int64_t b_off_tail_w(int n_block) { return b_off_body_w(2 * n_block); }
-__host__ __device__ static inline int64_t b_off_tail_b(int n_block) { return b_off_tail_w(n_block) + 3 * R2L_W; }
+#include "r2l_student_net.h"  // the parameter census (r2l_off_*)
 
 #define DW_CHUNK 64  // rays per work unit
 #ifndef DW_DEPTH
@@ -118,10 +109,6 @@ int r2l_dw_head16_launch(const R2LDwHeadArgs& a, int64_t slices, hipStream_t str
 int r2l_dw16_launch(const R2LDwArgs& a, int64_t wgs, const unsigned* run_unless, hipStream_t stream);
 
 // ---- the stages of a step, one launcher per file (called by r2l_backward_part_cfg, r2l_backward.hip) ---------------------------
-// fp32-MFMA dX chain (r2l_bwd32.hip)
-int r2l_bwd32_backward(const float* rgb, const float* target, const float* drgb, const float* save_x, const float* save_t,
-                       const float* wstream_bwd32, const float* params, int n_block, float grad_scale, float* dpre, float* gx,
-                       float* gt, float* sqerr_partial, int64_t N, hipStream_t stream);
 // opens a step of the fp16 trio in front of its dX chain (r2l_bwd2.hip: the B2S_* status words); drgb: generic mode, else nullptr
 int r2l_bwd2_open_step(unsigned* status, const float* params, int n_block, float grad_scale, const float* drgb, int64_t N,
                        hipStream_t stream);

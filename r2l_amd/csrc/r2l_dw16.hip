@@ -148,12 +148,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw16_kernel(const R2LDwArgs a, con
         if (r1 > Np) r1 = Np;
         const int ntiles = (int)((r1 - r0) / R2L_TILE_RAYS);
         // descriptors based at the first tile of the segment (16 KiB of fp16 stage pieces per tile and operand)
-        const unsigned long long ga = (unsigned long long)G + (unsigned long long)(r0 / R2L_TILE_RAYS) * DW16_OP_BYTES;
-        const unsigned long long aa = (unsigned long long)A + (unsigned long long)(r0 / R2L_TILE_RAYS) * DW16_OP_BYTES;
-        const u32x4 grs = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ga),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ga >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        const u32x4 ars = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)aa),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(aa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
+        const u32x4 grs = r2l_buffer_rsrc(reinterpret_cast<const unsigned char*>(G) + (unsigned long long)(r0 / R2L_TILE_RAYS) * DW16_OP_BYTES);
+        const u32x4 ars = r2l_buffer_rsrc(reinterpret_cast<const unsigned char*>(A) + (unsigned long long)(r0 / R2L_TILE_RAYS) * DW16_OP_BYTES);
         if constexpr (EXACT) {
             // unit q = (tile q >> 1, k-step q & 1) -> ring buffer q & 3: [G hi | A hi | G mid | A mid], 8 KiB each (8 feature
             // tiles T x 1 KiB: T*64 + rq*16 + g*8 + row*2 + h in 16-byte units, rq = ray quad 0..3); 8 loads per wave and unit.
@@ -330,8 +326,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw16_kernel(const R2LDwArgs a, con
         {
             const int n = lane & 31, hh = lane >> 5;
             float* sl = (a.slab != nullptr) ? a.slab + ((int64_t)blockIdx.x * 2 + (layer - first_layer)) * DW_SLAB_FLOATS : nullptr;
-            float* gw = a.grads + b_off_body_w(layer);
-            float* gbias = a.grads + b_off_body_b(layer);
+            float* gw = a.grads + r2l_off_body_w(layer);
+            float* gbias = a.grads + r2l_off_body_b(layer);
             float* rowp = (sl != nullptr ? sl : gw) + (wo * 128 + 4 * hh) * R2L_W + wi * 128 + n;
             if (sl != nullptr) {
 #pragma unroll

@@ -85,7 +85,7 @@ __global__ __launch_bounds__(256) void r2l_dw_reduce_kernel(const float* __restr
         const int slot = layer - (int)((w * upw) / upl);
         s += *reinterpret_cast<const f32x4*>(slab + (w * 2 + slot) * (int64_t)DW_SLAB_FLOATS + 4 * i4);
     }
-    f32x4* g = reinterpret_cast<f32x4*>(grads + b_off_body_w(layer0 + layer)) + i4;
+    f32x4* g = reinterpret_cast<f32x4*>(grads + r2l_off_body_w(layer0 + layer)) + i4;
     *g = *g + s;
 }
 
@@ -219,8 +219,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_body_kernel(const R2LDwArgs a) 
             dw_flush_slab(acc, bsum, a.slab + ((int64_t)blockIdx.x * 2 + (layer - first_layer)) * DW_SLAB_FLOATS, wo, wi,
                           lane);
         } else {
-            float* gw = a.grads + b_off_body_w(layer);
-            float* gb = a.grads + b_off_body_b(layer);
+            float* gw = a.grads + r2l_off_body_w(layer);
+            float* gb = a.grads + r2l_off_body_b(layer);
             dw_flush(acc, bsum, gw, gb, wo, wi, lane);
         }
 #endif
@@ -360,8 +360,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_body3_kernel(const R2LDwArgs a)
             dw_flush_slab(acc, bsum, a.slab + ((int64_t)blockIdx.x * 2 + (layer - first_layer)) * DW_SLAB_FLOATS, wo, wi,
                           lane);
         } else {
-            float* gw = a.grads + b_off_body_w(layer);
-            float* gb = a.grads + b_off_body_b(layer);
+            float* gw = a.grads + r2l_off_body_w(layer);
+            float* gb = a.grads + r2l_off_body_b(layer);
             dw_flush(acc, bsum, gw, gb, wo, wi, lane);
         }
         u += cend - cu;
@@ -525,12 +525,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_body3c_kernel(const R2LDwArgs a
         if (r1 > Np) r1 = Np;
         const int nsteps = (int)((r1 - r0) / 16);  // Np is a multiple of 32: always even
         // descriptors based at the first tile of the segment (+ this wave's eight chunks)
-        const unsigned long long ga = (unsigned long long)(G + r0 * R2L_W + wave * 8 * R2L_CHUNK_PIECE);
-        const unsigned long long aa = (unsigned long long)(A + r0 * R2L_W + wave * 8 * R2L_CHUNK_PIECE);
-        const u32x4 grs = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)ga),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(ga >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        const u32x4 ars = {(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)aa),
-                           (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(aa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
+        const u32x4 grs = r2l_buffer_rsrc(G + r0 * R2L_W + wave * 8 * R2L_CHUNK_PIECE);
+        const u32x4 ars = r2l_buffer_rsrc(A + r0 * R2L_W + wave * 8 * R2L_CHUNK_PIECE);
         // raw quad k of a step: k < 4 gradient chunk pair k, else activation chunk pair k - 4.  Steps past the end are
         // clamped to the last one (harmless reloads: every step issues exactly 8 loads, which keeps vmcnt(7) uniform)
         f32x4 raw[8];
@@ -618,8 +614,8 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_body3c_kernel(const R2LDwArgs a
         {
             const int n = lane & 31, hh = lane >> 5;
             float* sl = (a.slab != nullptr) ? a.slab + ((int64_t)blockIdx.x * 2 + (layer - first_layer)) * DW_SLAB_FLOATS : nullptr;
-            float* gw = a.grads + b_off_body_w(layer);
-            float* gbias = a.grads + b_off_body_b(layer);
+            float* gw = a.grads + r2l_off_body_w(layer);
+            float* gbias = a.grads + r2l_off_body_b(layer);
             float* rowp = (sl != nullptr ? sl : gw) + (wo * 128 + 4 * hh) * R2L_W + wi * 128 + n;
             if (sl != nullptr) {
 #pragma unroll

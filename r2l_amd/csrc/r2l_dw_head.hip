@@ -34,6 +34,7 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_head_kernel(const R2LDwHeadArgs
     const PECol c0 = pe_col(k0), c1 = pe_col(k1);
     const int e0 = k0 < R2L_IN ? k0 : R2L_IN - 1, e1 = k1 < R2L_IN ? k1 : R2L_IN - 1;  // clamped emb columns
     const float m0 = k0 < R2L_IN ? 1.f : 0.f, m1 = k1 < R2L_IN ? 1.f : 0.f;
+    // sample depth z = zl + zs * t_rand: the rule of r2l_depths (r2l_student_net.h), one sample per encoding column
     const float zl0 = from_emb ? 0.f : a.ztab[c0.smp], zs0 = jitter ? a.ztab[16 + c0.smp] : 0.f;
     const float zl1 = from_emb ? 0.f : a.ztab[c1.smp], zs1 = jitter ? a.ztab[16 + c1.smp] : 0.f;
 
@@ -154,7 +155,7 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_head_kernel(const R2LDwHeadArgs
                 }
             }
     if (kq == 0 && wave == 0) {
-        float* gb = a.grads + b_off_head_b();
+        float* gb = a.grads + r2l_off_head_b();
 #pragma unroll
         for (int e = 0; e < 4; ++e) {
             const float s0 = bs0[e] + __shfl_xor(bs0[e], 32);
@@ -181,7 +182,7 @@ __global__ void r2l_head_reduce_kernel(const float* __restrict__ slab, int n_sli
     if (k > R2L_IN) return;
     float s = 0.f;
     for (int sidx = 0; sidx < n_slices; ++sidx) s += slab[(int64_t)sidx * (R2L_W * 1024) + i];
-    if (k == R2L_IN) grads[b_off_head_b() + o] += s;  // column 1008 carries the bias partials
+    if (k == R2L_IN) grads[r2l_off_head_b() + o] += s;  // column 1008 carries the bias partials
     else grads[(int64_t)o * R2L_IN + k] += s;
 }
 

@@ -79,6 +79,7 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_head16_kernel(const R2LDwHeadAr
     const int nrays = (int)(r1 - r0);
     const Head16Pair pc = head16_pair(kq * 128 + wave * 32 + m);
     const bool trig_wave = kq * 128 + wave * 32 + 31 < 480;  // wave-uniform: every lane of this wave holds a (sin, cos) pair
+    // sample depth z = zl + zs * t_rand: the rule of r2l_depths (r2l_student_net.h), one sample per encoding column
     const float zla = a.ztab[pc.smp_a], zsa = JITTER ? a.ztab[16 + pc.smp_a] : 0.f;
     const float zlb = a.ztab[pc.smp_b], zsb = JITTER ? a.ztab[16 + pc.smp_b] : 0.f;
 
@@ -233,7 +234,7 @@ __global__ __launch_bounds__(256, 1) void r2l_dw_head16_kernel(const R2LDwHeadAr
             const float s = bsum[e] + __shfl_xor(bsum[e], 32);
             if (kg == 0) {
                 if (sl) sl[(32 * e + m) * 1024 + R2L_IN] = s;  // the slab row's padding column 1008 carries the bias partial
-                else atomicAdd(a.grads + b_off_head_b() + 32 * e + m, s);
+                else atomicAdd(a.grads + r2l_off_head_b() + 32 * e + m, s);
             }
         }
     }

@@ -32,12 +32,12 @@ __global__ __launch_bounds__(256) void r2l_dw_tail_kernel(const float* __restric
         if (f == 0) { p[3 * R2L_W + 0] = b0; p[3 * R2L_W + 1] = b1; p[3 * R2L_W + 2] = b2; }
         return;
     }
-    float* gw = grads + b_off_tail_w(n_block);
+    float* gw = grads + r2l_off_tail_w(n_block);
     atomicAdd(gw + 0 * R2L_W + f, s0);
     atomicAdd(gw + 1 * R2L_W + f, s1);
     atomicAdd(gw + 2 * R2L_W + f, s2);
     if (f == 0 && r0 < r1) {
-        float* gb = grads + b_off_tail_b(n_block);
+        float* gb = grads + r2l_off_tail_b(n_block);
         atomicAdd(gb + 0, b0);
         atomicAdd(gb + 1, b1);
         atomicAdd(gb + 2, b2);
@@ -59,8 +59,8 @@ __global__ __launch_bounds__(256) void r2l_tail_reduce_kernel(const float* __res
         float t = red[0][threadIdx.x];
 #pragma unroll
         for (int k = 1; k < 8; ++k) t += red[k][threadIdx.x];
-        if (row < 3) grads[b_off_tail_w(n_block) + row * R2L_W + f] += t;
-        else if (f < 3) grads[b_off_tail_b(n_block) + f] += t;
+        if (row < 3) grads[r2l_off_tail_w(n_block) + row * R2L_W + f] += t;
+        else if (f < 3) grads[r2l_off_tail_b(n_block) + f] += t;
     }
 }
 

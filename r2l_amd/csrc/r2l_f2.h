@@ -164,13 +164,6 @@ __device__ __forceinline__ void f2_report_amax(unsigned* st, float amax, int lan
 // half 0 = hi, mid.  The BODY biases are multiplied by inv_s (a power of two: exact); head weights and head bias are packed as
 // they are (the kernels scale the head's fp32 accumulators).  only_scaled: just the stages that depend on the scale (the body's
 // bias stages).
-__host__ __device__ static inline int64_t f2_off_head_b() { return (int64_t)R2L_IN * R2L_W; }
-__host__ __device__ static inline int64_t f2_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t f2_off_body_b(int layer) { return f2_off_body_w(layer) + R2L_W * R2L_W; }
-__host__ __device__ static inline int64_t f2_off_tail_w(int n_block) { return f2_off_body_w(2 * n_block); }
-__host__ __device__ static inline int64_t f2_off_tail_b(int n_block) { return f2_off_tail_w(n_block) + 3 * R2L_W; }
 __device__ __forceinline__ unsigned short f2_bits(_Float16 v) { return __builtin_bit_cast(unsigned short, v); }
 // one element (stage g, index `within` = ((tile * 64) + lane) * 8 + s of its 4096) of the stream
 __device__ __forceinline__ void f2_pack_fwd_element(const float* __restrict__ params, unsigned short* __restrict__ out, int n_block,
@@ -184,7 +177,7 @@ __device__ __forceinline__ void f2_pack_fwd_element(const float* __restrict__ pa
         float w = 0.f;
         if (g == 0) {
             bias_stage = true;
-            w = params[f2_off_head_b() + o];
+            w = params[r2l_off_head_b() + o];
         } else if (g < 64) {
             const int v = 8 * (int)(g - 1) + s;
             int col;
@@ -200,11 +193,11 @@ __device__ __forceinline__ void f2_pack_fwd_element(const float* __restrict__ pa
             const int layer = (int)((g - 64) / 17), r17 = (int)((g - 64) % 17);
             if (r17 == 0) {
                 bias_stage = true;
-                w = params[f2_off_body_b(layer) + o] * inv_s;
+                w = params[r2l_off_body_b(layer) + o] * inv_s;
             } else {
                 const int kb = r17 - 1, T = kb >> 1, r = kb & 1;
                 const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-                w = params[f2_off_body_w(layer) + (int64_t)o * R2L_W + in];
+                w = params[r2l_off_body_w(layer) + (int64_t)o * R2L_W + in];
             }
         }
         const _Float16 hi = (_Float16)w;
@@ -464,6 +457,19 @@ struct F2Pipe {
     F2Split sb;
     F2Split ones;
     float amax;  // max |B value| seen by this lane
+    // stage 0 of `stream` goes to buffer 0 at `lds_base`; the four waves fetch a quarter of every stage each
+    __device__ __forceinline__ void init(const unsigned char* stream, const unsigned char* lds_base, int lane_, int wave) {
+        rs = r2l_buffer_rsrc(stream);
+        lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)lds_base;
+        voff = (unsigned)lane_ * 16u;
+        wq = (unsigned)wave * (F2_STAGE_BYTES / 4);
+        base = lds_base;
+        lane = lane_;
+        gb = 0;
+        gq = 0;
+        gqb = 0;
+        amax = 0.f;
+    }
     __device__ __forceinline__ void issue() {
         const unsigned so = (unsigned)gq * F2_STAGE_BYTES + wq;
         const unsigned la = lds0 + (unsigned)gqb * F2_STAGE_BYTES + wq;

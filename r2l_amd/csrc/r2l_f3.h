@@ -3,7 +3,7 @@
 // with its hand-interleaved side work.  See the header comment of r2l_fwd3.hip for the scheme.  The gatherers at the end
 // (layer inputs with their ride-along stash stores, positional-encoding values) are shared with the fp16x2 kernels (r2l_f2.h).
 #pragma once
-#include "r2l_common.h"
+#include "r2l_student_net.h"
 
 typedef __bf16 bf16x8 __attribute__((ext_vector_type(8)));
 typedef float f32x8 __attribute__((ext_vector_type(8)));
@@ -158,6 +158,18 @@ struct F3PipeT {
     F3A4 a1, a2;         // A operands: first / second half of the current stage
     F3Split sb;          // B triple of the current stage
     F3Split ones;
+    // stage 0 of `stream` goes to buffer 0 at `lds_base`; the four waves fetch a quarter of every stage each
+    __device__ __forceinline__ void init(const unsigned char* stream, const unsigned char* lds_base, int lane_, int wave) {
+        rs = r2l_buffer_rsrc(stream);
+        lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) const unsigned char*)lds_base;
+        voff = (unsigned)lane_ * 16u;
+        wq = (unsigned)wave * (F3_STAGE_BYTES / 4);
+        base = lds_base;
+        lane = lane_;
+        gb = 0;
+        gq = 0;
+        gqb = 0;
+    }
     __device__ __forceinline__ void issue() {
         const unsigned so = (unsigned)gq * F3_STAGE_BYTES + wq;
         const unsigned la = lds0 + (unsigned)gqb * F3_STAGE_BYTES + wq;

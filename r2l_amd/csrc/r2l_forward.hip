@@ -6,17 +6,18 @@
 //
 // One wavefront = 32 rays for the whole network, activations register-resident in MFMA fragment layout
 // (see r2l_common.h); exact-fp32 v_mfma_f32_32x32x2_f32; 4 independent waves per 256-thread block, one per SIMD.
-#include "r2l_dispatch.h"
+#include "r2l_student_net.h"
 
 struct R2LFwdArgs {
-    // inputs (exactly one of {rays_o/rays_d}, {pose}, {emb} is used, selected by the MODE template argument)
+    // inputs (exactly one of {rays_o / rays_d}, {pose}, {emb} is used, selected by the MODE template argument)
+    // (the members of R2LRayIn, r2l_student_net.h, in the order this kernel's arguments have always had)
     const float* rays_o;   // [N,3]
     const float* rays_d;   // [N,3]
     const float* t_rand;   // [N,16] stratified jitter U[0,1) or nullptr (perturb == 0)
     const float* emb;      // [N,1008] pre-embedded input (module-boundary compatibility path)
     const float* ztab;     // [32]: z_lower[16], z_span[16]  (z = z_lower + z_span * t_rand ; z = z_lower if !t_rand)
     float c2w[12];         // row-major [3,4] camera-to-world (pose mode)
-    const float* c2w_dev;  // several frames per launch: [K][12] on the device (r2l_common.h r2l_pose_of), else nullptr
+    const float* c2w_dev;  // several frames per launch: [K][12] on the device (r2l_pose_of), else nullptr
     int H, Wimg;
     float focal;
     // parameters
@@ -29,15 +30,6 @@ struct R2LFwdArgs {
     float* save_t;         // [n_block][Np][256]     relu(hidden) of each block      or nullptr
     int64_t N;
 };
-
-// ---- flat parameter buffer offsets (state_dict order: head.0.{weight,bias}, body.b.body.{0,2}.{weight,bias}, tail.0.*)
-__host__ __device__ __forceinline__ int64_t off_head_b() { return (int64_t)R2L_IN * R2L_W; }
-__host__ __device__ __forceinline__ int64_t off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ __forceinline__ int64_t off_body_b(int layer) { return off_body_w(layer) + R2L_W * R2L_W; }
-__host__ __device__ __forceinline__ int64_t off_tail_w(int n_block) { return off_body_w(2 * n_block); }
-__host__ __device__ __forceinline__ int64_t off_tail_b(int n_block) { return off_tail_w(n_block) + 3 * R2L_W; }
 
 enum { MODE_RAYS = 0, MODE_POSE = 1, MODE_EMB = 2 };
 
@@ -84,15 +76,13 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_kernel(const R2LFwdArgs a) {
         }
     } else {
         float o[3], d[3];
-        if constexpr (MODE == MODE_RAYS) {
-#pragma unroll
-            for (int k = 0; k < 3; ++k) {
-                o[k] = a.rays_o[rc * 3 + k];
-                d[k] = a.rays_d[rc * 3 + k];
-            }
-        } else {
-            // PointSampler.__init__/sample_test (nerf_raybased.py:80-99): dirs = [(i-W/2)/f, -(j-H/2)/f, -1],
-            // rays_d[k] = sum_b dirs[b] * c2w[k][b], rays_o = c2w[:,3]
+        if constexpr (MODE == MODE_RAYS) r2l_ray_of_row(a.rays_o, a.rays_d, rc, o, d);
+        else {
+            // r2l_ray_of_pixel<true> (r2l_student_net.h), on this kernel's own lines: with pixel_ray's empty asm between the products
+            // hipcc re-allocates 1232 of this kernel's 10274 instruction lines, and the graded 9-frame render measured 0.03 %, 0.05 %
+            // and 0.12 % slower in three sessions — each within the parent's run-to-run spread, all of one sign
+            // (profiles/student_net_ab.txt).  Same operations in the same order: PointSampler.__init__ / sample_test
+            // (nerf_raybased.py:80-99); tests/test_student_forward_gpu.py holds the bits to those of r2l_frame_rays.
             const R2LPoseRay pr = r2l_pose_of(a.c2w, a.c2w_dev, (int64_t)a.H * a.Wimg, rc);
             const int pj = (int)(pr.pix / a.Wimg), pi = (int)(pr.pix % a.Wimg);
             const float dx = ((float)pi - (float)a.Wimg * 0.5f) / a.focal;
@@ -104,28 +94,8 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_kernel(const R2LFwdArgs a) {
                 o[k] = pr.c[4 * k + 3];
             }
         }
-        // the 8 sample depths of this half-wave (samples 8h .. 8h+7)
-        float z[8];
-        {
-            const f32x4 lo0 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h);
-            const f32x4 lo1 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h + 4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) {
-                z[k] = lo0[k];
-                z[4 + k] = lo1[k];
-            }
-            if (a.t_rand != nullptr) {  // z = lower + (upper-lower) * t_rand   (nerf_raybased.py:119-123)
-                const f32x4 sp0 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h);
-                const f32x4 sp1 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h + 4);
-                const f32x4 u0 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h);
-                const f32x4 u1 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h + 4);
-#pragma unroll
-                for (int k = 0; k < 4; ++k) {
-                    z[k] = lo0[k] + sp0[k] * u0[k];
-                    z[4 + k] = lo1[k] + sp1[k] * u1[k];
-                }
-            }
-        }
+        float z[8];  // the 8 sample depths of this half-wave (samples 8h .. 8h+7)
+        r2l_depths(a.ztab, a.t_rand, rc, 8 * h, z);
         // trig features: per coordinate [sin(2^0 x) .. sin(2^9 x), cos(2^0 x) .. cos(2^9 x)]   (nerf_raybased.py:199-203)
         // Software pipeline: while the 5 groups (160 MFMAs) of coordinate c run, the VALU evaluates the 10 sin/cos
         // pairs of coordinate c+1 (two per group, slotted between the MFMAs by the schedule pin).
@@ -213,7 +183,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_kernel(const R2LFwdArgs a) {
     if constexpr (SAVE) store_frag(a.save_x + (int64_t)a.n_block * Np * R2L_W, ray, h, x);
 
     // tail: rgb = sigmoid(Wt (x + X_0) + bt)
-    const float* tw = a.params + off_tail_w(a.n_block);
+    const float* tw = a.params + r2l_off_tail_w(a.n_block);
     float acc3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int T = 0; T < R2L_NT; ++T)
@@ -229,10 +199,12 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd_kernel(const R2LFwdArgs a) {
                 for (int c = 0; c < 3; ++c) acc3[c] = __builtin_fmaf(wv[c][j], y, acc3[c]);
             }
         }
+    // (r2l_tail_finish of r2l_student_net.h, on this kernel's own lines: it evaluates the sigmoid in every lane and predicates only
+    // the store; in the helper's form — sigmoid under the predicate — hipcc re-allocates ~780 instruction lines of this kernel)
 #pragma unroll
     for (int c = 0; c < 3; ++c) {
         acc3[c] += __shfl_xor(acc3[c], 32);
-        const float v = acc3[c] + a.params[off_tail_b(a.n_block) + c];
+        const float v = acc3[c] + a.params[r2l_off_tail_b(a.n_block) + c];
         acc3[c] = 1.0f / (1.0f + expf(-v));
     }
     if (valid && h == 0) {
@@ -259,30 +231,28 @@ static int launch_fwd(const R2LFwdArgs& a, hipStream_t stream) {
 // C ABI (declared in include/r2l_hip.h)
 // ------------------------------------------------------------------------------------------------------------------
 // One forward launch, as the plan says, of the rays in `a`: given explicitly (rays_o / rays_d, with or without the training
-// stash), by one pose (c2w_host12: a.c2w), or by a device table of poses (c2w_dev: several frames).  Behind a fp16x2 launch
+// stash), by one pose (a.c2w), or by a device table of poses (a.c2w_dev: several frames).  Behind a fp16x2 launch
 // comes its range-guard fallback: stream pack + the bf16x3 launch, both returning at once unless it raised its status word.
-static int forward_launch(const R2LPlan& plan, const R2LFwdArgs& a, const float* c2w_host12, const float* c2w_dev, hipStream_t stream) {
+static int forward_launch(const R2LPlan& plan, const R2LFwdArgs& a, hipStream_t stream) {
     const R2LStreams w = r2l_fwd_streams(a.wstream, a.n_block);
+    R2LRayIn rays{a.rays_o, a.rays_d, a.t_rand, a.ztab, {}, a.c2w_dev, a.H, a.Wimg, a.focal};
+    for (int i = 0; i < 12; ++i) rays.c2w[i] = a.c2w[i];
     if (plan.fwd == R2L_CHAIN_COOP16)
-        return r2l_coop16_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w16, a.params, a.n_block,
-                                  a.rgb, a.save_x, a.save_t, a.N, stream);
+        return r2l_coop16_forward(rays, w.w16, a.params, a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream);
     const unsigned* run_if = nullptr;
     if (plan.fwd == R2L_CHAIN_FP16) {
         // small launches: one 32-ray tile per workgroup instead of per wave (r2l_coopf_fwd.hip), same stream / stash / status word
         const int rc = plan.tiling == R2L_TILING_COOPF
-                           ? r2l_coopf_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w2, a.params,
-                                               a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, plan)
-                           : r2l_fwd2_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w2, a.params,
-                                              a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, c2w_dev, plan.stash_mid);
+                           ? r2l_coopf_forward(rays, w.w2, a.params, a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, plan)
+                           : r2l_fwd2_forward(rays, w.w2, a.params, a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, plan.stash_mid);
         if (rc) return rc;
         const int rp = r2l_fwd2_fallback_pack(a.params, a.n_block, w.w3, w.w2, stream);
         if (rp) return rp;
         run_if = w.status + F2S_GO;
     }
     if (plan.fwd == R2L_CHAIN_FP16 || plan.fwd == R2L_CHAIN_BF16X3)
-        return r2l_fwd3_forward(a.rays_o, a.rays_d, a.t_rand, a.ztab, c2w_host12, a.H, a.Wimg, a.focal, w.w3, a.params, a.n_block,
-                                a.rgb, a.save_x, a.save_t, a.N, stream, run_if, nullptr, c2w_dev);
-    if (c2w_host12 == nullptr) return launch_fwd<MODE_RAYS>(a, stream);
+        return r2l_fwd3_forward(rays, w.w3, a.params, a.n_block, a.rgb, a.save_x, a.save_t, a.N, stream, run_if);
+    if (!r2l_pose_mode(rays)) return launch_fwd<MODE_RAYS>(a, stream);
     return launch_fwd<MODE_POSE>(a, stream);
 }
 
@@ -306,7 +276,7 @@ extern "C" int r2l_forward_rays_cfg(const float* rays_o, const float* rays_d, co
     a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.wstream = wstream; a.params = params; a.n_block = n_block;
     a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
-    return forward_launch(r2l_plan(cfg, N, n_block, save_x != nullptr, false), a, nullptr, nullptr, (hipStream_t)stream);
+    return forward_launch(r2l_plan(cfg, N, n_block, save_x != nullptr, false), a, (hipStream_t)stream);
 }
 
 extern "C" int r2l_forward_pose(const float* c2w_host12, int H, int W, float focal, const float* ztab,
@@ -330,7 +300,7 @@ static int forward_poses(const r2l_config* cfg, const float* c2w_host12, const f
                           "call r2l_forward_pose per frame)");
         return (int)hipErrorInvalidValue;
     }
-    return forward_launch(plan, a, c2w_host12 ? c2w_host12 : a.c2w, c2w_dev, (hipStream_t)stream);
+    return forward_launch(plan, a, (hipStream_t)stream);
 }
 
 extern "C" int r2l_forward_pose_cfg(const float* c2w_host12, int H, int W, float focal, const float* ztab,
@@ -381,8 +351,8 @@ extern "C" int r2l_forward_emb_cfg(const float* emb, const float* wstream, const
     a.rgb = rgb; a.save_x = x0_scratch; a.save_t = nullptr; a.N = N;
     const int rc = launch_fwd<MODE_EMB>(a, (hipStream_t)stream);
     if (rc) return rc;
-    return r2l_fwd3_forward(nullptr, nullptr, nullptr, nullptr, nullptr, 0, 0, 0.f, r2l_fwd_streams(wstream, n_block).w3, params,
-                            n_block, rgb, nullptr, nullptr, N, (hipStream_t)stream, nullptr, x0_scratch);
+    return r2l_fwd3_forward(R2LRayIn{}, r2l_fwd_streams(wstream, n_block).w3, params, n_block, rgb, nullptr, nullptr, N,
+                            (hipStream_t)stream, nullptr, x0_scratch);
 }
 
 extern "C" int r2l_forward_emb(const float* emb, const float* wstream, const float* params, int n_block, float* rgb,

@@ -31,14 +31,7 @@ __global__ void r2l_fwd2_commit_kernel(unsigned* status) {
 // forward
 // =================================================================================================================
 struct F2Args {
-    const float* rays_o;
-    const float* rays_d;
-    const float* t_rand;
-    const float* ztab;
-    float c2w[12];
-    const float* c2w_dev;  // several frames per launch: [K][12] on the device (r2l_common.h r2l_pose_of), else nullptr
-    int H, Wimg;
-    float focal;
+    R2LRayIn rays;                // (r2l_student_net.h)
     const unsigned char* stream;  // fwd2 stage stream
     unsigned* status;             // range-guard word behind the stream: != 0 -> this launch is left to the bf16x3 kernel
     const float* params;
@@ -71,7 +64,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd2_kernel(const F2Args a) {
 
     // an earlier launch with these weights left fp16's range: the bf16x3 kernel behind this one does the work
     if (__builtin_nontemporal_load(a.status) != 0u) return;
-    for (int i = threadIdx.x; i < 3 * R2L_W + 3; i += 256) tail_w[i] = a.params[f2_off_tail_w(a.n_block) + i];  // (W then b: contiguous)
+    for (int i = threadIdx.x; i < 3 * R2L_W + 3; i += 256) tail_w[i] = a.params[r2l_off_tail_w(a.n_block) + i];  // (W then b: contiguous)
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     // every wave of the workgroup takes part in the weight staging and the barriers: a wave whose tile lies past the end
@@ -85,55 +78,14 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd2_kernel(const F2Args a) {
 
     // ---- rays -----------------------------------------------------------------------------------------------------------
     float o[3], d[3];
-    if constexpr (!POSE) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o[k] = a.rays_o[rc * 3 + k];
-            d[k] = a.rays_d[rc * 3 + k];
-        }
-    } else {
-        const R2LPoseRay pr = r2l_pose_of(a.c2w, a.c2w_dev, (int64_t)a.H * a.Wimg, rc);
-        const int pj = (int)(pr.pix / a.Wimg), pi = (int)(pr.pix % a.Wimg);
-        const float dx = ((float)pi - (float)a.Wimg * 0.5f) / a.focal;
-        const float dy = -(((float)pj - (float)a.H * 0.5f) / a.focal);
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            d[k] = (dx * pr.c[4 * k + 0] + dy * pr.c[4 * k + 1]) + (-1.0f) * pr.c[4 * k + 2];
-            o[k] = pr.c[4 * k + 3];
-        }
-    }
+    if constexpr (!POSE) r2l_ray_of_row(a.rays.rays_o, a.rays.rays_d, rc, o, d);
+    else r2l_ray_of_pixel<true>(a.rays.c2w, a.rays.c2w_dev, a.rays.H, a.rays.Wimg, a.rays.focal, rc, o, d);
     float z[8];  // the 8 sample depths of this half-wave (samples 8h .. 8h+7)
-    {
-        const f32x4 lo0 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h);
-        const f32x4 lo1 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { z[k] = lo0[k]; z[4 + k] = lo1[k]; }
-        if (a.t_rand != nullptr) {
-            const f32x4 sp0 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h);
-            const f32x4 sp1 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h + 4);
-            const f32x4 u0 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h);
-            const f32x4 u1 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h + 4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { z[k] = lo0[k] + sp0[k] * u0[k]; z[4 + k] = lo1[k] + sp1[k] * u1[k]; }
-        }
-    }
+    r2l_depths(a.rays.ztab, a.rays.t_rand, rc, 8 * h, z);
 
     // ---- weight staging: stage g of the stream is DMA'd into LDS buffer g % 6 by the four waves (a quarter each) ----------
     F2Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 4096u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-        P.amax = 0.f;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
 #pragma unroll
     for (int k = 0; k < F2_NBUF - 1; ++k) P.issue();  // stages 0 .. F2_NBUF-2
 #pragma unroll
@@ -343,15 +295,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd2_kernel(const F2Args a) {
 #pragma unroll
         for (int c = 0; c < 3; ++c) p3[c] = a2[c][0] + a2[c][1];
     }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p3[c] += __shfl_xor(p3[c], 32);
-    if (valid && h == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = p3[c] * act_s + tail_w[3 * R2L_W + c];  // (the chain ran on y / act_s: exact)
-            a.rgb[ray * 3 + c] = 1.0f / (1.0f + expf(-v));
-        }
-    }
+    r2l_tail_finish<true>(p3, tail_w + 3 * R2L_W, act_s, a.rgb, ray, valid && h == 0);  // (the chain ran on y / act_s: exact)
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -367,22 +311,19 @@ int r2l_fwd2_pack(const float* params, int n_block, float* wstream2, hipStream_t
     return 0;
 }
 
-int r2l_fwd2_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                     const float* c2w_host12, int H, int W, float focal, const float* wstream2, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const float* c2w_dev, bool stash_mid) {
+int r2l_fwd2_forward(const R2LRayIn& rays, const float* wstream2, const float* params, int n_block, float* rgb, float* save_x,
+                     float* save_t, int64_t N, hipStream_t stream, bool stash_mid) {
+    const bool pose = r2l_pose_mode(rays);
     F2Args a{};
-    a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
+    a.rays = rays;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = params;
     // the status word lives in the caller's stream buffer (library-private contents): written through, hence the cast
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + r2l_fwd2_status_offset(n_block));
-    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
-    if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.c2w_dev = c2w_host12 ? c2w_dev : nullptr;
+    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
     a.stash_mid = (save_x != nullptr && stash_mid) ? (unsigned)R2L_H16_MID_BYTES(R2L_PAD_ROWS(N)) : 0u;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
-    if (c2w_host12) hipLaunchKernelGGL((r2l_fwd2_kernel<true, false>), grid, block, 0, stream, a);
+    if (pose) hipLaunchKernelGGL((r2l_fwd2_kernel<true, false>), grid, block, 0, stream, a);
     else if (save_x && a.stash_mid != 0u) hipLaunchKernelGGL((r2l_fwd2_kernel<false, true, true>), grid, block, 0, stream, a);
     else if (save_x) hipLaunchKernelGGL((r2l_fwd2_kernel<false, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((r2l_fwd2_kernel<false, false>), grid, block, 0, stream, a);

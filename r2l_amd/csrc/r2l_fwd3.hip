@@ -20,14 +20,6 @@
 // it also writes the training stash (chunked layout + ReLU mask words, r2l_common.h).
 #include "r2l_f2.h"  // (r2l_f3.h + the fp16x2 stream's range control: this file holds its fallback pack)
 
-__host__ __device__ static inline int64_t f3_off_head_b() { return (int64_t)R2L_IN * R2L_W; }
-__host__ __device__ static inline int64_t f3_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
-__host__ __device__ static inline int64_t f3_off_body_b(int layer) { return f3_off_body_w(layer) + R2L_W * R2L_W; }
-__host__ __device__ static inline int64_t f3_off_tail_w(int n_block) { return f3_off_body_w(2 * n_block); }
-__host__ __device__ static inline int64_t f3_off_tail_b(int n_block) { return f3_off_tail_w(n_block) + 3 * R2L_W; }
-
 // =================================================================================================================
 // pack: flat fp32 parameters -> stage stream.  Stage g: 0 = head bias, 1..63 = head k-blocks, then per body layer
 // [bias stage, 16 k-block stages].  A stage is [split sp][tile t][lane (i,h)][slot s] bf16: split sp of
@@ -52,7 +44,7 @@ __device__ __forceinline__ void f3_pack_fwd_elements(const float* __restrict__ p
             float w = 0.f;
             if (g == 0) {
                 bias_stage = true;
-                w = params[f3_off_head_b() + o];
+                w = params[r2l_off_head_b() + o];
             } else if (g < 64) {
                 const int v = 8 * (int)(g - 1) + s;
                 int col;
@@ -68,11 +60,11 @@ __device__ __forceinline__ void f3_pack_fwd_elements(const float* __restrict__ p
                 const int layer = (int)((g - 64) / 17), r17 = (int)((g - 64) % 17);
                 if (r17 == 0) {
                     bias_stage = true;
-                    w = params[f3_off_body_b(layer) + o];
+                    w = params[r2l_off_body_b(layer) + o];
                 } else {
                     const int kb = r17 - 1, T = kb >> 1, r = kb & 1;
                     const int in = 32 * T + 8 * (2 * r + (s >> 2)) + 4 * h + (s & 3);
-                    w = params[f3_off_body_w(layer) + (int64_t)o * R2L_W + in];
+                    w = params[r2l_off_body_w(layer) + (int64_t)o * R2L_W + in];
                 }
             }
             const unsigned short hi = f3_bf16_rne(w);
@@ -120,14 +112,7 @@ __global__ void r2l_fwd2_fallback_pack_kernel(const float* __restrict__ params, 
 // forward
 // =================================================================================================================
 struct F3Args {
-    const float* rays_o;
-    const float* rays_d;
-    const float* t_rand;
-    const float* ztab;
-    float c2w[12];
-    const float* c2w_dev;  // several frames per launch: [K][12] on the device (r2l_common.h r2l_pose_of), else nullptr
-    int H, Wimg;
-    float focal;
+    R2LRayIn rays;                // (r2l_student_net.h)
     const unsigned char* stream;  // fwd3 stage stream
     const unsigned* run_if;       // nullptr, or: return at once while this word is 0 (range-guard fallback of r2l_fwd2.hip)
     const float* params;
@@ -161,17 +146,16 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd3_kernel(const F3Args a) {
     // ---- rays -----------------------------------------------------------------------------------------------------------
     float o[3], d[3];  // (X0: unused — the head is not part of the launch)
     if constexpr (X0) {
-    } else if constexpr (!POSE) {
-#pragma unroll
-        for (int k = 0; k < 3; ++k) {
-            o[k] = a.rays_o[rc * 3 + k];
-            d[k] = a.rays_d[rc * 3 + k];
-        }
-    } else {
-        const R2LPoseRay pr = r2l_pose_of(a.c2w, a.c2w_dev, (int64_t)a.H * a.Wimg, rc);
-        const int pj = (int)(pr.pix / a.Wimg), pi = (int)(pr.pix % a.Wimg);
-        const float dx = ((float)pi - (float)a.Wimg * 0.5f) / a.focal;
-        const float dy = -(((float)pj - (float)a.H * 0.5f) / a.focal);
+    } else if constexpr (!POSE) r2l_ray_of_row(a.rays.rays_o, a.rays.rays_d, rc, o, d);
+    else {
+        // r2l_ray_of_pixel<true> (r2l_student_net.h), on this kernel's own lines: with pixel_ray's empty asm between the products
+        // the 9-frame render of this kernel measured 0.22 % slower, beyond the parent's run-to-run spread of 0.19 %
+        // (profiles/student_net_ab.txt).  Same operations in the same order: tests/test_student_forward_gpu.py holds the bits
+        // to those of r2l_frame_rays.
+        const R2LPoseRay pr = r2l_pose_of(a.rays.c2w, a.rays.c2w_dev, (int64_t)a.rays.H * a.rays.Wimg, rc);
+        const int pj = (int)(pr.pix / a.rays.Wimg), pi = (int)(pr.pix % a.rays.Wimg);
+        const float dx = ((float)pi - (float)a.rays.Wimg * 0.5f) / a.rays.focal;
+        const float dy = -(((float)pj - (float)a.rays.H * 0.5f) / a.rays.focal);
 #pragma unroll
         for (int k = 0; k < 3; ++k) {
             d[k] = (dx * pr.c[4 * k + 0] + dy * pr.c[4 * k + 1]) + (-1.0f) * pr.c[4 * k + 2];
@@ -179,36 +163,11 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd3_kernel(const F3Args a) {
         }
     }
     float z[8];  // the 8 sample depths of this half-wave (samples 8h .. 8h+7)
-    if constexpr (!X0) {
-        const f32x4 lo0 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h);
-        const f32x4 lo1 = *reinterpret_cast<const f32x4*>(a.ztab + 8 * h + 4);
-#pragma unroll
-        for (int k = 0; k < 4; ++k) { z[k] = lo0[k]; z[4 + k] = lo1[k]; }
-        if (a.t_rand != nullptr) {
-            const f32x4 sp0 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h);
-            const f32x4 sp1 = *reinterpret_cast<const f32x4*>(a.ztab + 16 + 8 * h + 4);
-            const f32x4 u0 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h);
-            const f32x4 u1 = *reinterpret_cast<const f32x4*>(a.t_rand + rc * 16 + 8 * h + 4);
-#pragma unroll
-            for (int k = 0; k < 4; ++k) { z[k] = lo0[k] + sp0[k] * u0[k]; z[4 + k] = lo1[k] + sp1[k] * u1[k]; }
-        }
-    }
+    if constexpr (!X0) r2l_depths(a.rays.ztab, a.rays.t_rand, rc, 8 * h, z);
 
     // ---- weight staging: stage g of the stream is DMA'd into LDS buffer g % 6 by the four waves (a quarter each) ----------
     F3Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 6144u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
     P.issue(); P.issue(); P.issue(); P.issue(); P.issue();  // stages 0..4
 #pragma unroll
     for (int k = 0; k < 8; ++k) P.ones.h[k] = (__bf16)((h == 0 && k < 3) ? 1.0f : 0.0f);
@@ -348,7 +307,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd3_kernel(const F3Args a) {
     }
 
     // ---- tail: rgb = sigmoid(Wt (x + X_0) + bt) on the VALU -------------------------------------------------------------
-    const float* tw = a.params + f3_off_tail_w(a.n_block) + 4 * h;
+    const float* tw = a.params + r2l_off_tail_w(a.n_block) + 4 * h;
     float p3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
     for (int T = 0; T < R2L_NT; ++T)
@@ -364,15 +323,7 @@ __global__ __launch_bounds__(256, 1) void r2l_fwd3_kernel(const F3Args a) {
                 for (int c = 0; c < 3; ++c) p3[c] = __builtin_fmaf(wv[c][e], y, p3[c]);
             }
         }
-#pragma unroll
-    for (int c = 0; c < 3; ++c) p3[c] += __shfl_xor(p3[c], 32);
-    if (valid && h == 0) {
-#pragma unroll
-        for (int c = 0; c < 3; ++c) {
-            const float v = p3[c] + a.params[f3_off_tail_b(a.n_block) + c];
-            a.rgb[ray * 3 + c] = 1.0f / (1.0f + expf(-v));
-        }
-    }
+    r2l_tail_finish<false>(p3, a.params + r2l_off_tail_b(a.n_block), 1.0f, a.rgb, ray, valid && h == 0);
 }
 
 // ------------------------------------------------------------------------------------------------------------------
@@ -393,24 +344,20 @@ int r2l_fwd2_fallback_pack(const float* params, int n_block, float* wstream3, fl
     return 0;
 }
 
-int r2l_fwd3_forward(const float* rays_o, const float* rays_d, const float* t_rand, const float* ztab,
-                     const float* c2w_host12, int H, int W, float focal, const float* wstream3, const float* params,
-                     int n_block, float* rgb, float* save_x, float* save_t, int64_t N, hipStream_t stream,
-                     const unsigned* run_if, const float* x0_in, const float* c2w_dev) {
+int r2l_fwd3_forward(const R2LRayIn& rays, const float* wstream3, const float* params, int n_block, float* rgb, float* save_x,
+                     float* save_t, int64_t N, hipStream_t stream, const unsigned* run_if, const float* x0_in) {
     F3Args a{};
+    a.rays = rays;
     a.run_if = run_if;
-    a.rays_o = rays_o; a.rays_d = rays_d; a.t_rand = t_rand; a.ztab = ztab;
     a.stream = reinterpret_cast<const unsigned char*>(wstream3); a.params = params;
-    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N; a.H = H; a.Wimg = W; a.focal = focal;
-    if (c2w_host12) for (int i = 0; i < 12; ++i) a.c2w[i] = c2w_host12[i];
-    a.c2w_dev = c2w_host12 ? c2w_dev : nullptr;
+    a.n_block = n_block; a.rgb = rgb; a.save_x = save_x; a.save_t = save_t; a.N = N;
     const int64_t tiles = (N + R2L_TILE_RAYS - 1) / R2L_TILE_RAYS;
     const dim3 grid((unsigned)((tiles + 3) / 4)), block(256);
     if (x0_in != nullptr) {  // body + tail from a given X_0: the stream starts at the first body stage
         a.x0_in = x0_in;
         a.stream += (size_t)64 * F3_STAGE_BYTES;
         hipLaunchKernelGGL((r2l_fwd3_kernel<false, false, true>), grid, block, 0, stream, a);
-    } else if (c2w_host12) hipLaunchKernelGGL((r2l_fwd3_kernel<true, false>), grid, block, 0, stream, a);
+    } else if (r2l_pose_mode(rays)) hipLaunchKernelGGL((r2l_fwd3_kernel<true, false>), grid, block, 0, stream, a);
     else if (save_x) hipLaunchKernelGGL((r2l_fwd3_kernel<false, true>), grid, block, 0, stream, a);
     else hipLaunchKernelGGL((r2l_fwd3_kernel<false, false>), grid, block, 0, stream, a);
     R2L_CHECK(hipGetLastError());

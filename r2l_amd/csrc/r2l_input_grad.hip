@@ -147,7 +147,7 @@ __global__ __launch_bounds__(256, 1) void r2l_input_grad_kernel(const R2LInputGr
 #pragma unroll
         for (int sp = 0; sp < 4; ++sp) {
             const int s = 4 * pass + sp;
-            const float zl = a.ztab[s];
+            const float zl = a.ztab[s];  // (the depth rule of r2l_depths, r2l_student_net.h; jitter is a run-time flag here)
             z[sp] = zl;
             if (jitter) z[sp] = zl + a.ztab[16 + s] * a.t_rand[rl * 16 + s];
 #pragma unroll

@@ -1,11 +1,7 @@
 // r2l_pack.hip — re-pack the nn.Linear weights of NeRF_v3_2 (flat state_dict-order fp32 buffer; layer shapes from
 // /root/reference/model/nerf_raybased.py:500-537) into the per-lane MFMA A-operand weight streams that the chain
 // kernels consume sequentially (layout contract: r2l_common.h).  Runs once per optimizer step (23.7 MB gather).
-#include "r2l_dispatch.h"
-
-__host__ __device__ static inline int64_t pk_off_body_w(int layer) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)layer * (R2L_W * R2L_W + R2L_W);
-}
+#include "r2l_student_net.h"
 
 // forward stream: [head bias group | head trig groups (sample it, axis, g) | head identity groups] then per body layer
 // [bias group | 32 weight groups] in execution order.  Bias group: float4 component 0 of lane (l<32) of tile t holds
@@ -23,7 +19,7 @@ __global__ void r2l_pack_fwd_kernel(const float* __restrict__ params, float* __r
         if (gidx < R2L_FWD_HEAD_GROUPS) {
             const int g1 = (int)gidx - 1;
             if (g1 < 0) {
-                v = (j == 0 && h == 0) ? params[(int64_t)R2L_IN * R2L_W + o] : 0.f;
+                v = (j == 0 && h == 0) ? params[r2l_off_head_b() + o] : 0.f;
             } else if (g1 < R2L_HEAD_TRIG_GROUPS) {
                 const int it = g1 / 15, ax = (g1 % 15) / 5, g = g1 % 5;
                 const int k = ((8 * h + it) * 3 + ax) * 21 + 4 * g + j;
@@ -37,10 +33,10 @@ __global__ void r2l_pack_fwd_kernel(const float* __restrict__ params, float* __r
             const int64_t gb = gidx - R2L_FWD_HEAD_GROUPS;
             const int layer = (int)(gb / R2L_FWD_LAYER_GROUPS), G = (int)(gb % R2L_FWD_LAYER_GROUPS) - 1;
             if (G < 0) {
-                v = (j == 0 && h == 0) ? params[pk_off_body_w(layer) + R2L_W * R2L_W + o] : 0.f;
+                v = (j == 0 && h == 0) ? params[r2l_off_body_b(layer) + o] : 0.f;
             } else {
                 const int in = 32 * (G >> 2) + 8 * (G & 3) + 4 * h + j;
-                v = params[pk_off_body_w(layer) + (int64_t)o * R2L_W + in];
+                v = params[r2l_off_body_w(layer) + (int64_t)o * R2L_W + in];
             }
         }
         out[i] = v;
@@ -60,7 +56,7 @@ __global__ void r2l_pack_bwd_kernel(const float* __restrict__ params, float* __r
         const int slot = (int)(gidx / R2L_LAYER_GROUPS), G = (int)(gidx % R2L_LAYER_GROUPS);
         const int layer = 2 * n_block - 1 - slot;
         const int in = 32 * (G >> 2) + 8 * (G & 3) + 4 * h + j;
-        out[i] = params[pk_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
+        out[i] = params[r2l_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
     }
 }
 
@@ -93,7 +89,7 @@ __global__ void r2l_pack_fwd16_kernel(const float* __restrict__ params, float* _
             const int64_t gb = gidx - R2L_C16_HEAD_GROUPS;
             const int layer = (int)(gb / R2L_C16_LAYER_GROUPS), G = (int)(gb % R2L_C16_LAYER_GROUPS);
             const int in = 16 * G + 4 * kk + e;
-            v = params[pk_off_body_w(layer) + (int64_t)o * R2L_W + in];
+            v = params[r2l_off_body_w(layer) + (int64_t)o * R2L_W + in];
         }
         out[i] = v;
     }
@@ -112,12 +108,12 @@ __global__ void r2l_pack_bwd16_kernel(const float* __restrict__ params, float* _
         const int slot = (int)(gidx / R2L_C16_LAYER_GROUPS), G = (int)(gidx % R2L_C16_LAYER_GROUPS);
         const int layer = 2 * n_block - 1 - slot;
         const int in = 16 * G + 4 * kk + e;
-        out[i] = params[pk_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
+        out[i] = params[r2l_off_body_w(layer) + (int64_t)in * R2L_W + o];  // (W^T)[o][in] = W[in][o]
     }
 }
 
 extern "C" int64_t r2l_param_count(int n_block) {
-    return (int64_t)R2L_IN * R2L_W + R2L_W + (int64_t)2 * n_block * (R2L_W * R2L_W + R2L_W) + 3 * R2L_W + 3;
+    return r2l_off_total(n_block);
 }
 
 // a stream buffer holds every layout (r2l_dispatch.h R2LStreams); every kernel finds its part there

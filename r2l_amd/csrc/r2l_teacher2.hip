@@ -262,20 +262,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     const float act_s = f2_act_scale(a.status);  // the activation scale the stream is packed for
 
     F2Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 4096u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-        P.amax = 0.f;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
 #pragma unroll
     for (int k = 0; k < F2_NBUF - 1; ++k) P.issue();  // stages 0 .. F2_NBUF-2
 #pragma unroll

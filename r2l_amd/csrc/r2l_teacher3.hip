@@ -123,19 +123,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T16Args a) {
     const float* P0 = a.params;
 
     F3Pipe P;
-    {
-        const unsigned long long sa = (unsigned long long)a.stream;
-        P.rs = u32x4{(unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)sa),
-                     (unsigned)__builtin_amdgcn_readfirstlane((int)(unsigned)(sa >> 32)) & 0xffffu, 0xffffffffu, 0x00020000u};
-        P.lds0 = (unsigned)(size_t)(__attribute__((address_space(3))) unsigned char*)&wbuf[0][0];
-        P.voff = (unsigned)lane * 16u;
-        P.wq = (unsigned)wave * 6144u;
-        P.base = &wbuf[0][0];
-        P.lane = lane;
-        P.gb = 0;
-        P.gq = 0;
-        P.gqb = 0;
-    }
+    P.init(a.stream, &wbuf[0][0], lane, wave);
     P.issue(); P.issue(); P.issue(); P.issue(); P.issue();
 #pragma unroll
     for (int k = 0; k < 8; ++k) P.ones.h[k] = (__bf16)((h == 0 && k < 3) ? 1.0f : 0.0f);

@@ -66,7 +66,7 @@ __global__ __launch_bounds__(256) void r2l_adam_pack_kernel(float* __restrict__ 
     if ((int)blockIdx.x < n_body) {
         const int layer = (int)blockIdx.x >> 6, To = ((int)blockIdx.x >> 3) & 7, Ti = (int)blockIdx.x & 7;
         const int r = t >> 3, c4 = (t & 7) * 4;
-        const int64_t at = f2_off_body_w(layer) + (int64_t)(32 * To + r) * R2L_W + 32 * Ti + c4;
+        const int64_t at = r2l_off_body_w(layer) + (int64_t)(32 * To + r) * R2L_W + 32 * Ti + c4;
         f32x4 pv = *reinterpret_cast<const f32x4*>(p + at);
         const f32x4 gv = *reinterpret_cast<const f32x4*>(g + at);
         f32x4 mv = *reinterpret_cast<const f32x4*>(m + at), vv = *reinterpret_cast<const f32x4*>(v + at);
@@ -107,12 +107,12 @@ __global__ __launch_bounds__(256) void r2l_adam_pack_kernel(float* __restrict__ 
     // instead of the device-wide fence a "last workgroup commits" costs — measured: that fence made a 2400-workgroup pack 156 us)
     if ((int)blockIdx.x == n_body && t == 0) f2_commit_scale(status, f2_next_scale(status), false);
     // everything that is not a body weight: [0, head) ++ the body biases ++ the tail
-    const int64_t head = f2_off_body_w(0), n_bias = (int64_t)2 * n_block * R2L_W, tail = 3 * R2L_W + 3;
+    const int64_t head = r2l_off_body_w(0), n_bias = (int64_t)2 * n_block * R2L_W, tail = 3 * R2L_W + 3;
     const int64_t total = head + n_bias + tail;
     for (int64_t j = (int64_t)((int)blockIdx.x - n_body) * 256 + t; j < total; j += (int64_t)AP_REST_WGS * 256) {
         int64_t at = j;
-        if (j >= head + n_bias) at = f2_off_tail_w(n_block) + (j - head - n_bias);
-        else if (j >= head) at = f2_off_body_b((int)((j - head) >> 8)) + ((j - head) & 255);
+        if (j >= head + n_bias) at = r2l_off_tail_w(n_block) + (j - head - n_bias);
+        else if (j >= head) at = r2l_off_body_b((int)((j - head) >> 8)) + ((j - head) & 255);
         float mi = m[at], vi = v[at];
         p[at] = r2l_adam_one(p[at], g[at], mi, vi, k);
         m[at] = mi;

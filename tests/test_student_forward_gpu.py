@@ -271,6 +271,29 @@ def test_pose_paths_vs_fp64(nb, H, W, family, monkeypatch):
     check("pose n_block %d frame %d of %d x %d" % (nb, k, H, W), family, one, Yk, emb_err_of(family), family in FP16X2)
 
 
+@pytest.mark.parametrize("family", list(FAMILIES))
+@pytest.mark.parametrize("H,W", list(POSE_FRAMES))
+def test_pose_mode_equals_rays_mode_on_frame_rays(H, W, family, monkeypatch):
+    """The pose mode of every forward chain forms the ray of a pixel with the pixel_ray of csrc/r2l_pixel_ray.h, the one that
+    r2l_frame_rays writes (csrc/r2l_student_net.h): so a pose-mode launch and a rays-mode launch on the rows render.frame_rays
+    gives for the same poses are the same arithmetic on the same bits, and their rgb is equal bit for bit — no tolerance.
+    7 x 9: two tiles, the second ragged; 33 x 31: more than one workgroup in every family; K frames by the pose table where the
+    family takes one (tiles straddle frames), then the last frame by value."""
+    from r2l_amd import render
+    sd, nb = net(3)
+    hw = H * W
+    use_family(monkeypatch, **FAMILIES[family])
+    o, d, _ = render.frame_rays(poses().cuda(), H, W, POSE_FRAMES[(H, W)])
+    for frames, rows in ((None, slice(0, K_FRAMES * hw)), (K_FRAMES - 1, slice((K_FRAMES - 1) * hw, K_FRAMES * hw))):
+        by_pose = run_pose(dict(sd=sd, nb=nb), family, H, W, frames).clone()
+        c = dict(sd=sd, nb=nb, o=o[rows], d=d[rows], u=None)
+        by_rays = run_rays(c, family, by_pose.shape[0], 0., False)
+        differ = int((by_pose.view(torch.int32) != by_rays.view(torch.int32)).any(1).sum().item())
+        print("POSE == RAYS | %s | %d x %d, %s | %d of %d rays differ" % (family, H, W, "K frames" if frames is None else "one frame",
+                                                                        differ, by_pose.shape[0]))
+        assert differ == 0, (family, H, W, frames, differ)
+
+
 @pytest.mark.parametrize("family", ["main-f32mfma", "coop16", "main"])
 @pytest.mark.parametrize("nb,n", S.FWD_SELF_CHECK_SHAPES)
 def test_bars_see_one_feature_of_one_ray(nb, n, family, monkeypatch):
