@@ -520,6 +520,63 @@ int r2l_occ_compact(const r2l_occ_grid* grid, const float* rays_o, const float* 
 int r2l_occ_scatter(const float* raw_live /*[M,4]*/, const int64_t* idx /*[M]*/, int64_t M, float* raw_out, int64_t R, int S,
                     void* stream);
 
+/* ---- occupancy inside the fused frames call: the live count stays on the device --------------------------------------------------
+ * The chain above reads M on the host to size the point-network launch.  The calls below remove that read, so that empty space
+ * can be skipped where nothing synchronises (r2l_teacher_frames_occ_cfg):
+ *   r2l_occ_index -> r2l_teacher_mlp_live_cfg -> r2l_raw2outputs.
+ * The 40 bytes a sample of copied rows, the raw_live buffer and the scatter launch of the chain above are not needed.
+ *
+ * idx_out[0..M) and *count_out exactly as r2l_occ_compact writes them (ascending, the same bits) and none of its row copies: the
+ * same count / scan / placement kernels with the copies compiled out.  idx_out has capacity R*S; entries >= M are not written.
+ * work: r2l_occ_index_work_bytes(R*S) bytes (-1 for R*S < 0 or >= 2^31), 4-byte aligned.  R == 0 is a successful no-op that sets
+ * *count_out = 0.  Refused: a NULL grid / pointer, R < 0, S < 1, R*S >= 2^31, a grid that r2l_occ_build would refuse. */
+int64_t r2l_occ_index_work_bytes(int64_t n_samples);
+int r2l_occ_index(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, const float* z, int64_t R, int S,
+                  int64_t* idx_out, int64_t* count_out, void* work, void* stream);
+/* live_acc[0] += *count; live_acc[1] += total (device int64[2], caller-zeroed): one thread of one launch, ordered by `stream` behind
+ * the call that wrote *count.  No atomics: calls on one stream add up exactly.  Refused: a NULL pointer, total < 0. */
+int r2l_occ_live_add(const int64_t* count /*device, 1*/, int64_t total, int64_t* live_acc, void* stream);
+
+/* The point network on an index list with a device count.  raw[R,S,4] is zero-filled first (a memset, as r2l_occ_scatter); then for
+ * i < min(*count_dev, R*S) and n = idx[i]:  raw[n] = net(rays_o[n/S] + rays_d[n/S] * z[n], viewdirs[n/S]), the point formed with
+ * product and sum rounded separately.  An idx[i] outside [0, R*S) reads and writes nothing at that number; nothing outside
+ * raw[0 .. R*S*4) is written; a *count_dev above R*S counts as R*S, one below 1 leaves the zero fill alone.  idx has capacity R*S;
+ * entries at or past the count are not read.  No host synchronisation and no atomics beyond what r2l_teacher_mlp_cfg does (the fp16x2
+ * family's range control).  raw[n] has the bits r2l_teacher_mlp_cfg(..., R, S) writes at n, in every kernel family: a point is a
+ * column of its tile and does not depend on its neighbours, so the call equals r2l_occ_compact -> r2l_teacher_mlp_cfg on [M,1] ->
+ * r2l_occ_scatter bit for bit when idx / count_dev come from r2l_occ_index.
+ * Launch: the kernels of r2l_teacher_mlp_cfg in their live instantiation (a template parameter: the plain kernels are compiled from
+ * the code they always had), over a grid sized for the capacity R*S.  Tile lane i takes sample idx[i]; a workgroup (128 lanes)
+ * leaves as a whole, before any LDS staging or barrier, when its first lane is at or past the count — which covers a count of 0 —,
+ * and a partly filled last workgroup clamps its idle lanes to row count - 1.  The fp16x2 family keeps its range control: its live
+ * kernel is followed by the rescale kernel and by the bf16x3 live kernel with run_if = GO, the dispatch of r2l_teacher_mlp_cfg;
+ * cfg is consulted with the capacity (only cfg->precision matters).  The training form (r2l_teacher_mlp_train) has no live variant.
+ * R == 0 is a successful no-op.  Refused before any launch (hipErrorInvalidValue, r2l_last_error names the argument): a NULL
+ * pointer, R < 0, S < 1, R*S >= 2^31, raw not 16-byte aligned, an invalid cfg. */
+int r2l_teacher_mlp_live_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z /*[R,S]*/,
+                             const int64_t* idx /*device, capacity R*S*/, const int64_t* count_dev /*device, 1*/,
+                             const float* wstream, const float* tparams, float* raw /*[R,S,4]*/, int64_t R, int S, void* stream,
+                             const r2l_config* cfg);
+
+/* r2l_teacher_frames_cfg with each of its two r2l_teacher_mlp_cfg launches replaced by r2l_occ_index -> r2l_teacher_mlp_live_cfg on
+ * the pass's grid (grid_fine NULL: grid_coarse serves both passes); every other stage, the draws and the outputs are those of
+ * r2l_teacher_frames_cfg, arguments up to rgb0 included.  Still no allocation and no host synchronisation.  live_acc: NULL, or device
+ * int64[2] that receives += (live samples, all samples) of every pass (r2l_occ_live_add).  work: 16-byte aligned,
+ * r2l_teacher_frames_occ_work_floats(d) floats = r2l_teacher_frames_work_floats(d) + idx (2 floats per sample of the larger pass,
+ * rounded up to 4) + 4 (the count) + r2l_occ_index_work_bytes of that pass in floats (rounded up to 4).  A frame equals the per-pose
+ * render through r2l_occ_compact / r2l_occ_scatter on the same rays and draws bit for bit; against the frame without grids it
+ * differs only on rays with a skipped sample of positive sigma.  r2l_teacher_frames_cfg itself enqueues exactly what it always did
+ * and r2l_teacher_frames_work_floats is unchanged (one body serves both entry points).
+ * Refused in addition to r2l_teacher_frames_cfg's refusals: a NULL grid_coarse, a grid r2l_occ_build would refuse, d->ndc == 1 (the
+ * box is in world space).  The descriptor's reserved stays zero: the grids are arguments. */
+int64_t r2l_teacher_frames_occ_work_floats(const r2l_teacher_frame_desc* d);
+int r2l_teacher_frames_occ_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                               const float* ttab, const float* u_det, const float* wstream_coarse, const float* tparams_coarse,
+                               const float* wstream_fine, const float* tparams_fine, float* rows, float* rgb, float* disp, float* acc,
+                               float* depth, float* rgb0, const r2l_occ_grid* grid_coarse,
+                               const r2l_occ_grid* grid_fine /*NULL: grid_coarse serves both passes*/,
+                               int64_t* live_acc /*device int64[2] or NULL*/, float* work, void* stream, const r2l_config* cfg);
+
 /* ---- test-set metric ------------------------------------------------------------------------------------------------
  * out[0] = SSIM(img1, img2): utils/ssim_torch.py:28-56,86-94 as called at main.py:46,254,334 (11x11 Gaussian sigma 1.5,
  * zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over every pixel and channel), fused into one kernel + a fixed-order

@@ -169,6 +169,12 @@ SIGNATURES = {
     "r2l_occ_compact_work_bytes": (_l, [_l]),
     "r2l_occ_compact": (_i, [_occp] + [_p] * 4 + [_l, _i] + [_p] * 8),
     "r2l_occ_scatter": (_i, [_p, _p, _l, _p, _l, _i, _p]),
+    "r2l_occ_index_work_bytes": (_l, [_l]),
+    "r2l_occ_index": (_i, [_occp] + [_p] * 3 + [_l, _i] + [_p] * 4),
+    "r2l_occ_live_add": (_i, [_p, _l, _p, _p]),
+    "r2l_teacher_mlp_live_cfg": (_i, [_p] * 9 + [_l, _i, _p, _cfgp]),
+    "r2l_teacher_frames_occ_work_floats": (_l, [_descp]),
+    "r2l_teacher_frames_occ_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 12 + [_occp, _occp, _p, _p, _p, _cfgp]),
     "r2l_ssim_partial_count": (_l, [_i, _i, _i]),
     "r2l_ssim": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "r2l_flip_partial_count": (_l, [_i, _i, _i]),

@@ -23,7 +23,7 @@ from .checkpoint import load_weights
 from .driver import _runs, apply_arithmetic, init_distributed, sync
 from .logger import Logger
 from .nerf_raybased import NeRF
-from .options import parse_args, validate_accelerated, validate_occupancy
+from .options import parse_args, validate_accelerated, validate_occ_fused, validate_occupancy
 from .render import get_embedder, get_rays, render, render_frames, run_network
 
 
@@ -98,7 +98,7 @@ def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device
         store = RayStore(cap, device, seed=9973 * rank, logger=logger)
     t0 = time.time()
     filler = TeacherFill(store, args, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                         rand_pose=rand_pose, ndc=ndc)
+                         rand_pose=rand_pose, ndc=ndc, occ_args=args if args.r2l_occ_fused else None)
     prov = filler.provenance()
     while not filler.done:
         filler.fill_group()
@@ -114,6 +114,7 @@ def main(argv=None):
     args = parse_args(argv)
     validate_accelerated(args)
     validate_occupancy(args)
+    validate_occ_fused(args, ("r2l_fused_frames", "r2l_store_save"))
     if args.r2l_occupancy and args.r2l_store_save:
         raise ValueError("--r2l_occupancy: not with --r2l_store_save, which renders through the fused frames call (no host read of "
                          "the live count)")
@@ -143,6 +144,10 @@ def main(argv=None):
     if args.r2l_occupancy:  # both grids once, behind --r2l_precision: every per-pose render below skips the empty samples
         from .occupancy import build_pair, log_live
         occ_pair = kwargs["occupancy"] = build_pair(args, coarse, fine, near, far, logger)
+    occ_fused = None  # --r2l_occ_fused: the same grids inside the fused frames calls below (not needed by a pure store fill,
+    if args.r2l_occ_fused and (args.r2l_fused_frames and (args.test_teacher or not args.r2l_store_save)):  # which builds its own)
+        from .occupancy import FusedOccupancy
+        occ_fused = FusedOccupancy(args, coarse, fine, near, far, logger)
     if args.test_teacher:
         # "Testing teacher..." (create_data.py:723-741): the test views through render_path with render_kwargs_test (perturb =
         # --perturb_test, raw_noise_std = 0), Loss / PSNR logged before any data is generated; frames sharded over the ranks
@@ -153,7 +158,7 @@ def main(argv=None):
         kw_test = dict(kwargs, perturb=args.perturb_test, raw_noise_std=0., near=near, far=far)
         _, misc = render_path(poses[i_split[2]], coarse, None, device, logger, gt_imgs=images[i_split[2]], rank=rank, world=world,
                               teacher=dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kw_test, render_factor=args.render_factor,
-                                           fused=args.r2l_fused_frames),
+                                           fused=args.r2l_fused_frames, occ_fused=occ_fused),
                               lpips_params=load_lpips_weights(args, device, logger),
                               lpips_vgg_params=load_lpips_vgg_weights(args, device, logger))
         logger.info("Teacher test: Loss %.4f PSNR %.4f%s" % (misc["test_loss"].item(), misc["test_psnr"].item(), lpips_field(misc)))
@@ -162,7 +167,9 @@ def main(argv=None):
         # no shard files and no --datadir_kd: the poses go through the online fill (online_kd.TeacherFill: the same RandomState,
         # frame ids and flush keys) into a device-resident store, compact with --r2l_compact_store, and the store is written as
         # one checksummed file — the very rows main.py --r2l_online_kd would have rendered, for main.py --r2l_store_load
-        del coarse, fine, kwargs  # (TeacherFill builds its own pair and releases it after the last group)
+        if occ_fused is not None:  # (the test render's share; the fill logs its own)
+            occ_fused.log(logger)
+        del coarse, fine, kwargs, occ_fused  # (TeacherFill builds its own pair and releases it after the last group)
         return store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device, logger)
 
     datadir_new = args.datadir_kd.split(":")[-1]
@@ -249,7 +256,8 @@ def main(argv=None):
                 with torch.no_grad():
                     parts = [render_frames(c2ws[a:a + n], H, W, focals[a:a + n], near, far, coarse, fine, args.N_samples,
                                            args.N_importance, args.perturb, args.white_bkgd, seed=1000003 * rank,
-                                           frame_id0=ids[a], rows=True, ndc=ndc, ndc_focal=focal)["rows"]  # (a whole frame per pass)
+                                           frame_id0=ids[a], rows=True, ndc=ndc, ndc_focal=focal,
+                                           **(occ_fused.kwargs() if occ_fused is not None else {}))["rows"]  # (a whole frame per pass)
                              for a, n in _runs(ids)]
                 filled = len(group) * H * W
                 free[k].wait()  # the flush that last used this buffer has been written
@@ -275,4 +283,6 @@ def main(argv=None):
         raise errors[0]
     if occ_pair is not None:
         log_live(occ_pair, logger)
+    if occ_fused is not None:
+        occ_fused.log(logger)
     return {"n_rays": n_rays, "datadir": datadir_new, "logger": logger}

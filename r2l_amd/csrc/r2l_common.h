@@ -510,6 +510,8 @@ __device__ __forceinline__ void r2l_no_pack(float& v) { asm volatile("" : "+v"(v
 extern "C" const char* r2l_last_error(void);
 void r2l_set_error(const char* what, hipError_t e);
 void r2l_set_error_msg(const char* msg);
+// r2l_occupancy.hip: what is wrong with an occupancy grid (r2l_occ_build's rule), or nullptr
+const char* r2l_occ_grid_why(const r2l_occ_grid* g, const char* null_msg);
 #define R2L_CHECK(expr)                        \
     do {                                       \
         hipError_t _e = (expr);                \

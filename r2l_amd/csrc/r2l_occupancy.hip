@@ -1,12 +1,15 @@
 // Occupancy grid of the teacher's render: a bit per cell of a box says whether the trained density can be positive there, and
 // the sample points of a launch that fall into an empty cell are dropped before the point network sees them (raw2outputs gives
 // a sample with sigma <= 0 the weight 0 exactly, so a dropped sample whose sigma is not positive changes no bit of a frame).
-// Four stateless calls (include/r2l_hip.h "occupancy grid" pins the arithmetic):
+// Stateless calls (include/r2l_hip.h "occupancy grid" pins the arithmetic):
 //   r2l_occ_build    sigma of (G k)^3 probes through the EXISTING point-network launch (r2l_teacher_mlp_cfg, S = 1), slab by
 //                    slab, a cell's bit = any of its k^3 probes above the threshold, then a box maximum (dilation);
 //   r2l_occ_compact  the live samples of [R,S] in ascending order: their index and their (o, d, viewdirs, z) as S = 1 rows;
-//   r2l_occ_scatter  raw of the live rows back into a zero-filled [R,S,4].
-// No kernel of the point network is touched.  Nothing here is compute-bound: build is the network's time, compact and scatter
+//   r2l_occ_scatter  raw of the live rows back into a zero-filled [R,S,4];
+//   r2l_occ_index    r2l_occ_compact's idx and count without its row copies (the same kernels, a template switch), for the point
+//                    network's live form (r2l_teacher_mlp_live_cfg), which reads the count on the device; r2l_occ_live_add sums
+//                    counts in stream order.
+// No kernel of the point network is touched here.  Nothing here is compute-bound: build is the network's time, compact and scatter
 // move 40 + 8 and 32 bytes per live sample.  Every output position comes from a scan, never from the arrival order of an
 // atomic (there are no atomics in this file): the same arguments give the same bits.
 #include "r2l_common.h"
@@ -145,7 +148,8 @@ struct CompactArgs {
     int64_t* idx;
 };
 
-template <bool EMIT>
+// ROWS: the (o, d, viewdirs, z) row copies of r2l_occ_compact; without them the placement writes idx alone (r2l_occ_index)
+template <bool EMIT, bool ROWS = true>
 __global__ __launch_bounds__(OCC_THREADS) void r2l_occ_compact_kernel(const CompactArgs a) {
     __shared__ unsigned wsum[OCC_THREADS / 64];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
@@ -182,13 +186,15 @@ __global__ __launch_bounds__(OCC_THREADS) void r2l_occ_compact_kernel(const Comp
             if (live) {
                 const int64_t pos = (int64_t)running + before + (unsigned)__popcll(m & ((1ull << lane) - 1ull));
                 a.idx[pos] = n;
+                if constexpr (ROWS) {
 #pragma unroll
-                for (int c = 0; c < 3; ++c) {
-                    a.out_o[pos * 3 + c] = a.o[ray * 3 + c];
-                    a.out_d[pos * 3 + c] = a.d[ray * 3 + c];
-                    a.out_v[pos * 3 + c] = a.v[ray * 3 + c];
+                    for (int c = 0; c < 3; ++c) {
+                        a.out_o[pos * 3 + c] = a.o[ray * 3 + c];
+                        a.out_d[pos * 3 + c] = a.d[ray * 3 + c];
+                        a.out_v[pos * 3 + c] = a.v[ray * 3 + c];
+                    }
+                    a.out_z[pos] = zz;
                 }
-                a.out_z[pos] = zz;
             }
             running += total;
             __syncthreads();
@@ -236,6 +242,14 @@ __global__ __launch_bounds__(OCC_SCAN_THREADS) void r2l_occ_scan_kernel(unsigned
         run += c;
     }
     if (t == 0) *count_out = (int64_t)total;
+}
+
+// live_acc[0] += *count, live_acc[1] += total: one thread, ordered by the stream behind the scan that wrote *count (no atomics)
+__global__ void r2l_occ_live_add_kernel(const int64_t* __restrict__ count, int64_t total, int64_t* __restrict__ live_acc) {
+    if (blockIdx.x == 0 && threadIdx.x == 0) {
+        live_acc[0] += *count;
+        live_acc[1] += total;
+    }
 }
 
 // ---- scatter ----------------------------------------------------------------------------------------------------------------
@@ -416,6 +430,66 @@ extern "C" int r2l_occ_compact(const r2l_occ_grid* grid, const float* rays_o, co
     R2L_CHECK(hipGetLastError());
     return 0;
 }
+
+extern "C" int64_t r2l_occ_index_work_bytes(int64_t n) {
+    if (n < 0 || n >= ((int64_t)1 << 31)) {
+        r2l_set_error_msg("r2l_occ_index_work_bytes: need 0 <= R*S < 2^31");
+        return -1;
+    }
+    return r2l_occ_compact_work_bytes(n);  // (the same per-workgroup counts)
+}
+
+// r2l_occ_compact without its row copies: the same count / scan / placement launches, idx and the count bit for bit
+extern "C" int r2l_occ_index(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, const float* z, int64_t R, int S,
+                             int64_t* idx_out, int64_t* count_out, void* work, void* stream) {
+    if (const char* why = occ_grid_check(grid, "r2l_occ_index: grid is NULL")) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    R2L_REQUIRE(R >= 0, "r2l_occ_index: R is negative");
+    R2L_REQUIRE(S >= 1, "r2l_occ_index: S: need S >= 1");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_occ_index: R*S: need R*S < 2^31");
+    R2L_REQUIRE(count_out != nullptr, "r2l_occ_index: count_out is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    if (R == 0) {
+        R2L_CHECK(hipMemsetAsync(count_out, 0, sizeof(int64_t), s));
+        return 0;
+    }
+    R2L_REQUIRE(rays_o != nullptr, "r2l_occ_index: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_occ_index: rays_d is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_occ_index: z is NULL");
+    R2L_REQUIRE(idx_out != nullptr, "r2l_occ_index: idx_out is NULL");
+    R2L_REQUIRE(work != nullptr, "r2l_occ_index: work is NULL");
+    R2L_REQUIRE(((uintptr_t)work & 3) == 0, "r2l_occ_index: work is not 4-byte aligned");
+    CompactArgs a{};
+    a.g = occ_dev(grid);
+    a.o = rays_o; a.d = rays_d; a.z = z;
+    a.n = R * (int64_t)S;
+    a.S = S;
+    a.blk = (unsigned*)work;
+    a.idx = idx_out;
+    const int64_t nb = (a.n + OCC_CHUNK - 1) / OCC_CHUNK;  // <= 2^20
+    hipLaunchKernelGGL((r2l_occ_compact_kernel<false, false>), dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, a);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(r2l_occ_scan_kernel, dim3(1), dim3(OCC_SCAN_THREADS), 0, s, a.blk, nb, (nb + OCC_SCAN_THREADS - 1) / OCC_SCAN_THREADS,
+                       count_out);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((r2l_occ_compact_kernel<true, false>), dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_occ_live_add(const int64_t* count, int64_t total, int64_t* live_acc, void* stream) {
+    R2L_REQUIRE(count != nullptr, "r2l_occ_live_add: count is NULL");
+    R2L_REQUIRE(total >= 0, "r2l_occ_live_add: total is negative");
+    R2L_REQUIRE(live_acc != nullptr, "r2l_occ_live_add: live_acc is NULL");
+    hipLaunchKernelGGL(r2l_occ_live_add_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, count, total, live_acc);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// what r2l_teacher_frames_occ_cfg asks of a grid before it enqueues anything
+const char* r2l_occ_grid_why(const r2l_occ_grid* g, const char* null_msg) { return occ_grid_check(g, null_msg); }
 
 extern "C" int r2l_occ_scatter(const float* raw_live, const int64_t* idx, int64_t M, float* raw_out, int64_t R, int S, void* stream) {
     R2L_REQUIRE(R >= 0, "r2l_occ_scatter: R is negative");

@@ -226,6 +226,8 @@ __device__ __forceinline__ void t2_vstage(f32x16 (&acc)[R2L_NT], F2Pipe& P, F2Sp
     }
 }
 
+// LIVE: the launch form on an index list with a device count (r2l_teacher_net.h "live form")
+template <bool LIVE>
 __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[F2_NBUF][F2_STAGE_BYTES];
     // weights of the two VALU heads (alpha_linear [256], rgb_linear [3][128]): staged in LDS once per workgroup.  Read from global
@@ -237,6 +239,11 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     // loads the pipeline has in flight for the stages behind the tile (1 - 2 us per 60 us tile: most of what the heads "cost")
     __shared__ __attribute__((aligned(16))) float head_b[4];  // rgb_linear.bias[0..2], alpha_linear.bias
     if (__builtin_nontemporal_load(a.status) != 0u) return;
+    int64_t n_pts = a.n_pts;
+    if constexpr (LIVE) {  // (before the cooperative staging below: the whole workgroup leaves, or none of it)
+        n_pts = t_live_count(a.count_dev, a.n_pts);
+        if (t_live_workgroup_idle(n_pts)) return;
+    }
     const TOff off = t_offsets();
     for (int i = threadIdx.x; i < T_W; i += 256) { head_a[0][i] = 0.f; head_a[1][i] = a.params[off.alpha_w + i]; }
     for (int i = threadIdx.x; i < 3 * T_VIEWS; i += 256) head_rgb[i] = a.params[off.rgb_w + i];  // (published by the prologue's barrier)
@@ -245,8 +252,10 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     const int64_t pt = tile * R2L_TILE_RAYS + (lane & 31);
-    const bool valid = pt < a.n_pts;
-    const int64_t pc = valid ? pt : a.n_pts - 1;
+    bool valid = pt < n_pts;
+    int64_t pc = valid ? pt : n_pts - 1;
+    int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -386,7 +395,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     alpha = (alpha + __shfl_xor(alpha, 32)) * act_s + head_b[3];  // (the chain holds activations / act_s: exact)
     if (valid && h == 0) {
         const f32x4 o4 = {acc3[0], acc3[1], acc3[2], alpha};
-        *reinterpret_cast<f32x4*>(a.raw + pt * 4) = o4;
+        *reinterpret_cast<f32x4*>(a.raw + (LIVE ? (int64_t)live_n : pt) * 4) = o4;
     }
 }
 
@@ -408,13 +417,16 @@ int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream)
 }
 
 int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
-                     const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream) {
+                     const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
+                     const int64_t* idx, const int64_t* count_dev) {
     T16Args a{};
+    a.idx = idx; a.count_dev = count_dev;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
     // the status word lives in the caller's stream buffer (library-private contents): written through, hence the cast
     a.status = reinterpret_cast<unsigned*>(const_cast<float*>(wstream2) + t2_status_offset());
-    hipLaunchKernelGGL(r2l_teacher2_kernel, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
+    if (idx != nullptr) hipLaunchKernelGGL(r2l_teacher2_kernel<true>, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(r2l_teacher2_kernel<false>, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());
     hipLaunchKernelGGL(r2l_teacher2_rescale_kernel, dim3(512), dim3(256), 0, stream, tparams,
                        reinterpret_cast<unsigned short*>(const_cast<float*>(wstream2)), a.status);

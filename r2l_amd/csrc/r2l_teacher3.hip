@@ -99,16 +99,25 @@ struct T3Select {
     }
 };
 
+// LIVE: the launch form on an index list with a device count (r2l_teacher_net.h "live form")
+template <bool LIVE>
 __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T16Args a) {
     __shared__ __attribute__((aligned(16))) unsigned char wbuf[F3_NBUF][F3_STAGE_BYTES];
     if (a.run_if != nullptr && __builtin_nontemporal_load(a.run_if) == 0u) return;
+    int64_t n_pts = a.n_pts;
+    if constexpr (LIVE) {
+        n_pts = t_live_count(a.count_dev, a.n_pts);
+        if (t_live_workgroup_idle(n_pts)) return;
+    }
     const TOff off = t_offsets();
     const int lane = threadIdx.x & 63, h = lane >> 5;
     const int wave = __builtin_amdgcn_readfirstlane((int)(threadIdx.x >> 6));
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
     const int64_t pt = tile * R2L_TILE_RAYS + (lane & 31);
-    const bool valid = pt < a.n_pts;
-    const int64_t pc = valid ? pt : a.n_pts - 1;
+    bool valid = pt < n_pts;
+    int64_t pc = valid ? pt : n_pts - 1;
+    int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -227,7 +236,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T16Args a) {
     for (int c = 0; c < 3; ++c) acc3[c] = acc3[c] + __shfl_xor(acc3[c], 32) + P0[off.rgb_b + c];
     if (valid && h == 0) {
         const f32x4 o4 = {acc3[0], acc3[1], acc3[2], alpha};
-        *reinterpret_cast<f32x4*>(a.raw + pt * 4) = o4;
+        *reinterpret_cast<f32x4*>(a.raw + (LIVE ? (int64_t)live_n : pt) * 4) = o4;
     }
 }
 
@@ -245,12 +254,14 @@ int r2l_teacher3_pack(const float* tparams, float* wstream3, hipStream_t stream)
 
 int r2l_teacher3_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream3, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const unsigned* run_if) {
+                     const unsigned* run_if, const int64_t* idx, const int64_t* count_dev) {
     T16Args a{};
     a.run_if = run_if;
+    a.idx = idx; a.count_dev = count_dev;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream3); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
-    hipLaunchKernelGGL(r2l_teacher3_kernel, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
+    if (idx != nullptr) hipLaunchKernelGGL(r2l_teacher3_kernel<true>, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
+    else hipLaunchKernelGGL(r2l_teacher3_kernel<false>, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

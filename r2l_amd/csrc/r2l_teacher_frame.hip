@@ -9,6 +9,8 @@
 //   r2l_teacher_frames_cfg: rays -> stratified z -> coarse MLP -> raw2outputs -> sample_pdf + sort -> fine MLP -> raw2outputs,
 //                           the EXISTING kernels of those stages enqueued back to back on the caller's stream through one work
 //                           buffer the caller sized once: no allocation, no host synchronisation
+//   r2l_teacher_frames_occ_cfg: the same body with each point-network launch replaced by r2l_occ_index -> r2l_teacher_mlp_live_cfg
+//                           (occupancy grids, the live count read on the device): still no host synchronisation
 //   r2l_pixel_batch       : the batching mode of teacher training (main.py:1137-1162, 1199-1210) without its bank of rays:
 //                           draw t takes pixel pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img*H*W training pixels
 //                           (csrc/r2l_perm.h, the ray store's sampler), and its ray is computed on the spot
@@ -21,6 +23,7 @@
 #include "r2l_perm.h"
 #include "r2l_pixel_ray.h"
 #include <math.h>
+#include <stdio.h>
 
 namespace {
 
@@ -310,6 +313,34 @@ FrameWork frame_work(const r2l_teacher_frame_desc* d) {
     return w;
 }
 
+// What the occupancy form adds behind the plain work buffer: idx (int64 per sample of the larger pass), the count, the index work
+struct OccWork {
+    int64_t idx, count, iwork, total;
+};
+OccWork occ_work(const r2l_teacher_frame_desc* d, const FrameWork& w) {
+    const int64_t hw = (int64_t)d->H * d->W;
+    const int64_t cr = d->chunk_rays > 0 && d->chunk_rays < hw ? d->chunk_rays : hw;
+    const int64_t n = cr * ((int64_t)d->N_samples + d->N_importance);  // samples of the larger pass
+    OccWork o{};
+    o.idx = w.total;
+    o.count = o.idx + r4(2 * n);
+    o.iwork = o.count + 4;
+    const int64_t ib = n < ((int64_t)1 << 31) ? r2l_occ_index_work_bytes(n) : 0;  // (a larger pass is refused by the index call)
+    o.total = o.iwork + r4((ib + 3) / 4);
+    return o;
+}
+
+// The grids of the occupancy form, or none: the ONE body below serves both entry points
+struct FrameOcc {
+    const r2l_occ_grid *coarse, *fine;
+    int64_t* live_acc;
+};
+
+int frames_body(const char* who, const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d, const float* ttab,
+                const float* u_det, const float* wstream_coarse, const float* tparams_coarse, const float* wstream_fine,
+                const float* tparams_fine, float* rows, float* rgb, float* disp, float* acc, float* depth, float* rgb0, float* work,
+                void* stream, const r2l_config* cfg, const FrameOcc* occ);
+
 }  // namespace
 
 extern "C" int r2l_draw_uniform(float* out, int64_t n, uint64_t seed, uint64_t stream_id, void* stream) {
@@ -435,26 +466,94 @@ extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_d
                                       const float* ttab, const float* u_det, const float* wstream_coarse, const float* tparams_coarse,
                                       const float* wstream_fine, const float* tparams_fine, float* rows, float* rgb, float* disp,
                                       float* acc, float* depth, float* rgb0, float* work, void* stream, const r2l_config* cfg) {
+    return frames_body("r2l_teacher_frames_cfg", c2w_dev, focal_dev, K, d, ttab, u_det, wstream_coarse, tparams_coarse, wstream_fine,
+                       tparams_fine, rows, rgb, disp, acc, depth, rgb0, work, stream, cfg, nullptr);
+}
+
+extern "C" int64_t r2l_teacher_frames_occ_work_floats(const r2l_teacher_frame_desc* d) {
+    if (const char* why = desc_check(d)) {
+        r2l_set_error_msg(why);
+        return -1;
+    }
+    return occ_work(d, frame_work(d)).total;
+}
+
+extern "C" int r2l_teacher_frames_occ_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                                          const float* ttab, const float* u_det, const float* wstream_coarse,
+                                          const float* tparams_coarse, const float* wstream_fine, const float* tparams_fine, float* rows,
+                                          float* rgb, float* disp, float* acc, float* depth, float* rgb0,
+                                          const r2l_occ_grid* grid_coarse, const r2l_occ_grid* grid_fine, int64_t* live_acc, float* work,
+                                          void* stream, const r2l_config* cfg) {
+    if (const char* why = desc_check(d)) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    R2L_REQUIRE(d->ndc == 0, "r2l_teacher_frames_occ_cfg: r2l_teacher_frame_desc.ndc must be 0 (the box of an occupancy grid is in world space)");
+    if (const char* why = r2l_occ_grid_why(grid_coarse, "r2l_teacher_frames_occ_cfg: grid_coarse is NULL")) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    if (grid_fine != nullptr)
+        if (const char* why = r2l_occ_grid_why(grid_fine, "r2l_teacher_frames_occ_cfg: grid_fine is NULL")) {
+            r2l_set_error_msg(why);
+            return (int)hipErrorInvalidValue;
+        }
+    const FrameOcc occ{grid_coarse, grid_fine ? grid_fine : grid_coarse, live_acc};
+    return frames_body("r2l_teacher_frames_occ_cfg", c2w_dev, focal_dev, K, d, ttab, u_det, wstream_coarse, tparams_coarse, wstream_fine,
+                       tparams_fine, rows, rgb, disp, acc, depth, rgb0, work, stream, cfg, &occ);
+}
+
+namespace {
+
+// a refusal of the body, named after the entry point that was called
+#define FRAMES_REQUIRE(cond, msg)                                    \
+    do {                                                             \
+        if (!(cond)) {                                               \
+            static thread_local char buf_[256];                      \
+            snprintf(buf_, sizeof buf_, "%s: %s", who, msg);         \
+            r2l_set_error_msg(buf_);                                 \
+            return (int)hipErrorInvalidValue;                        \
+        }                                                            \
+    } while (0)
+
+// The point network of one pass: the plain launch, or (occupancy form) index -> [live_acc] -> the live launch
+int frames_mlp(const float* o, const float* dd, const float* v, const float* z, const float* wstream, const float* tparams, float* raw,
+               int64_t cr, int S, void* stream, const r2l_config* cfg, const r2l_occ_grid* grid, const FrameOcc* occ, float* work,
+               const OccWork& ow) {
+    if (occ == nullptr) return r2l_teacher_mlp_cfg(o, dd, v, z, wstream, tparams, raw, cr, S, stream, cfg);
+    int64_t* const idx = reinterpret_cast<int64_t*>(work + ow.idx);
+    int64_t* const count = reinterpret_cast<int64_t*>(work + ow.count);
+    int rc;
+    if ((rc = r2l_occ_index(grid, o, dd, z, cr, S, idx, count, work + ow.iwork, stream))) return rc;
+    if (occ->live_acc != nullptr && (rc = r2l_occ_live_add(count, cr * (int64_t)S, occ->live_acc, stream))) return rc;
+    return r2l_teacher_mlp_live_cfg(o, dd, v, z, idx, count, wstream, tparams, raw, cr, S, stream, cfg);
+}
+
+int frames_body(const char* who, const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d, const float* ttab,
+                const float* u_det, const float* wstream_coarse, const float* tparams_coarse, const float* wstream_fine,
+                const float* tparams_fine, float* rows, float* rgb, float* disp, float* acc, float* depth, float* rgb0, float* work,
+                void* stream, const r2l_config* cfg, const FrameOcc* occ) {
     if (const char* why = desc_check(d)) {
         r2l_set_error_msg(why);
         return (int)hipErrorInvalidValue;
     }
     R2L_CFG_ENTER(cfg);
-    R2L_REQUIRE(K >= 0, "r2l_teacher_frames_cfg: K is negative");
-    R2L_REQUIRE((wstream_fine == nullptr) == (tparams_fine == nullptr),
-                "r2l_teacher_frames_cfg: wstream_fine / tparams_fine: both or neither (NULL pair: the coarse net serves both passes)");
-    R2L_REQUIRE(d->perturb != 0 || d->N_importance == 0 || u_det != nullptr,
-                "r2l_teacher_frames_cfg: u_det is NULL (needed with perturb == 0 and N_importance > 0)");
-    R2L_REQUIRE(focal_dev != nullptr || d->focal > 0.f, "r2l_teacher_frames_cfg: need r2l_teacher_frame_desc.focal > 0 (or focal_dev)");
+    FRAMES_REQUIRE(K >= 0, "K is negative");
+    FRAMES_REQUIRE((wstream_fine == nullptr) == (tparams_fine == nullptr),
+                "wstream_fine / tparams_fine: both or neither (NULL pair: the coarse net serves both passes)");
+    FRAMES_REQUIRE(d->perturb != 0 || d->N_importance == 0 || u_det != nullptr,
+                "u_det is NULL (needed with perturb == 0 and N_importance > 0)");
+    FRAMES_REQUIRE(focal_dev != nullptr || d->focal > 0.f, "need r2l_teacher_frame_desc.focal > 0 (or focal_dev)");
     if (K == 0) return 0;
-    R2L_REQUIRE(c2w_dev && ttab && wstream_coarse && tparams_coarse && work,
-                "r2l_teacher_frames_cfg: a required pointer is NULL (c2w_dev, ttab, wstream_coarse, tparams_coarse, work)");
-    R2L_REQUIRE(((uintptr_t)work & 15) == 0, "r2l_teacher_frames_cfg: work must be 16-byte aligned");
+    FRAMES_REQUIRE(c2w_dev && ttab && wstream_coarse && tparams_coarse && work,
+                "a required pointer is NULL (c2w_dev, ttab, wstream_coarse, tparams_coarse, work)");
+    FRAMES_REQUIRE(((uintptr_t)work & 15) == 0, "work must be 16-byte aligned");
     const hipStream_t st = (hipStream_t)stream;
     const int S = d->N_samples, NI = d->N_importance, T = S + NI;
     const int64_t hw = (int64_t)d->H * d->W;
     const int64_t cr_max = d->chunk_rays > 0 && d->chunk_rays < hw ? d->chunk_rays : hw;
     const FrameWork w = frame_work(d);
+    const OccWork ow = occ_work(d, w);  // (read by the occupancy form only)
     float* const nf = work + w.nearfar;
     float *const o = work + w.o, *const dd = work + w.d, *const v = work + w.v, *const z = work + w.z, *const raw = work + w.raw;
     const float* wfine = wstream_fine ? wstream_fine : wstream_coarse;
@@ -479,7 +578,9 @@ extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_d
                 if ((rc = launch_draw(t_rand, cr * S, r0 * S, d->seed, 2 * fid, st))) return rc;
             }
             if ((rc = r2l_stratified_z(nf, nf + 1, 0, ttab, t_rand, z, cr, S, stream))) return rc;
-            if ((rc = r2l_teacher_mlp_cfg(o, dd, v, z, wstream_coarse, tparams_coarse, raw, cr, S, stream, cfg))) return rc;
+            if ((rc = frames_mlp(o, dd, v, z, wstream_coarse, tparams_coarse, raw, cr, S, stream, cfg, occ ? occ->coarse : nullptr, occ, work,
+                                 ow)))
+                return rc;
             if (NI == 0) {
                 if ((rc = r2l_raw2outputs(raw, z, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, S, stream)))
                     return rc;
@@ -497,7 +598,9 @@ extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_d
                 if ((rc = r2l_sample_pdf_sort(z, work + w.wts, u, d->perturb ? NI : 0, work + w.zs, work + w.zall, nullptr, cr, S, NI,
                                               stream)))
                     return rc;
-                if ((rc = r2l_teacher_mlp_cfg(o, dd, v, work + w.zall, wfine, pfine, raw, cr, T, stream, cfg))) return rc;
+                if ((rc = frames_mlp(o, dd, v, work + w.zall, wfine, pfine, raw, cr, T, stream, cfg, occ ? occ->fine : nullptr, occ, work,
+                                     ow)))
+                    return rc;
                 if ((rc = r2l_raw2outputs(raw, work + w.zall, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, T,
                                           stream)))
                     return rc;
@@ -510,3 +613,5 @@ extern "C" int r2l_teacher_frames_cfg(const float* c2w_dev, const float* focal_d
     }
     return 0;
 }
+
+}  // namespace

@@ -115,6 +115,8 @@ struct TeacherArgs {
     int64_t n_pts;          // R*S
     int S;
     float* stash;           // training only (r2l_teacher_mlp_train): the layer outputs of every point (r2l_teacher_net.h)
+    const int64_t* idx;        // live form only (r2l_teacher_net.h): the sample of every tile lane, capacity n_pts
+    const int64_t* count_dev;  // live form only: how many entries of idx count (device, 1)
 };
 
 // one wave's NT 32-feature tiles of a layer output (accumulator layout: point = lane & 31, feature 32T + 8q + 4h + j)
@@ -177,15 +179,24 @@ __device__ __forceinline__ void t_pe_gemm(f32x16 (&acc)[R2L_NT], const float (&p
 }
 
 // STASH: the same chain (bit-identical raw), plus every layer output written to a.stash for the backward pass
-template <bool STASH>
+// LIVE: the launch form on an index list with a device count (r2l_teacher_net.h "live form"; never with STASH)
+template <bool STASH, bool LIVE = false>
 __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherArgs a) {
+    static_assert(!(STASH && LIVE), "the training form has no live variant");
+    int64_t n_pts = a.n_pts;
+    if constexpr (LIVE) {
+        n_pts = t_live_count(a.count_dev, a.n_pts);
+        if (t_live_workgroup_idle(n_pts)) return;
+    }
     const TOff off = t_offsets();
     const int wave = threadIdx.x >> 6, lane = threadIdx.x & 63, h = lane >> 5;
     const int64_t tile = (int64_t)blockIdx.x * 4 + wave;
-    if (tile * R2L_TILE_RAYS >= a.n_pts) return;
+    if (tile * R2L_TILE_RAYS >= n_pts) return;
     const int64_t pt = tile * R2L_TILE_RAYS + (lane & 31);
-    const bool valid = pt < a.n_pts;
-    const int64_t pc = valid ? pt : a.n_pts - 1;
+    bool valid = pt < n_pts;
+    int64_t pc = valid ? pt : n_pts - 1;
+    int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -310,7 +321,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
     for (int c = 0; c < 3; ++c) acc3[c] = acc3[c] + __shfl_xor(acc3[c], 32) + P[off.rgb_b + c];
     if (valid && h == 0) {
         const f32x4 o4 = {acc3[0], acc3[1], acc3[2], alpha};
-        *reinterpret_cast<f32x4*>(a.raw + pt * 4) = o4;
+        *reinterpret_cast<f32x4*>(a.raw + (LIVE ? (int64_t)live_n : pt) * 4) = o4;
     }
 }
 
@@ -367,6 +378,46 @@ extern "C" int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, con
     if (arith == R2L_ARITH_BF16X3)  // R2L_NO_FWD2=1: fp32-exact products on the bf16 matrix pipe (R2L_NO_FWD3=1: fp32 MFMA)
         return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, a.n_pts, S, (hipStream_t)stream, nullptr);
     hipLaunchKernelGGL(r2l_teacher_mlp_kernel<false>, dim3(t_workgroups(a.n_pts)), dim3(256), 0, (hipStream_t)stream, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The point network on an index list with a device count (include/r2l_hip.h): the dispatch of r2l_teacher_mlp_cfg with every
+// kernel in its live form, behind a zero fill of raw.  Nothing here reads the count on the host.
+extern "C" int r2l_teacher_mlp_live_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                        const int64_t* idx, const int64_t* count_dev, const float* wstream, const float* params,
+                                        float* raw, int64_t R, int S, void* stream, const r2l_config* cfg) {
+    R2L_CFG_ENTER(cfg);
+    R2L_REQUIRE(R >= 0, "r2l_teacher_mlp_live_cfg: R is negative");
+    R2L_REQUIRE(S >= 1, "r2l_teacher_mlp_live_cfg: S: need S >= 1");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_teacher_mlp_live_cfg: R*S: need R*S < 2^31");
+    if (R == 0) return 0;
+    R2L_REQUIRE(rays_o != nullptr, "r2l_teacher_mlp_live_cfg: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_teacher_mlp_live_cfg: rays_d is NULL");
+    R2L_REQUIRE(viewdirs != nullptr, "r2l_teacher_mlp_live_cfg: viewdirs is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_teacher_mlp_live_cfg: z is NULL");
+    R2L_REQUIRE(idx != nullptr, "r2l_teacher_mlp_live_cfg: idx is NULL");
+    R2L_REQUIRE(count_dev != nullptr, "r2l_teacher_mlp_live_cfg: count_dev is NULL");
+    R2L_REQUIRE(wstream != nullptr, "r2l_teacher_mlp_live_cfg: wstream is NULL");
+    R2L_REQUIRE(params != nullptr, "r2l_teacher_mlp_live_cfg: tparams is NULL");
+    R2L_REQUIRE(raw != nullptr, "r2l_teacher_mlp_live_cfg: raw is NULL");
+    R2L_REQUIRE(((uintptr_t)raw & 15) == 0, "r2l_teacher_mlp_live_cfg: raw is not 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t cap = R * (int64_t)S;
+    R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)cap * 4 * sizeof(float), st));  // (sigma = +0 -> alpha = 0, as r2l_occ_scatter)
+    const int arith = r2l_plan(cfg, cap, 0, false, false).arith_fwd;  // the capacity, as r2l_teacher_mlp_cfg asks for n_pts
+    if (arith == R2L_ARITH_FP16X2) {
+        const int rc = r2l_teacher2_mlp(rays_o, rays_d, viewdirs, z, t_w2(wstream), params, raw, cap, S, st, idx, count_dev);
+        if (rc) return rc;
+        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, cap, S, st,
+                                r2l_teacher2_status(t_w2(wstream)) + F2S_GO, idx, count_dev);
+    }
+    if (arith == R2L_ARITH_BF16X3)
+        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, cap, S, st, nullptr, idx, count_dev);
+    TeacherArgs a{};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
+    a.raw = raw; a.n_pts = cap; a.S = S; a.idx = idx; a.count_dev = count_dev;
+    hipLaunchKernelGGL((r2l_teacher_mlp_kernel<false, true>), dim3(t_workgroups(cap)), dim3(256), 0, st, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

@@ -19,7 +19,7 @@ from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import (parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_image_store,
-                      validate_occupancy, validate_store_file)
+                      validate_occ_fused, validate_occupancy, validate_store_file)
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -597,7 +597,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
                 with torch.no_grad():  # (draws of --perturb_test > 0: stream pair of frame i = its pose number, whatever the ranks)
                     outs = [render_frames(c2ws[k:k + n], H, W, focal, kw["near"], kw["far"], kw["network_fn"], kw.get("network_fine"),
                                           kw["N_samples"], kw.get("N_importance", 0), kw.get("perturb", 0.), kw.get("white_bkgd", False),
-                                          seed=int(teacher.get("seed", 0)), frame_id0=idx[k], ndc=bool(kw.get("ndc")))["rgb"]
+                                          seed=int(teacher.get("seed", 0)), frame_id0=idx[k], ndc=bool(kw.get("ndc")),
+                                          **(teacher["occ_fused"].kwargs() if teacher.get("occ_fused") is not None else {}))["rgb"]
                             for k, n in _runs(idx)]
                 frames = (outs[0] if len(outs) == 1 else torch.cat(outs, 0)).view(len(idx), H, W, 3)
                 e1.record()
@@ -750,7 +751,7 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         else:
             loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
         filler = TeacherFill(loader, targs, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                             rand_pose=scene.rand_pose, ndc=scene.ndc)
+                             rand_pose=scene.rand_pose, ndc=scene.ndc, occ_args=args if args.r2l_occ_fused else None)
         # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
         # number, so these are the same rows bit for bit
         n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
@@ -852,6 +853,13 @@ def main(argv=None):
                                   "the teacher runs through utils/train_nerf.py")
     if is_teacher:
         validate_occupancy(args, raw_noise_std=0.)  # (the teacher's test render runs without noise; student runs ignore the switch)
+        validate_occ_fused(args, ("r2l_fused_frames",), raw_noise_std=0.)
+    elif args.r2l_occ_fused:  # the teacher of the online fill: its config says whether it has view directions (its raw_noise_std
+        targs_ = None         # is 0, or parse_teacher_config refuses it)
+        if args.r2l_online_kd and args.r2l_teacher_config:
+            from .options import parse_teacher_config
+            targs_ = parse_teacher_config(args.r2l_teacher_config)
+        validate_occ_fused(args, ("r2l_online_kd",), raw_noise_std=0., use_viewdirs=targs_.use_viewdirs if targs_ is not None else True)
     rank, world, device = init_distributed()
     if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
         raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
@@ -891,6 +899,9 @@ def main(argv=None):
         if args.r2l_occupancy:  # both grids once, behind --r2l_precision
             from .occupancy import build_pair
             kwargs_test["occupancy"] = build_pair(args, model, kwargs_test["network_fine"], near, far, logger)
+        if args.r2l_occ_fused:  # the same grids inside the fused frames calls of render_path
+            from .occupancy import FusedOccupancy
+            teacher["occ_fused"] = FusedOccupancy(args, model, kwargs_test["network_fine"], near, far, logger)
     else:
         model, embedder, history, ckpt = create_r2l(args, device, logger)
         point_sampler = PointSampler(H, W, focal, args.n_sample_per_ray, near, far, device=device)
@@ -930,6 +941,8 @@ def main(argv=None):
         if teacher is not None and "occupancy" in teacher["render_kwargs"]:
             from .occupancy import log_live
             log_live(teacher["render_kwargs"]["occupancy"], logger)
+        if teacher is not None and teacher.get("occ_fused") is not None:
+            teacher["occ_fused"].log(logger)
         # (the reference writes the video of whichever frames it rendered — test views too, main.py:1096-1097)
         video_path = save_video(rgbs, logger, expid, iter_, args.video_tag, rank, world, device)
         if "errors" in misc:  # (main.py:1098-1102: the |rgb - gt| frames as a second video)

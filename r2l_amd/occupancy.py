@@ -9,6 +9,11 @@ the live samples (cell bit set, or outside the box) through the point network:
     compact (r2l_occ_compact) -> read M (8 bytes, the one synchronisation) -> TeacherEngine.mlp on [M] rows with S = 1
     -> scatter (r2l_occ_scatter) into a zero-filled raw[R,S,4] -> the unchanged raw2outputs / sample_pdf_sort.
 
+Inside the fused frames call (render_frames(occupancy=pair), --r2l_occ_fused) the count never leaves the device:
+
+    index (r2l_occ_index: compact's idx and count, no row copies) -> TeacherEngine.mlp_live on the index list (the kernels' live
+    form reads the count itself and writes raw in place) -> the unchanged raw2outputs / sample_pdf_sort.
+
 build_spec / compact_spec / scatter_spec restate the three library calls in numpy: they are what CPU tensors run, and what
 the tests hold the kernels to bit for bit.
 """
@@ -259,6 +264,23 @@ class OccupancyGrid:
         M = int(b["count"].item())  # the 8-byte device-to-host copy: the one synchronisation of the masked query
         return M, b["idx"][:M], b["o"][:M], b["d"][:M], b["v"][:M], b["z"][:M]
 
+    def index(self, rays_o, rays_d, z, live_acc=None):
+        """(idx, count): the live samples' numbers, ascending, in an int64 tensor of capacity R*S (entries at and past the count are
+        not written) and their count as an int64[1] device tensor — r2l_occ_compact's idx and count without its row copies
+        (r2l_occ_index), and WITHOUT a read on the host: what TeacherEngine.mlp_live takes.  live_acc: None or an int64[2] device
+        tensor that receives += (count, R*S) in stream order (r2l_occ_live_add).  The returned tensors are views of buffers the
+        grid re-uses on the next call."""
+        R, S = z.shape
+        b = self._buffers(max(R * S, 1), z.device)
+        lib = _lib.load()
+        with torch.cuda.device(z.device):
+            _lib.check(lib.r2l_occ_index(ctypes.byref(self.desc()), _ptr(rays_o.contiguous()), _ptr(rays_d.contiguous()),
+                                         _ptr(z.contiguous()), R, S, _ptr(b["idx"]), _ptr(b["count"]), _ptr(b["work"]), _stream()),
+                       "r2l_occ_index")
+            if live_acc is not None:
+                _lib.check(lib.r2l_occ_live_add(_ptr(b["count"]), R * S, _ptr(live_acc), _stream()), "r2l_occ_live_add")
+        return b["idx"][:max(R * S, 1)], b["count"]
+
     @staticmethod
     def scatter(raw_live, idx, R, S):
         """raw[R,S,4] on the GPU: zeros, raw[idx[i]] = raw_live[i] (r2l_occ_scatter)."""
@@ -345,7 +367,7 @@ def miss_report(ray_batch, network_fn, network_fine, occupancy, N_samples, N_imp
 
 
 # ---------------------------------------------------------------------------------------------------------------
-# drivers (--r2l_occupancy)
+# drivers (--r2l_occupancy, --r2l_occ_fused)
 # ---------------------------------------------------------------------------------------------------------------
 def box_half_side(args, near, far):
     """--r2l_occ_bound, or 0.625 (far - near): 2.5 for the Blender scenes (near 2, far 6), whose objects sit inside [-1.5, 1.5]^3."""
@@ -366,6 +388,29 @@ def build_pair(args, coarse, fine, near, far, logger):
                     "%.1f%% of the cells occupied" % (name, g.G, b, g.k, g.dilate, g.build_seconds, 100. * g.occupied_share()))
         grids.append(g)
     return tuple(grids)
+
+
+class FusedOccupancy:
+    """The grids of a run with --r2l_occ_fused: the pair build_pair makes, and the device counters the fused frames calls add
+    their live and total samples to (render_frames(occupancy=, live_acc=)).  Nothing is read per frame: log() reads the two
+    counters once, when the run's frames are done."""
+
+    def __init__(self, args, coarse, fine, near, far, logger):
+        self.pair = build_pair(args, coarse, fine, near, far, logger)
+        self.bound = box_half_side(args, near, far)
+        self.live_acc = torch.zeros(2, dtype=torch.int64, device=self.pair[0].bits.device)
+
+    def kwargs(self):
+        return {"occupancy": self.pair, "live_acc": self.live_acc}
+
+    def provenance(self):
+        g = self.pair[0]
+        return {"res": g.G, "bound": self.bound, "k": g.k, "dilate": g.dilate}
+
+    def log(self, logger):
+        a, b = (int(x) for x in self.live_acc.tolist())  # the one read of the run
+        logger.info("occupancy grid: live points %d / %d (%.1f%%)" % (a, b, 100. * a / max(b, 1)))
+        return a, b
 
 
 def log_live(pair, logger):

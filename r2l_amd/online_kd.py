@@ -35,11 +35,16 @@ def shards_needed(n_pose, chunk_poses, H, W, rank=0, world=1, rays_per_shard=RAY
     return sum((min(chunk, n - a) * H * W) // rays_per_shard for a in range(0, n, chunk))
 
 
+class _Quiet:
+    def info(self, *a):
+        pass
+
+
 class TeacherFill:
     """State of an incremental fill: the rank's pose list, its RandomState, the teacher pair and what is still pending."""
 
     def __init__(self, store, targs, H, W, focal, near, far, n_pose, chunk_poses, rank, world, device, logger=None,
-                 rand_pose=None, ndc=False):
+                 rand_pose=None, ndc=False, occ_args=None):
         from .create_data import create_teacher
         from .driver import apply_arithmetic
         check_teacher_args(targs, device)
@@ -59,6 +64,15 @@ class TeacherFill:
         self.r2l_config = None  # the record apply_arithmetic returns (precision of the teacher kernels): provenance()
         if logger is not None:
             self.r2l_config = apply_arithmetic(targs, self.device, logger, teachers=(self.coarse, self.fine))
+        # --r2l_occ_fused (occ_args: the namespace that carries r2l_occ_res / r2l_occ_bound): both grids once, behind the
+        # arithmetic switch; the build is deterministic, so a re-run renders the same store
+        self.occ = self.occ_prov = None
+        if occ_args is not None:
+            from .occupancy import FusedOccupancy
+            if self.ndc:
+                raise ValueError("--r2l_occ_fused puts its box about the origin of a bounded scene: not with an NDC (llff) scene")
+            self.occ = FusedOccupancy(occ_args, self.coarse, self.fine, self.near, self.far, _Quiet() if logger is None else logger)
+            self.occ_prov = self.occ.provenance()  # (kept: the grids go with the teacher in release())
 
     @property
     def pending(self):
@@ -80,7 +94,8 @@ class TeacherFill:
         return {"teacher_ckpt": a.teacher_ckpt, "N_samples": a.N_samples, "N_importance": a.N_importance, "perturb": a.perturb,
                 "white_bkgd": bool(a.white_bkgd), "use_rand_focal": bool(a.use_rand_focal), "n_pose": self.n_pose,
                 "create_data_chunk": self.chunk, "near": self.near, "far": self.far, "ndc": self.ndc, "focal": self.focal,
-                "precision": (self.r2l_config or {}).get("precision", a.r2l_precision), "R2L_SEED": os.environ.get("R2L_SEED", "0")}
+                "precision": (self.r2l_config or {}).get("precision", a.r2l_precision), "R2L_SEED": os.environ.get("R2L_SEED", "0"),
+                **({"occupancy": self.occ_prov} if self.occ_prov is not None else {})}
 
     def fill_group(self):
         """Render the next flush group into the store; returns the number of shards it added."""
@@ -101,11 +116,12 @@ class TeacherFill:
         e[0].record()
         # a compact store (raystore.CompactRayStore) takes rgb and the poses: the 24 bytes of o, d per ray are never written
         compact = hasattr(self.store, "append_frames")
+        occ_kw = self.occ.kwargs() if self.occ is not None else {}
         with torch.no_grad():
             parts = [render_frames(c2ws[s:s + n], self.H, self.W, focals[s:s + n], self.near, self.far, self.coarse, self.fine,
                                    a.N_samples, a.N_importance, a.perturb, a.white_bkgd, seed=1000003 * self.rank,
-                                   frame_id0=ids[s], rows=not compact, ndc=self.ndc,
-                                   ndc_focal=self.focal)["rgb" if compact else "rows"] for s, n in _runs(ids)]
+                                   frame_id0=ids[s], rows=not compact, ndc=self.ndc, ndc_focal=self.focal,
+                                   **occ_kw)["rgb" if compact else "rows"] for s, n in _runs(ids)]
         rows = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         key = int(self.rng.randint(0, 2**31 - 1))  # the flush seed: drawn where create_data.main's flush() draws it
         e[1].record()
@@ -124,6 +140,10 @@ class TeacherFill:
         """Drop the teacher: its engines (flat parameters, packed streams), the frames' work buffer and the modules."""
         if self.coarse is None:
             return
+        if self.occ is not None:  # the live share of the whole fill: the one read of the counters
+            if self.logger is not None:
+                self.occ.log(self.logger)
+            self.occ = None
         freed = 0
         for net in (self.coarse, self.fine):
             eng = net.__dict__.pop("_r2l_teacher_engine", None)

@@ -61,6 +61,11 @@ FLAGS = {
     # --r2l_fused_frames / --r2l_online_kd (the frames call has no host read of the live count), --dataset_type llff (NDC space
     # needs its own box) or raw_noise_std > 0.  utils/train_nerf.py and student training ignore the three
     "r2l_occupancy": ("flag", False), "r2l_occ_res": (int, 128), "r2l_occ_bound": (float, 0.),
+    # the same grids inside the FUSED frames call (r2l_teacher_frames_occ_cfg: the live count stays on the device, nothing is
+    # read on the host): utils/create_data.py --create_data rand with --r2l_fused_frames or --r2l_store_save, --test_teacher and
+    # main.py --model_name nerf --render_only with --r2l_fused_frames, main.py --r2l_online_kd.  Shares r2l_occ_res / r2l_occ_bound;
+    # not together with --r2l_occupancy (the per-pose path), nor with llff or raw_noise_std > 0.  utils/train_nerf.py ignores it
+    "r2l_occ_fused": ("flag", False),
     # device-resident ray store (r2l_amd/raystore.py): training draws its shards from HBM with one launch per step.
     # r2l_device_store: the shard files of --datadir_kd are read once into the store.  r2l_online_kd: no files at all, the
     # teacher (--teacher_ckpt, described by the config file --r2l_teacher_config) renders --n_pose_kd poses into the store, all
@@ -280,7 +285,7 @@ def validate_occupancy(args, raw_noise_std=None):
     for other in ("r2l_fused_frames", "r2l_online_kd"):
         if getattr(args, other):
             raise ValueError("--r2l_occupancy skips samples after a host read of the live count: not with --%s, whose frames call "
-                             "enqueues every stage without one (a device-side count is the follow-up)" % other)
+                             "enqueues every stage without one (--r2l_occ_fused skips inside that call, with the count left on the device)" % other)
     if args.dataset_type == "llff":
         raise ValueError("--r2l_occupancy puts its box about the origin of a bounded scene: not with --dataset_type llff (NDC "
                          "space needs a box of its own)")
@@ -293,6 +298,33 @@ def validate_occupancy(args, raw_noise_std=None):
         raise ValueError("--r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
     if not args.use_viewdirs:
         raise ValueError("--r2l_occupancy needs --use_viewdirs (the teacher kernels' network)")
+
+
+def validate_occ_fused(args, paths, raw_noise_std=None, use_viewdirs=None):
+    """--r2l_occ_fused: the occupancy grids inside the fused frames call.  paths: the switches of this entry point that render
+    through that call (one of them must be given).  raw_noise_std / use_viewdirs: the values of the TEACHER the frames come from
+    (default: this namespace's; main.py --r2l_online_kd passes its teacher config's).  Names the other flag, before anything is
+    loaded."""
+    if not args.r2l_occ_fused:
+        return
+    if args.r2l_occupancy:
+        raise ValueError("--r2l_occ_fused skips samples inside the fused frames call, --r2l_occupancy in the per-pose render: give "
+                         "one of the two (not --r2l_occ_fused with --r2l_occupancy)")
+    if not any(getattr(args, p) for p in paths):
+        raise ValueError("--r2l_occ_fused acts inside the fused frames call: it needs %s (the per-pose renders take "
+                         "--r2l_occupancy)" % " or ".join("--" + p for p in paths))
+    if args.dataset_type == "llff":
+        raise ValueError("--r2l_occ_fused puts its box about the origin of a bounded scene: not with --dataset_type llff (NDC "
+                         "space needs a box of its own)")
+    if (args.raw_noise_std if raw_noise_std is None else raw_noise_std) > 0:
+        raise ValueError("--r2l_occ_fused with raw_noise_std > 0: noise can lift a skipped sample above zero (pass "
+                         "--raw_noise_std 0)")
+    if not 1 <= args.r2l_occ_res <= 512:
+        raise ValueError("--r2l_occ_fused: --r2l_occ_res must be in 1 .. 512, got %d" % args.r2l_occ_res)
+    if args.r2l_occ_bound < 0:
+        raise ValueError("--r2l_occ_fused: --r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
+    if not (args.use_viewdirs if use_viewdirs is None else use_viewdirs):
+        raise ValueError("--r2l_occ_fused needs a teacher with --use_viewdirs (the teacher kernels' network)")
 
 
 def validate_compact_store(args):

@@ -153,6 +153,22 @@ class TeacherEngine:
                                          _stream(), ctypes.byref(_engine.merged_config(self.cfg))), "r2l_teacher_mlp")
         return raw
 
+    def mlp_live(self, rays_o, rays_d, viewdirs, z, idx, count):
+        """raw[R,S,4]: zero, but raw[n] = the point network at sample n = idx[i] for i < min(count[0], R*S) — mlp's bits there
+        (r2l_teacher_mlp_live_cfg).  idx: int64 device tensor of at least R*S entries (the count says how many are read, so the
+        tensor must reach the capacity), count: int64[1] on the device, as OccupancyGrid.index returns them.  Nothing is read on
+        the host."""
+        self.ensure_packed()
+        R, S = z.shape
+        if idx.dtype != torch.int64 or count.dtype != torch.int64 or idx.numel() < R * S or count.numel() < 1:
+            raise ValueError("mlp_live: idx must be int64 with at least R*S = %d entries and count int64[1]" % (R * S))
+        raw = torch.empty(R, S, 4, dtype=torch.float32, device=z.device)
+        _lib.check(
+            self.lib.r2l_teacher_mlp_live_cfg(_ptr(rays_o.contiguous()), _ptr(rays_d.contiguous()), _ptr(viewdirs.contiguous()),
+                                              _ptr(z.contiguous()), _ptr(idx.contiguous()), _ptr(count), _ptr(self.wstream),
+                                              _ptr(self.flat), _ptr(raw), R, S, _stream(),
+                                              ctypes.byref(_engine.merged_config(self.cfg))), "r2l_teacher_mlp_live_cfg")
+        return raw
 
     def range_info(self):
         """Range control of the fp16 teacher kernel (include/r2l_hip.h; as R2LEngine.range_info; synchronises)."""
@@ -476,7 +492,7 @@ def draw_normal(n, seed, stream_id, device, scale=1.):
 
 
 def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samples, N_importance, perturb, white_bkgd, seed,
-                  frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None):
+                  frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None, occupancy=None, live_acc=None):
     """K teacher frames from K poses in ONE library call (r2l_teacher_frames_cfg): what render(H, W, focal_k, c2w=c2ws[k],
     ndc=False, near=, far=, use_viewdirs=True, ...) computes per pose, with the random draws of perturb > 0 made on the device
     by draw_uniform (frame k: t_rand = stream 2*(frame_id0+k), u = stream 2*(frame_id0+k)+1 of `seed`).  GPU only.
@@ -485,7 +501,11 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
     'rows' ([K*H*W,9] = [o, d, rgb] when rows=True, else None)}.
     ndc=True: render(..., ndc=True) per pose instead (desc.ndc): rows keep the world rays, the stages see their ndc_rays image.  The
     NDC coefficients take ONE focal, ndc_focal (default: `focal`, which must then be a number) — with per-frame focals that is the
-    reference's use_rand_focal: rays from focal_k, render(H, W, focal, rays=...) with the scene's."""
+    reference's use_rand_focal: rays from focal_k, render(H, W, focal, rays=...) with the scene's.
+    occupancy = (grid_coarse, grid_fine), two built r2l_amd.occupancy.OccupancyGrid (the same one twice when the coarse net serves
+    both passes): r2l_teacher_frames_occ_cfg — each pass sends only its live samples through the point network, the live count
+    never leaves the device.  live_acc: None or an int64[2] device tensor that receives += (live, all) samples of every pass; the
+    caller reads it when it wants the share (one read per run, not per frame).  Not with ndc=True: the box is in world space."""
     c2ws = _pose_table(c2ws, next(network_fn.parameters()).device)
     _need_gpu(c2ws, "render_frames")
     dev = c2ws.device
@@ -504,7 +524,18 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
     desc = _lib.TeacherFrameDesc(ndc=int(bool(ndc)), H=H, W=W, focal=f, near=near, far=far, N_samples=N_samples, N_importance=N_importance,
                                  perturb=int(perturb > 0), white_bkgd=int(bool(white_bkgd)), raw_noise_std=0.,
                                  chunk_rays=int(chunk), seed=int(seed) & (2**64 - 1), frame_id0=int(frame_id0) & (2**64 - 1))
-    n_work = lib.r2l_teacher_frames_work_floats(ctypes.byref(desc))
+    if occupancy is not None:
+        if ndc:
+            raise ValueError("render_frames: occupancy with ndc=True — the box of an occupancy grid is in world space")
+        for g in occupancy:
+            if g.bits is None or g.bits.device != dev:
+                raise ValueError("render_frames: occupancy needs two grids built on %s" % dev)
+        if live_acc is not None and (live_acc.dtype != torch.int64 or live_acc.numel() != 2 or live_acc.device != dev):
+            raise ValueError("render_frames: live_acc must be an int64[2] tensor on %s" % dev)
+    elif live_acc is not None:
+        raise ValueError("render_frames: live_acc without occupancy")
+    size_fn = lib.r2l_teacher_frames_work_floats if occupancy is None else lib.r2l_teacher_frames_occ_work_floats
+    n_work = size_fn(ctypes.byref(desc))
     if n_work < 0:
         _lib.check(1, "r2l_teacher_frames_work_floats")
     work = getattr(coarse, "_frames_work", None)  # kept on the engine: frames of one size re-use it
@@ -517,10 +548,15 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
     new = lambda *s: torch.empty(*s, dtype=torch.float32, device=dev)
     out = {"rgb": new(R, 3), "disp": new(R), "acc": new(R), "depth": new(R), "rgb0": new(R, 3) if N_importance > 0 else None,
            "rows": new(R, 9) if rows else None}
-    _lib.check(
-        lib.r2l_teacher_frames_cfg(_ptr(c2ws), _ptr(fdev), K, ctypes.byref(desc), _ptr(ttab), _ptr(u_det), _ptr(coarse.wstream),
-                                   _ptr(coarse.flat), _ptr(None if fine is None else fine.wstream),
-                                   _ptr(None if fine is None else fine.flat), _ptr(out["rows"]), _ptr(out["rgb"]),
-                                   _ptr(out["disp"]), _ptr(out["acc"]), _ptr(out["depth"]), _ptr(out["rgb0"]), _ptr(work),
-                                   _stream(), ctypes.byref(_engine.merged_config(coarse.cfg))), "r2l_teacher_frames_cfg")
+    head = (_ptr(c2ws), _ptr(fdev), K, ctypes.byref(desc), _ptr(ttab), _ptr(u_det), _ptr(coarse.wstream), _ptr(coarse.flat),
+            _ptr(None if fine is None else fine.wstream), _ptr(None if fine is None else fine.flat), _ptr(out["rows"]),
+            _ptr(out["rgb"]), _ptr(out["disp"]), _ptr(out["acc"]), _ptr(out["depth"]), _ptr(out["rgb0"]))
+    tail = (_ptr(work), _stream(), ctypes.byref(_engine.merged_config(coarse.cfg)))
+    with torch.cuda.device(dev):
+        if occupancy is None:
+            _lib.check(lib.r2l_teacher_frames_cfg(*head, *tail), "r2l_teacher_frames_cfg")
+        else:
+            gc, gf = occupancy
+            _lib.check(lib.r2l_teacher_frames_occ_cfg(*head, ctypes.byref(gc.desc()), None if gf is gc else ctypes.byref(gf.desc()),
+                                                      _ptr(live_acc), *tail), "r2l_teacher_frames_occ_cfg")
     return out

@@ -6,6 +6,14 @@ kernel times of compact and scatter on one chunk, max |d RGB| and PSNR between t
 a skipped sample with sigma > 0 on the 2000 rays of tests/test_occupancy_gpu.py (test 5).
 
     python tools/occupancy_time.py --out profiles/occupancy.txt
+
+--fused: the grids inside the fused frames call (render_frames(occupancy=pair), r2l_teacher_frames_occ_cfg) instead.  Same frame,
+pair, grid and boxes; ms per frame of (a) render_frames without grids, (b) render_frames with the grids, (c) the per-pose path
+above (render(..., occupancy=pair), chunk 32 768) and (d) render_frames with an ALL-EMPTY grid whose box holds every sample (the
+floor: the capacity-sized grid of workgroups that leave at once, the index launches, the stages around the point network), three
+rounds alternated a -> b -> c -> d; the live share of (b) from its device counters and the spread between rounds.
+
+    python tools/occupancy_time.py --fused --out profiles/occupancy_fused.txt
 """
 import argparse
 import math
@@ -31,6 +39,54 @@ def timed(fn):
     return e0.elapsed_time(e1), out
 
 
+def fused_report(a, nets, H, W, focal, c2w, dev):
+    """The lines of --fused (see the module docstring)."""
+    import numpy as np
+    med = lambda v: sorted(v)[len(v) // 2]
+    kw = dict(chunk=32768, c2w=c2w, ndc=False, near=2., far=6., use_viewdirs=True, network_fn=nets[0], network_fine=nets[1],
+              network_query_fn=None, N_samples=64, N_importance=128, perturb=0., white_bkgd=True)
+    per_pose = lambda occ: render.render(H, W, focal, occupancy=occ, **kw)[0]
+    frames = lambda occ, acc=None: render.render_frames(c2w[None], H, W, focal, 2., 6., nets[0], nets[1], 64, 128, 0., True, seed=0,
+                                                        occupancy=occ, live_acc=acc)["rgb"]
+    lines = ["teacher frames, %d x %d, 64+128 samples, perturb 0, precision %s (%s), trained-like pair of tests/teacher_util.py, %s"
+             % (H, W, a.precision, engine.arithmetic(render.teacher_engine(nets[0]).cfg)["precision"], torch.cuda.get_device_name(0)),
+             "grid %d^3 cells x 2 probes per cell and axis x dilation 1; ms/frame by device events, one process, rounds alternated a -> b -> c -> d" % a.res,
+             "(a) render_frames, no grids   (b) render_frames(occupancy=pair): a whole frame per pass, no host read",
+             "(c) render(occupancy=pair) per pose, chunk 32768: a host read of the live count per pass   (d) render_frames, all-empty grid "
+             "over +-16: every sample inside and skipped"]
+    with torch.no_grad():
+        empty = OC.OccupancyGrid([-16.] * 3, [16.] * 3, G=a.res, k=1, dilate=0).set_bits(np.zeros(OC.n_words(a.res), np.uint32), device=dev)
+        for box in (1.6, 2.5):
+            pair = tuple(OC.OccupancyGrid([-box] * 3, [box] * 3, G=a.res).build(n) for n in nets)
+            acc, acc_d = (torch.zeros(2, dtype=torch.int64, device=dev) for _ in range(2))
+            paths = {"a": lambda: frames(None), "b": lambda: frames(pair, acc), "c": lambda: per_pose(pair),
+                     "d": lambda: frames((empty, empty), acc_d)}
+            for fn in paths.values():
+                fn()  # warm-up: weight packing, allocator, work buffers
+            acc.zero_()
+            acc_d.zero_()
+            ms, out = {k: [] for k in paths}, {}
+            for _ in range(a.rounds):
+                for k, fn in paths.items():
+                    t, out[k] = timed(fn)
+                    ms[k].append(t)
+            live, total = (int(x) for x in acc.tolist())
+            share = live / max(total, 1)
+            lines.append("box +-%.1f: occupied cells %.1f %% (coarse net) / %.1f %% (fine net)" %
+                         (box, 100 * pair[0].occupied_share(), 100 * pair[1].occupied_share()))
+            for k, v in ms.items():
+                lines.append("  (%s) %s   median %.2f, spread %.2f" % (k, "  ".join("%.2f" % x for x in v), med(v), max(v) - min(v)))
+            spread = max(max(v) - min(v) for v in ms.values())
+            lines.append("  live points of (b) %.1f %% (%d / %d over %d frames); (d) live %d" %
+                         (100 * share, live, total, a.rounds, int(acc_d[0])))
+            lines.append("  (b) / (a) %.3f; (b) - (c) %+.2f ms (largest spread of a path %.2f ms); live share x (a) + (d) = %.2f ms against (b) %.2f ms"
+                         % (med(ms["b"]) / med(ms["a"]), med(ms["b"]) - med(ms["c"]), spread, share * med(ms["a"]) + med(ms["d"]), med(ms["b"])))
+            lines.append("  max |rgb(b) - rgb(c)| %.3e (the per-pose path forms its own rays), max |rgb(b) - rgb(a)| %.3e; (d) is the "
+                         "background: %s" % (float((out["b"].reshape(-1, 3) - out["c"].reshape(-1, 3)).abs().max()),
+                                             float((out["b"] - out["a"]).abs().max()), bool((out["d"] == 1.).all())))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=400)
@@ -38,6 +94,7 @@ def main():
     ap.add_argument("--rounds", type=int, default=3)
     ap.add_argument("--precision", default="auto", choices=["auto", "fp16x2", "bf16x3", "fp32_mfma"])
     ap.add_argument("--out", default="")
+    ap.add_argument("--fused", action="store_true", help="time the grids inside the fused frames call (profiles/occupancy_fused.txt)")
     a = ap.parse_args()
     dev = "cuda:0"
     nets = []
@@ -52,6 +109,13 @@ def main():
     H = W = a.size
     focal = 555.5555155968841 * a.size / 400.
     c2w = torch.from_numpy(O.pose_spherical(35., -25., 4.)[:3, :4]).to(dev)
+    if a.fused:
+        text = "\n".join(fused_report(a, nets, H, W, focal, c2w, dev))
+        print(text)
+        if a.out:
+            with open(os.path.abspath(a.out), "w") as f:
+                f.write(text + "\n")
+        return
     kw = dict(chunk=32768, c2w=c2w, ndc=False, near=2., far=6., use_viewdirs=True, network_fn=nets[0], network_fine=nets[1],
               network_query_fn=None, N_samples=64, N_importance=128, perturb=0., white_bkgd=True)
     frame = lambda occ: render.render(H, W, focal, occupancy=occ, **kw)[0]
