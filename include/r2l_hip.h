@@ -550,7 +550,9 @@ int r2l_occ_live_add(const int64_t* count /*device, 1*/, int64_t total, int64_t*
  * leaves as a whole, before any LDS staging or barrier, when its first lane is at or past the count — which covers a count of 0 —,
  * and a partly filled last workgroup clamps its idle lanes to row count - 1.  The fp16x2 family keeps its range control: its live
  * kernel is followed by the rescale kernel and by the bf16x3 live kernel with run_if = GO, the dispatch of r2l_teacher_mlp_cfg;
- * cfg is consulted with the capacity (only cfg->precision matters).  The training form (r2l_teacher_mlp_train) has no live variant.
+ * cfg is consulted with the capacity (only cfg->precision matters).  The training form (r2l_teacher_mlp_train) has no live variant
+ * behind THIS entry point, which writes no stash: its live form is a call of its own, r2l_teacher_mlp_train_live ("occupancy while
+ * the teacher trains", below).
  * R == 0 is a successful no-op.  Refused before any launch (hipErrorInvalidValue, r2l_last_error names the argument): a NULL
  * pointer, R < 0, S < 1, R*S >= 2^31, raw not 16-byte aligned, an invalid cfg. */
 int r2l_teacher_mlp_live_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z /*[R,S]*/,
@@ -1065,6 +1067,64 @@ int r2l_teacher_train_step(const r2l_teacher_step_desc* d,
         float* params, float* grads, float* exp_avg, float* exp_avg_sq,   /* [coarse | fine], r2l_teacher_param_count() each */
         float* wstream_coarse, float* wstream_fine, /* wstream_fine NULL iff N_importance == 0 */
         float* loss_out /* dev [2]: loss, psnr */, float* work, void* stream);
+
+/* ---- occupancy while the teacher trains: the training step on the live samples -----------------------------------------------
+ * With raw_noise_std == 0 a sample whose sigma pre-activation is not positive has alpha = 0 exactly in r2l_raw2outputs and an exactly
+ * zero row of d loss / d raw in r2l_raw2outputs_backward (relu' = 0 on sigma, weight 0 on the colours): it adds exact zeros to every
+ * weight gradient.  Leaving such samples out of the forward AND the backward changes a step by summation order only, as long as the
+ * grid skips no sample of positive sigma; what a grid costs in training is its staleness between refreshes, not a biased gradient.
+ * The three calls below are r2l_teacher_mlp_train, r2l_teacher_backward and r2l_teacher_train_step on an index list whose count stays
+ * on the device (r2l_occ_index).  All are stateless, check their arguments before any launch (hipErrorInvalidValue, r2l_last_error
+ * names the argument), enqueue on `stream`, never synchronise, use no atomics and give the same bits for the same arguments.  The plain
+ * calls enqueue what they always did: the live kernels are instantiations of their own (template parameters / wrappers around the
+ * one GEMM body).
+ *
+ * r2l_teacher_mlp_train_live: the fp32-MFMA training forward launched over the capacity P = R*S; tile lane i < count =
+ * min(*count_dev, P) takes sample n = idx[i].  raw[R,S,4] is zero-filled first (a memset), then raw[n] gets the bits
+ * r2l_teacher_mlp_train(..., R, S) writes at n.  The stash is COMPACT: slot l sits at the offset a stash of P points has it
+ * (r2l_teacher_stash_floats(P) floats in all), and row i of a slot holds the layer output of sample idx[i], bit for bit the plain
+ * call's row idx[i]; rows at or past the count are not written.  A workgroup (128 lanes) with no lane below the count leaves as a
+ * whole before any staging or barrier.  An idx[i] outside [0, P) reads and writes nothing (neither raw nor its stash row).
+ * R == 0 is a successful no-op.  Refused: a NULL pointer, R < 0, S < 1, R*S >= 2^31, raw or stash not 16-byte aligned. */
+int r2l_teacher_mlp_train_live(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z /*[R,S]*/,
+                               const int64_t* idx /*device, capacity R*S*/, const int64_t* count_dev /*device, 1*/,
+                               const float* wstream, const float* tparams, float* raw /*[R,S,4]*/, float* stash, int64_t R, int S,
+                               void* stream);
+/* r2l_teacher_backward on the live samples.  stash: r2l_teacher_mlp_train_live's on the same idx / count_dev; draw[R,S,4] as
+ * r2l_raw2outputs_backward writes it.  work: r2l_teacher_train_live_work_floats(P) = r2l_teacher_train_work_floats(P) + 4 P floats
+ * (-1 for P < 0); a first small kernel gathers draw[idx[p]] to [count,4] there (zero for an idx[p] outside [0, P)).  Every GEMM
+ * launch of the chain is sized for the capacity and reads count = min(*count_dev, P) itself: dX tiles (128 rows) whose first row is
+ * at or past the count leave whole; weight-gradient chunks (2048 points) at or past the count contribute nothing, and the slab
+ * reduce sums the live chunks in increasing order.  The encoder operand reads ray idx[p] / S and z[idx[p]].
+ * grads equals, BIT FOR BIT, r2l_teacher_backward on the compacted problem: rows rays_o[idx/S], rays_d[idx/S], viewdirs[idx/S] and
+ * z.flat[idx] as [M,1], the stash slots gathered to the layout of M points, and draw.flat[idx].  A count of 0 gives all-zero grads;
+ * a count above P counts as P; R == 0 zero-fills grads.  Refused: a NULL pointer, R < 0, S < 1, R*S >= 65535 * 128. */
+int64_t r2l_teacher_train_live_work_floats(int64_t P);
+int r2l_teacher_backward_live(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z /*[R,S]*/,
+                              const int64_t* idx, const int64_t* count_dev, const float* tparams, const float* stash,
+                              const float* draw /*[R,S,4]*/, float* grads, float* work, int64_t R, int S, void* stream);
+/* r2l_teacher_train_step with each pass's r2l_teacher_mlp_train replaced by r2l_occ_index -> r2l_teacher_mlp_train_live on the pass's
+ * grid (grid_fine NULL: grid_coarse serves both passes) and each r2l_teacher_backward by r2l_teacher_backward_live on the same
+ * idx / count; the draws, r2l_raw2outputs, r2l_sample_pdf_sort, r2l_raw2outputs_backward, the loss, Adam and the re-pack are those of
+ * r2l_teacher_train_step, arguments up to loss_out included.  Still no allocation and no host synchronisation.  live_acc: NULL, or
+ * device int64[2] that receives += (live samples, all samples) of every pass (r2l_occ_live_add).  work: 16-byte aligned,
+ * r2l_teacher_step_occ_work_floats(d) floats (-1 with r2l_last_error for a descriptor the call would refuse): the parts of
+ * r2l_teacher_step_work_floats with the backward's scratch that of r2l_teacher_backward_live, then idx (2 floats per sample) and the
+ * count (4) of each pass and r2l_occ_index_work_bytes of the larger pass, every part rounded up to 4 KiB.  With all-ones grids the
+ * step equals r2l_teacher_train_step bit for bit; r2l_teacher_train_step itself enqueues exactly what it always did and
+ * r2l_teacher_step_work_floats is unchanged (one body serves both entry points).
+ * Refused in addition to r2l_teacher_train_step's refusals: a NULL grid_coarse, a grid r2l_occ_build would refuse,
+ * d->raw_noise_std > 0 (noise can lift a skipped sample above zero), N_rand * (N_samples + N_importance) >= 65535 * 128.  The
+ * descriptor's reserved stays zero: the grids are arguments.  r2l_amd/teacher_train.py (TeacherTrainer.set_occupancy) is the worked
+ * example. */
+int64_t r2l_teacher_step_occ_work_floats(const r2l_teacher_step_desc* d);
+int r2l_teacher_train_step_occ(const r2l_teacher_step_desc* d,
+        const float* rays_o, const float* rays_d, const float* viewdirs, const float* target,
+        const float* ttab, const float* u_det,
+        float* params, float* grads, float* exp_avg, float* exp_avg_sq,
+        float* wstream_coarse, float* wstream_fine,
+        float* loss_out, const r2l_occ_grid* grid_coarse, const r2l_occ_grid* grid_fine /*NULL: grid_coarse serves both passes*/,
+        int64_t* live_acc /*device int64[2] or NULL*/, float* work, void* stream);
 
 /* ---- frame writer (host threads; test-set evaluation) ------------------------------------------------------------------
  * Replaces `imageio.imwrite(filename, to8b(rgb))` of every prediction / ground-truth frame in render_path (main.py:337-344):

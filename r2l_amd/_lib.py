@@ -217,6 +217,11 @@ SIGNATURES = {
     "r2l_pose_refine_step": (_i, [_posep] + [_p] * 11),
     "r2l_teacher_step_work_floats": (_l, [_stepp]),
     "r2l_teacher_train_step": (_i, [_stepp] + [_p] * 15),
+    "r2l_teacher_mlp_train_live": (_i, [_p] * 10 + [_l, _i, _p]),
+    "r2l_teacher_train_live_work_floats": (_l, [_l]),
+    "r2l_teacher_backward_live": (_i, [_p] * 11 + [_l, _i, _p]),
+    "r2l_teacher_step_occ_work_floats": (_l, [_stepp]),
+    "r2l_teacher_train_step_occ": (_i, [_stepp] + [_p] * 13 + [_occp, _occp, _p, _p, _p]),
     "r2l_png_writer_open": (_i, [_i, _i, _p]),
     "r2l_png_writer_submit": (_i, [_p, ctypes.c_char_p, _p, _i, _i, _i, _p, _p]),
     "r2l_png_writer_wait": (_i, [_p, _l]),

@@ -178,11 +178,12 @@ __device__ __forceinline__ void t_pe_gemm(f32x16 (&acc)[R2L_NT], const float (&p
     t_pe_steps<BASE, 0, NG>(acc, p, h, ws, t_xyz_group<0>(p, h));
 }
 
+// The chain of one workgroup, the body of the two kernels below.
 // STASH: the same chain (bit-identical raw), plus every layer output written to a.stash for the backward pass
-// LIVE: the launch form on an index list with a device count (r2l_teacher_net.h "live form"; never with STASH)
-template <bool STASH, bool LIVE = false>
-__global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherArgs a) {
-    static_assert(!(STASH && LIVE), "the training form has no live variant");
+// LIVE: the launch form on an index list with a device count (r2l_teacher_net.h "live form").  With STASH the stash is COMPACT:
+//       tile lane i writes row i of every slot (the slots at the offsets of a stash of n_pts points), raw goes to sample idx[i]
+template <bool STASH, bool LIVE>
+__device__ __forceinline__ void t_mlp_chain(const TeacherArgs& a) {
     int64_t n_pts = a.n_pts;
     if constexpr (LIVE) {
         n_pts = t_live_count(a.count_dev, a.n_pts);
@@ -219,7 +220,8 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         mfma_bias_group<true, 0>(x, ws, one_h0);
         t_pe_gemm<1, T_PE_GROUPS>(x, p, h, ws);  // 1 + 9 groups: the loop below starts at an even group index
     }
-    float* const st = STASH ? a.stash + pc * T_W : nullptr;  // this point's row in slot 0
+    const int64_t srow = LIVE ? pt : pc;                       // this point's stash row (live: its tile lane)
+    float* const st = STASH ? a.stash + srow * T_W : nullptr;  // ... in slot 0
     if constexpr (STASH)
         if (valid) t_stash_store(st, x, h, true);
     // (L1,L2) (L3,L4) (L5,L6) (L7,feature): t = W_odd relu(x) [+ W5pe pe] + b ; x = W_even relu(t) + b
@@ -300,7 +302,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         }
     }
     if constexpr (STASH)
-        if (valid) t_stash_store(T_STASH_SLOT(a.stash, T_STASH_VIEWS, a.n_pts) + pc * T_VIEWS, v, h, true);
+        if (valid) t_stash_store(T_STASH_SLOT(a.stash, T_STASH_VIEWS, a.n_pts) + srow * T_VIEWS, v, h, true);
     // rgb = Wrgb relu(v) + b
     float acc3[3] = {0.f, 0.f, 0.f};
 #pragma unroll
@@ -324,6 +326,16 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherAr
         *reinterpret_cast<f32x4*>(a.raw + (LIVE ? (int64_t)live_n : pt) * 4) = o4;
     }
 }
+
+// inference (plain and live) and training (plain): the kernel r2l_teacher_mlp_cfg, r2l_teacher_mlp_live_cfg and
+// r2l_teacher_mlp_train launch.  Its live form writes no stash
+template <bool STASH, bool LIVE = false>
+__global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_kernel(const TeacherArgs a) {
+    static_assert(!(STASH && LIVE), "the training form's live variant is r2l_teacher_mlp_train_live_kernel");
+    t_mlp_chain<STASH, LIVE>(a);
+}
+// training on an index list (r2l_teacher_mlp_train_live): the chain with the compact stash, a kernel of its own
+__global__ __launch_bounds__(256, 1) void r2l_teacher_mlp_train_live_kernel(const TeacherArgs a) { t_mlp_chain<true, true>(a); }
 
 // ------------------------------------------------------------------------------------------------------------------
 // C ABI
@@ -436,6 +448,38 @@ extern "C" int r2l_teacher_mlp_train(const float* rays_o, const float* rays_d, c
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
     a.raw = raw; a.n_pts = R * (int64_t)S; a.S = S; a.stash = stash;
     hipLaunchKernelGGL(r2l_teacher_mlp_kernel<true>, dim3(t_workgroups(a.n_pts)), dim3(256), 0, (hipStream_t)stream, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+// The training forward on an index list with a device count (include/r2l_hip.h): the fp32 chain with stash in its live form behind
+// a zero fill of raw.  Nothing here reads the count on the host.
+extern "C" int r2l_teacher_mlp_train_live(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                          const int64_t* idx, const int64_t* count_dev, const float* wstream, const float* params,
+                                          float* raw, float* stash, int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0, "r2l_teacher_mlp_train_live: R is negative");
+    R2L_REQUIRE(S >= 1, "r2l_teacher_mlp_train_live: S: need S >= 1");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_teacher_mlp_train_live: R*S: need R*S < 2^31");
+    if (R == 0) return 0;
+    R2L_REQUIRE(rays_o != nullptr, "r2l_teacher_mlp_train_live: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_teacher_mlp_train_live: rays_d is NULL");
+    R2L_REQUIRE(viewdirs != nullptr, "r2l_teacher_mlp_train_live: viewdirs is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_teacher_mlp_train_live: z is NULL");
+    R2L_REQUIRE(idx != nullptr, "r2l_teacher_mlp_train_live: idx is NULL");
+    R2L_REQUIRE(count_dev != nullptr, "r2l_teacher_mlp_train_live: count_dev is NULL");
+    R2L_REQUIRE(wstream != nullptr, "r2l_teacher_mlp_train_live: wstream is NULL");
+    R2L_REQUIRE(params != nullptr, "r2l_teacher_mlp_train_live: tparams is NULL");
+    R2L_REQUIRE(raw != nullptr, "r2l_teacher_mlp_train_live: raw is NULL");
+    R2L_REQUIRE(((uintptr_t)raw & 15) == 0, "r2l_teacher_mlp_train_live: raw is not 16-byte aligned");
+    R2L_REQUIRE(stash != nullptr, "r2l_teacher_mlp_train_live: stash is NULL");
+    R2L_REQUIRE(((uintptr_t)stash & 15) == 0, "r2l_teacher_mlp_train_live: stash is not 16-byte aligned");
+    const hipStream_t st = (hipStream_t)stream;
+    const int64_t cap = R * (int64_t)S;
+    R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)cap * 4 * sizeof(float), st));  // (sigma = +0 -> alpha = 0, as r2l_teacher_mlp_live_cfg)
+    TeacherArgs a{};
+    a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
+    a.raw = raw; a.n_pts = cap; a.S = S; a.stash = stash; a.idx = idx; a.count_dev = count_dev;
+    hipLaunchKernelGGL(r2l_teacher_mlp_train_live_kernel, dim3(t_workgroups(cap)), dim3(256), 0, st, a);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

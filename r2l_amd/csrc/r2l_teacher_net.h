@@ -147,6 +147,8 @@ struct T16Args {
 // The launch is sized for the capacity n_pts = R*S; tile lane i < count = min(*count_dev, n_pts) takes sample n = idx[i] where the
 // plain form takes sample i, and stores at raw + 4 n.  LIVE is a template parameter of each kernel: the plain instantiations
 // compile from the code they always had.  A point is a column of its tile, so raw[n] has the bits the plain form writes at n.
+// The fp32 chain's training form (STASH) has a live instantiation too, in a kernel of its own (r2l_teacher_mlp_train_live_kernel): its
+// stash is compact, tile lane i writes row i of a slot.
 // The count is an ordinary load of one address by every lane (the compiler may make it a scalar load).
 __device__ __forceinline__ int64_t t_live_count(const int64_t* __restrict__ count_dev, int64_t cap) {
     const int64_t c = *count_dev;

@@ -7,6 +7,9 @@
 //                           here from counter-based streams of (seed, step): a C host reproduces a run, a resume needs no generator
 // Two kernels of its own, one thread each: near / far into the work buffer (r2l_stratified_z reads them from the device), and the
 // step's loss / psnr from the two nets' r2l_loss_finish results.
+//   r2l_teacher_train_step_occ: the same body with each pass's forward replaced by r2l_occ_index -> r2l_teacher_mlp_train_live and each
+//                           network backward by r2l_teacher_backward_live on the same idx / count (occupancy grids; the live counts
+//                           stay on the device): still no allocation and no host synchronisation
 #include "r2l_common.h"
 #include <math.h>
 
@@ -50,9 +53,12 @@ const char* step_desc_check(const r2l_teacher_step_desc* d) {
 struct StepWork {
     int64_t nearfar, z, raw_c, stash_c, rgb_c, s_c, draw, sqerr_c, sqerr_f, mse_c, mse_f, bwd, trand, noise_c;
     int64_t wts, zs, zall, raw_f, stash_f, u, noise_f, total;
+    int64_t idx_c, count_c, idx_f, count_f, iwork;  // occupancy form only: int64 idx per sample and count (4) per pass, the index work
 };
 int64_t r4(int64_t n) { return (n + 3) & ~(int64_t)3; }
-StepWork step_work(const r2l_teacher_step_desc* d) {
+// occ: the layout of r2l_teacher_train_step_occ — the backward's scratch is r2l_teacher_backward_live's, and the parts of the two index
+// lists follow the plain parts.  Without it the layout is the one r2l_teacher_train_step always had.
+StepWork step_work(const r2l_teacher_step_desc* d, bool occ = false) {
     const int64_t R = d->N_rand, S = d->N_samples, NI = d->N_importance, T = S + NI;
     const bool noise = d->raw_noise_std > 0.f;
     StepWork w{};
@@ -66,7 +72,7 @@ StepWork step_work(const r2l_teacher_step_desc* d) {
     w.draw = take(R * T * 4);                        // d loss / d raw of one net at a time
     w.sqerr_c = take(R); w.sqerr_f = take(NI > 0 ? R : 0);
     w.mse_c = take(2); w.mse_f = take(NI > 0 ? 2 : 0);
-    w.bwd = take(r2l_teacher_train_work_floats(R * T));  // scratch of one net's backward at a time
+    w.bwd = take(occ ? r2l_teacher_train_live_work_floats(R * T) : r2l_teacher_train_work_floats(R * T));  // scratch of one net's backward at a time
     w.trand = take(d->perturb ? R * S : 0);
     w.noise_c = take(noise ? R * S : 0);
     w.wts = take(NI > 0 ? R * S : 0);
@@ -76,8 +82,52 @@ StepWork step_work(const r2l_teacher_step_desc* d) {
     w.stash_f = take(NI > 0 ? r2l_teacher_stash_floats(R * T) : 0);
     w.u = take(d->perturb ? R * NI : 0);
     w.noise_f = take(noise && NI > 0 ? R * T : 0);
+    if (occ) {
+        w.idx_c = take(2 * R * S); w.count_c = take(4);
+        w.idx_f = take(NI > 0 ? 2 * R * T : 0); w.count_f = take(NI > 0 ? 4 : 0);
+        w.iwork = take((r2l_occ_index_work_bytes(R * T) + 3) / 4);  // (R*T < 65535 * 128 < 2^31: step_occ_desc_check)
+    }
     w.total = at;
     return w;
+}
+
+// what the occupancy form asks of a valid descriptor beyond step_desc_check, or nullptr
+const char* step_occ_desc_check(const r2l_teacher_step_desc* d) {
+    if (d->raw_noise_std > 0.f)
+        return "r2l_teacher_train_step_occ: r2l_teacher_step_desc.raw_noise_std must be 0 (noise can lift a skipped sample above zero)";
+    if ((int64_t)d->N_rand * ((int64_t)d->N_samples + d->N_importance) >= (int64_t)65535 * 128)
+        return "r2l_teacher_train_step_occ: r2l_teacher_step_desc.N_rand: too many samples for one call (need N_rand * (N_samples + "
+               "N_importance) < 65535 * 128)";
+    return nullptr;
+}
+
+// The grids of the occupancy form, or none: the ONE body below serves both entry points
+struct StepOcc {
+    const r2l_occ_grid *coarse, *fine;
+    int64_t* live_acc;
+};
+
+int step_body(const r2l_teacher_step_desc* d, const float* rays_o, const float* rays_d, const float* viewdirs, const float* target,
+              const float* ttab, const float* u_det, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* wstream_coarse,
+              float* wstream_fine, float* loss_out, float* work, void* stream, const StepOcc* occ);
+
+// The forward with stash of one pass: the plain launch, or (occupancy form) index -> [live_acc] -> the live launch
+int step_forward(const float* o, const float* dd, const float* v, const float* z, const float* wstream, const float* tparams, float* raw,
+                 float* stash, int64_t R, int S, void* stream, const r2l_occ_grid* grid, const StepOcc* occ, int64_t* idx, int64_t* count,
+                 void* iwork) {
+    if (occ == nullptr) return r2l_teacher_mlp_train(o, dd, v, z, wstream, tparams, raw, stash, R, S, stream);
+    int rc;
+    if ((rc = r2l_occ_index(grid, o, dd, z, R, S, idx, count, iwork, stream))) return rc;
+    if (occ->live_acc != nullptr && (rc = r2l_occ_live_add(count, R * (int64_t)S, occ->live_acc, stream))) return rc;
+    return r2l_teacher_mlp_train_live(o, dd, v, z, idx, count, wstream, tparams, raw, stash, R, S, stream);
+}
+
+// The network backward of one pass: the plain chain, or the live one on the pass's idx / count
+int step_backward(const float* o, const float* dd, const float* v, const float* z, const float* tparams, const float* stash,
+                  const float* draw, float* grads, float* work, int64_t R, int S, void* stream, const StepOcc* occ, const int64_t* idx,
+                  const int64_t* count) {
+    if (occ == nullptr) return r2l_teacher_backward(o, dd, v, z, tparams, stash, draw, grads, work, R, S, stream);
+    return r2l_teacher_backward_live(o, dd, v, z, idx, count, tparams, stash, draw, grads, work, R, S, stream);
 }
 
 }  // namespace
@@ -94,6 +144,55 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
                                       const float* target, const float* ttab, const float* u_det, float* params, float* grads,
                                       float* exp_avg, float* exp_avg_sq, float* wstream_coarse, float* wstream_fine, float* loss_out,
                                       float* work, void* stream) {
+    return step_body(d, rays_o, rays_d, viewdirs, target, ttab, u_det, params, grads, exp_avg, exp_avg_sq, wstream_coarse, wstream_fine,
+                     loss_out, work, stream, nullptr);
+}
+
+extern "C" int64_t r2l_teacher_step_occ_work_floats(const r2l_teacher_step_desc* d) {
+    if (const char* why = step_desc_check(d)) {
+        r2l_set_error_msg(why);
+        return -1;
+    }
+    if (const char* why = step_occ_desc_check(d)) {
+        r2l_set_error_msg(why);
+        return -1;
+    }
+    return step_work(d, true).total;
+}
+
+extern "C" int r2l_teacher_train_step_occ(const r2l_teacher_step_desc* d, const float* rays_o, const float* rays_d, const float* viewdirs,
+                                          const float* target, const float* ttab, const float* u_det, float* params, float* grads,
+                                          float* exp_avg, float* exp_avg_sq, float* wstream_coarse, float* wstream_fine, float* loss_out,
+                                          const r2l_occ_grid* grid_coarse, const r2l_occ_grid* grid_fine, int64_t* live_acc, float* work,
+                                          void* stream) {
+    if (const char* why = step_desc_check(d)) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    if (const char* why = step_occ_desc_check(d)) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    if (const char* why = r2l_occ_grid_why(grid_coarse, "r2l_teacher_train_step_occ: grid_coarse is NULL")) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    if (grid_fine != nullptr) {
+        if (const char* why = r2l_occ_grid_why(grid_fine, "r2l_teacher_train_step_occ: grid_fine is NULL")) {
+            r2l_set_error_msg(why);
+            return (int)hipErrorInvalidValue;
+        }
+    }
+    const StepOcc occ{grid_coarse, grid_fine ? grid_fine : grid_coarse, live_acc};
+    return step_body(d, rays_o, rays_d, viewdirs, target, ttab, u_det, params, grads, exp_avg, exp_avg_sq, wstream_coarse, wstream_fine,
+                     loss_out, work, stream, &occ);
+}
+
+namespace {
+
+int step_body(const r2l_teacher_step_desc* d, const float* rays_o, const float* rays_d, const float* viewdirs, const float* target,
+              const float* ttab, const float* u_det, float* params, float* grads, float* exp_avg, float* exp_avg_sq, float* wstream_coarse,
+              float* wstream_fine, float* loss_out, float* work, void* stream, const StepOcc* occ) {
     if (const char* why = step_desc_check(d)) {
         r2l_set_error_msg(why);
         return (int)hipErrorInvalidValue;
@@ -119,7 +218,12 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
     R2L_REQUIRE(((uintptr_t)work & 15) == 0, "r2l_teacher_train_step: work must be 16-byte aligned");
 
     const hipStream_t st = (hipStream_t)stream;
-    const StepWork w = step_work(d);
+    const StepWork w = step_work(d, occ != nullptr);
+    int64_t* const idx_c = occ ? (int64_t*)(work + w.idx_c) : nullptr;
+    int64_t* const count_c = occ ? (int64_t*)(work + w.count_c) : nullptr;
+    int64_t* const idx_f = occ ? (int64_t*)(work + w.idx_f) : nullptr;
+    int64_t* const count_f = occ ? (int64_t*)(work + w.count_f) : nullptr;
+    void* const iwork = occ ? (void*)(work + w.iwork) : nullptr;
     const int64_t n_net = r2l_teacher_param_count();
     const uint64_t sid = ((uint64_t)1 << 62) + 4 * (uint64_t)d->step;  // streams sid + 0 .. 3 of this step (include/r2l_hip.h)
     const bool noise = d->raw_noise_std > 0.f;
@@ -140,7 +244,8 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
         noise_c = work + w.noise_c;
         if ((rc = r2l_draw_normal(noise_c, (int64_t)R * S, d->seed, sid + 2, d->raw_noise_std, stream))) return rc;
     }
-    if ((rc = r2l_teacher_mlp_train(rays_o, rays_d, viewdirs, z, wstream_coarse, params, work + w.raw_c, work + w.stash_c, R, S, stream)))
+    if ((rc = step_forward(rays_o, rays_d, viewdirs, z, wstream_coarse, params, work + w.raw_c, work + w.stash_c, R, S, stream,
+                           occ ? occ->coarse : nullptr, occ, idx_c, count_c, iwork)))
         return rc;
 
     const float* mse_last = work + w.mse_c;
@@ -164,14 +269,14 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
             if ((rc = r2l_draw_normal(noise_f, (int64_t)R * T, d->seed, sid + 3, d->raw_noise_std, stream))) return rc;
         }
         float* const fparams = params + n_net;
-        if ((rc = r2l_teacher_mlp_train(rays_o, rays_d, viewdirs, zall, wstream_fine, fparams, work + w.raw_f, work + w.stash_f, R, T,
-                                        stream)))
+        if ((rc = step_forward(rays_o, rays_d, viewdirs, zall, wstream_fine, fparams, work + w.raw_f, work + w.stash_f, R, T, stream,
+                               occ ? occ->fine : nullptr, occ, idx_f, count_f, iwork)))
             return rc;
         if ((rc = r2l_raw2outputs_backward(work + w.raw_f, zall, rays_d, noise_f, d->white_bkgd, target, work + w.draw, work + w.sqerr_f,
                                            R, T, stream)))
             return rc;
-        if ((rc = r2l_teacher_backward(rays_o, rays_d, viewdirs, zall, fparams, work + w.stash_f, work + w.draw, grads + n_net,
-                                       work + w.bwd, R, T, stream)))
+        if ((rc = step_backward(rays_o, rays_d, viewdirs, zall, fparams, work + w.stash_f, work + w.draw, grads + n_net, work + w.bwd, R,
+                                T, stream, occ, idx_f, count_f)))
             return rc;
         if ((rc = r2l_loss_finish(work + w.sqerr_f, R, inv_denom, work + w.mse_f, stream))) return rc;
         mse_last = work + w.mse_f;
@@ -180,8 +285,8 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
     if ((rc = r2l_raw2outputs_backward(work + w.raw_c, z, rays_d, noise_c, d->white_bkgd, target, work + w.draw, work + w.sqerr_c, R, S,
                                        stream)))
         return rc;
-    if ((rc = r2l_teacher_backward(rays_o, rays_d, viewdirs, z, params, work + w.stash_c, work + w.draw, grads, work + w.bwd, R, S,
-                                   stream)))
+    if ((rc = step_backward(rays_o, rays_d, viewdirs, z, params, work + w.stash_c, work + w.draw, grads, work + w.bwd, R, S, stream, occ,
+                            idx_c, count_c)))
         return rc;
     if ((rc = r2l_loss_finish(work + w.sqerr_c, R, inv_denom, work + w.mse_c, stream))) return rc;
     hipLaunchKernelGGL(r2l_step_loss_kernel, dim3(1), dim3(64), 0, st, mse_last, mse_first, loss_out);
@@ -196,3 +301,5 @@ extern "C" int r2l_teacher_train_step(const r2l_teacher_step_desc* d, const floa
     if (NI > 0 && (rc = r2l_pack_teacher(params + n_net, wstream_fine, stream))) return rc;
     return 0;
 }
+
+}  // namespace

@@ -3,6 +3,8 @@
 //   r2l_raw2outputs_backward : loss seed 2 (rgb_map - target) / (3R) and autograd of raw2outputs (main.py:556-621) -> draw
 //   r2l_teacher_backward     : dX chain and weight / bias gradients of NeRF(D=8, W=256, 63+27, skips=[4], use_viewdirs)
 //                              (model/nerf_raybased.py:357-401) from draw and the stash of r2l_teacher_mlp_train
+//   r2l_teacher_backward_live : the same chain on the live samples of an index list, the count read on the device (occupancy grids
+//                              while the teacher trains; below r2l_teacher_backward)
 //   r2l_raw2outputs_backward_scaled : the first with the seed scale (or dL/drgb_map itself) an argument, and dL/d|rays_d|
 //   r2l_teacher_backward_input      : the same dX chain with no weight product, on to rays_o / rays_d / viewdirs (end of file)
 // The products are fp32-input MFMA (v_mfma_f32_32x32x2_f32) in one LDS-tiled GEMM kernel with loader / epilogue functors:
@@ -242,9 +244,10 @@ struct EpSlab {
     }
 };
 
+// (the kernel's body as a function: the live kernels below run it behind their own read of the device count)
 template <class LA, class LB, class EP>
-__global__ __launch_bounds__(256) void tt_gemm_kernel(const LA la, const LB lb, const EP ep, int64_t M, int N, int64_t K,
-                                                      int64_t kchunk, float* bias_slab) {
+__device__ __forceinline__ void tt_gemm_tile(const LA& la, const LB& lb, const EP& ep, int64_t M, int N, int64_t K, int64_t kchunk,
+                                             float* bias_slab) {
     __shared__ float As[TT_BK][TT_BM + 1];
     __shared__ float Bs[TT_BK][TT_BN + 1];
     __shared__ float rs[2][TT_BM];
@@ -305,6 +308,38 @@ __global__ __launch_bounds__(256) void tt_gemm_kernel(const LA la, const LB lb, 
         __syncthreads();
         if (tid < TT_BM && m0 + tid < M) bias_slab[((int64_t)blockIdx.z * M + m0 + tid) * (N + 1) + N] = rs[0][tid] + rs[1][tid];
     }
+}
+
+template <class LA, class LB, class EP>
+__global__ __launch_bounds__(256) void tt_gemm_kernel(const LA la, const LB lb, const EP ep, int64_t M, int N, int64_t K,
+                                                      int64_t kchunk, float* bias_slab) {
+    tt_gemm_tile(la, lb, ep, M, N, K, kchunk, bias_slab);
+}
+
+// ---- live form (r2l_teacher_backward_live): the points are rows 0 .. count - 1 of a launch sized for the capacity `cap`, and the
+// count = min(*count_dev, cap) is read here, by every launch of the chain (an ordinary load of one address, as the forward's live form).
+__device__ __forceinline__ int64_t tt_live_count(const int64_t* __restrict__ count_dev, int64_t cap) {
+    const int64_t c = *count_dev;
+    return c < cap ? c : cap;
+}
+// dX: the points are the rows.  A tile whose first row is at or past the count leaves whole, before any staging or barrier;
+// a partly filled tile stores rows below the count only.
+template <class LA, class LB>
+__global__ __launch_bounds__(256) void tt_gemm_live_dx_kernel(const LA la, const LB lb, EpDX ep, int N, int64_t K,
+                                                              const int64_t* __restrict__ count_dev, int64_t cap) {
+    const int64_t cnt = tt_live_count(count_dev, cap);
+    if ((int64_t)blockIdx.y * TT_BM >= cnt) return;
+    ep.M = cnt;
+    tt_gemm_tile(la, lb, ep, cnt, N, K, K, nullptr);
+}
+// dW: the points are K.  A chunk (blockIdx.z) at or past the count leaves whole and writes no slab; the last live chunk ends at
+// the count, as the plain form's last chunk ends at P.
+template <class LA, class LB>
+__global__ __launch_bounds__(256) void tt_gemm_live_dw_kernel(const LA la, const LB lb, const EpSlab ep, int64_t M, int N,
+                                                              const int64_t* __restrict__ count_dev, int64_t cap, float* bias_slab) {
+    const int64_t cnt = tt_live_count(count_dev, cap);
+    if ((int64_t)blockIdx.z * TT_KCHUNK >= cnt) return;
+    tt_gemm_tile(la, lb, ep, M, N, cnt, TT_KCHUNK, bias_slab);
 }
 
 // grads[w_off + m*N + n] = sum_z slab[z][m][n] (n < N), grads[b_off + m] = sum_z slab[z][m][N]; z in increasing order
@@ -422,6 +457,178 @@ extern "C" int r2l_teacher_backward(const float* rays_o, const float* rays_d, co
     }
     // layer 0: dW over PE(xyz)
     return tt_weight_grad(cur, T_W, T_W, act(nullptr, T_XYZ, 0, 0), T_XYZ, P, slab, grads, off.w[0], off.b[0], st);
+}
+
+// ------------------------------------------------------------------------------------------------------------------
+// The same backward on the live samples of an index list, the count left on the device (r2l_teacher_backward_live): the chain
+// above with every launch sized for the capacity P and reading count = min(*count_dev, P) itself.  Point p < count is sample
+// idx[p]: the stash of r2l_teacher_mlp_train_live is compact (row p), draw is gathered to [count,4] first, and the encoder operand
+// reads ray idx[p] / S and z[idx[p]].  Every product then runs over rows / chunks 0 .. count - 1 exactly as the plain chain runs
+// over 0 .. P - 1 on the compacted problem, so the two give the same bits.
+// ------------------------------------------------------------------------------------------------------------------
+// LdActB with the encodings read through idx (a number outside [0, cap) reads sample 0 in its place; its draw row is zero)
+struct LdActBLive {
+    const float* act;
+    const float *rays_o, *rays_d, *viewdirs, *z;
+    const int64_t* idx;
+    int64_t cap;
+    int S, nx, w1, nd;
+    __device__ int64_t sample(int64_t p) const {
+        const int64_t n = idx[p];
+        return n >= 0 && n < cap ? n : 0;
+    }
+    __device__ float operator()(int64_t p, int64_t n) const {
+        if (n < nx) {
+            const int64_t s = sample(p), ray = s / S;
+            const int c = (int)n;
+            const int ax = c < 3 ? c : (c - 3) % 3;
+            const float x = rays_o[ray * 3 + ax] + rays_d[ray * 3 + ax] * z[s];  // as the forward: mul / add rounded separately
+            return LdActB::tt_pe(x, c);
+        }
+        n -= nx;
+        if (n < w1) return act[p * w1 + n];
+        n -= w1;
+        const int64_t ray = sample(p) / S;
+        const int c = (int)n;
+        return LdActB::tt_pe(viewdirs[ray * 3 + (c < 3 ? c : (c - 3) % 3)], c);
+    }
+};
+
+// dg[p] = draw[idx[p]] for p < count (zero for a number outside [0, cap)): one thread per float
+__global__ void tt_gather_draw_kernel(const float* __restrict__ draw, const int64_t* __restrict__ idx,
+                                      const int64_t* __restrict__ count_dev, int64_t cap, float* __restrict__ dg) {
+    const int64_t cnt = tt_live_count(count_dev, cap);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt * 4; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t n = idx[i >> 2];
+        dg[i] = n >= 0 && n < cap ? draw[n * 4 + (i & 3)] : 0.f;
+    }
+}
+
+// tt_rgb_head_dx_kernel over the live rows
+__global__ void tt_rgb_head_dx_live_kernel(const float* __restrict__ draw, const float* __restrict__ rgb_w,
+                                           const float* __restrict__ vstash, float* __restrict__ gv,
+                                           const int64_t* __restrict__ count_dev, int64_t cap) {
+    const int64_t cnt = tt_live_count(count_dev, cap);
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < cnt * 128; i += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t p = i >> 7;
+        const int j = (int)(i & 127);
+        const float v = draw[p * 4] * rgb_w[j] + draw[p * 4 + 1] * rgb_w[128 + j] + draw[p * 4 + 2] * rgb_w[256 + j];
+        gv[i] = vstash[i] > 0.f ? v : 0.f;
+    }
+}
+
+// tt_slab_reduce_kernel over the live chunks, in increasing order (none: the gradient is zero)
+__global__ void tt_slab_reduce_live_kernel(const float* __restrict__ slab, const int64_t* __restrict__ count_dev, int64_t cap,
+                                           int64_t M, int N, float* __restrict__ grads, int64_t w_off, int64_t b_off) {
+    const int64_t cnt = tt_live_count(count_dev, cap);
+    const int Z = cnt > 0 ? (int)((cnt + TT_KCHUNK - 1) / TT_KCHUNK) : 0;
+    const int64_t cols = N + 1;
+    for (int64_t i = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; i < M * cols; i += (int64_t)gridDim.x * blockDim.x) {
+        float s = 0.f;
+        for (int zz = 0; zz < Z; ++zz) s += slab[(int64_t)zz * M * cols + i];
+        const int64_t m = i / cols;
+        const int n = (int)(i % cols);
+        if (n < N) grads[w_off + m * N + n] = s;
+        else grads[b_off + m] = s;
+    }
+}
+
+struct TTLive {
+    const int64_t* count_dev;
+    int64_t cap;
+};
+
+static int tt_weight_grad_live(const float* G, int ldg, int64_t M, const LdActBLive& b, int N, const TTLive& lv, float* slab,
+                               float* grads, int64_t w_off, int64_t b_off, hipStream_t st) {
+    const int64_t nz = (lv.cap + TT_KCHUNK - 1) / TT_KCHUNK;  // (< 65536: checked by the entry point)
+    const dim3 grid((unsigned)((N + TT_BN - 1) / TT_BN), (unsigned)((M + TT_BM - 1) / TT_BM), (unsigned)nz);
+    hipLaunchKernelGGL((tt_gemm_live_dw_kernel<LdTransA, LdActBLive>), grid, dim3(256), 0, st, LdTransA{G, ldg}, b,
+                       EpSlab{slab, M, N}, M, N, lv.count_dev, lv.cap, slab);
+    R2L_CHECK(hipGetLastError());
+    const int64_t n = M * (N + 1);
+    hipLaunchKernelGGL(tt_slab_reduce_live_kernel, dim3((unsigned)((n + 255) / 256)), dim3(256), 0, st, slab, lv.count_dev, lv.cap, M, N,
+                       grads, w_off, b_off);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+static int tt_dx_live(const float* G, int ldg, int Kout, const float* w, int ldw, int col0, int N, float* out, const float* mask,
+                      const float* r1a, const float* r1b, const TTLive& lv, hipStream_t st) {
+    const EpDX ep{out, N, mask, N, r1a, r1b, lv.cap, N};  // (.M: the kernel puts the count there)
+    const dim3 grid((unsigned)((N + TT_BN - 1) / TT_BN), (unsigned)((lv.cap + TT_BM - 1) / TT_BM), 1);
+    hipLaunchKernelGGL((tt_gemm_live_dx_kernel<LdRowA, LdWeightB>), grid, dim3(256), 0, st, LdRowA{G, ldg}, LdWeightB{w, ldw, col0}, ep,
+                       N, (int64_t)Kout, lv.count_dev, lv.cap);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t r2l_teacher_train_live_work_floats(int64_t P) {
+    if (P < 0) return -1;
+    return r2l_teacher_train_work_floats(P) + 4 * P;  // r2l_teacher_backward's, then the gathered draw [P,4]
+}
+
+extern "C" int r2l_teacher_backward_live(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                         const int64_t* idx, const int64_t* count_dev, const float* tparams, const float* stash,
+                                         const float* draw, float* grads, float* work, int64_t R, int S, void* stream) {
+    R2L_REQUIRE(R >= 0, "r2l_teacher_backward_live: R is negative");
+    R2L_REQUIRE(S >= 1, "r2l_teacher_backward_live: S: need S >= 1");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < (int64_t)65535 * TT_BM,
+                "r2l_teacher_backward_live: R*S: too many points for one call (need R*S < 65535 * 128)");
+    R2L_REQUIRE(grads != nullptr, "r2l_teacher_backward_live: grads is NULL");
+    const TOff off = t_offsets();
+    const int64_t P = R * (int64_t)S;
+    const hipStream_t st = (hipStream_t)stream;
+    if (P == 0) {  // no points: every gradient is zero
+        R2L_CHECK(hipMemsetAsync(grads, 0, sizeof(float) * off.total, st));
+        return 0;
+    }
+    R2L_REQUIRE(rays_o != nullptr, "r2l_teacher_backward_live: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_teacher_backward_live: rays_d is NULL");
+    R2L_REQUIRE(viewdirs != nullptr, "r2l_teacher_backward_live: viewdirs is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_teacher_backward_live: z is NULL");
+    R2L_REQUIRE(idx != nullptr, "r2l_teacher_backward_live: idx is NULL");
+    R2L_REQUIRE(count_dev != nullptr, "r2l_teacher_backward_live: count_dev is NULL");
+    R2L_REQUIRE(tparams != nullptr, "r2l_teacher_backward_live: tparams is NULL");
+    R2L_REQUIRE(stash != nullptr, "r2l_teacher_backward_live: stash is NULL");
+    R2L_REQUIRE(draw != nullptr, "r2l_teacher_backward_live: draw is NULL");
+    R2L_REQUIRE(work != nullptr, "r2l_teacher_backward_live: work is NULL");
+    const float* W = tparams;
+    float* ga = work;
+    float* gb = ga + P * T_W;
+    float* gv = gb + P * T_W;
+    float* slab = gv + P * T_VIEWS;
+    float* dg = slab + tt_slab_floats(P);
+    const TTLive lv{count_dev, P};
+    auto slot = [&](int l) { return T_STASH_SLOT(stash, (int64_t)l, P); };  // compact rows, the slots where a stash of P points has them
+    const float* vst = slot(T_STASH_VIEWS);
+    auto act = [&](const float* a, int nx, int w1, int nd) { return LdActBLive{a, rays_o, rays_d, viewdirs, z, idx, P, S, nx, w1, nd}; };
+    const unsigned nblk = (unsigned)((P * T_VIEWS + 255) / 256 < 65536 ? (P * T_VIEWS + 255) / 256 : 65536);
+    int rc;
+    hipLaunchKernelGGL(tt_gather_draw_kernel, dim3((unsigned)((P * 4 + 255) / 256 < 65536 ? (P * 4 + 255) / 256 : 65536)), dim3(256), 0, st,
+                       draw, idx, count_dev, P, dg);
+    R2L_CHECK(hipGetLastError());
+    // from here on: r2l_teacher_backward's sequence with draw = dg and the live launches
+    if ((rc = tt_weight_grad_live(dg, 4, 3, act(vst, 0, T_VIEWS, 0), T_VIEWS, lv, slab, grads, off.rgb_w, off.rgb_b, st))) return rc;
+    if ((rc = tt_weight_grad_live(dg + 3, 4, 1, act(slot(7), 0, T_W, 0), T_W, lv, slab, grads, off.alpha_w, off.alpha_b, st))) return rc;
+    hipLaunchKernelGGL(tt_rgb_head_dx_live_kernel, dim3(nblk), dim3(256), 0, st, dg, W + off.rgb_w, vst, gv, count_dev, P);
+    R2L_CHECK(hipGetLastError());
+    if ((rc = tt_weight_grad_live(gv, T_VIEWS, T_VIEWS, act(slot(T_STASH_FEAT), 0, T_W, T_DIR), T_W + T_DIR, lv, slab, grads,
+                                  off.views_w, off.views_b, st)))
+        return rc;
+    if ((rc = tt_dx_live(gv, T_VIEWS, T_VIEWS, W + off.views_w, T_W + T_DIR, 0, T_W, ga, nullptr, nullptr, nullptr, lv, st))) return rc;
+    if ((rc = tt_weight_grad_live(ga, T_W, T_W, act(slot(7), 0, T_W, 0), T_W, lv, slab, grads, off.feat_w, off.feat_b, st))) return rc;
+    if ((rc = tt_dx_live(ga, T_W, T_W, W + off.feat_w, T_W, 0, T_W, gb, slot(7), dg + 3, W + off.alpha_w, lv, st))) return rc;
+    float* cur = gb;
+    float* nxt = ga;
+    for (int l = 7; l >= 1; --l) {
+        const int nx = l == 5 ? T_XYZ : 0;
+        const int fin = nx + T_W;
+        if ((rc = tt_weight_grad_live(cur, T_W, T_W, act(slot(l - 1), nx, T_W, 0), fin, lv, slab, grads, off.w[l], off.b[l], st)))
+            return rc;
+        if ((rc = tt_dx_live(cur, T_W, T_W, W + off.w[l], fin, nx, T_W, nxt, slot(l - 1), nullptr, nullptr, lv, st))) return rc;
+        float* t = cur; cur = nxt; nxt = t;
+    }
+    return tt_weight_grad_live(cur, T_W, T_W, act(nullptr, T_XYZ, 0, 0), T_XYZ, lv, slab, grads, off.w[0], off.b[0], st);
 }
 
 // ------------------------------------------------------------------------------------------------------------------

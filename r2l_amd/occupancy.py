@@ -14,6 +14,10 @@ Inside the fused frames call (render_frames(occupancy=pair), --r2l_occ_fused) th
     index (r2l_occ_index: compact's idx and count, no row copies) -> TeacherEngine.mlp_live on the index list (the kernels' live
     form reads the count itself and writes raw in place) -> the unchanged raw2outputs / sample_pdf_sort.
 
+While the teacher trains (TeacherTrainer(occupancy=pair), --r2l_occ_train) the same index list serves the forward with stash and
+the backward (r2l_teacher_mlp_train_live, r2l_teacher_backward_live); TrainOccupancy below holds the driver's refresh rule, and
+OccupancyGrid.rebuild refills a grid in place.
+
 build_spec / compact_spec / scatter_spec restate the three library calls in numpy: they are what CPU tensors run, and what
 the tests hold the kernels to bit for bit.
 """
@@ -153,8 +157,9 @@ class OccupancyGrid:
     pair of built grids as occupancy=(grid_for_network_fn, grid_for_network_fine).  live_points / total_points count what the
     renders since reset_counters() sent to the network and what they would have sent without the grid."""
 
-    def __init__(self, lo, hi, G=128, k=2, dilate=1, sigma_thresh=0.0):
+    def __init__(self, lo, hi, G=128, k=2, dilate=1, sigma_thresh=0.0, precision=None):
         self.G, self.k, self.dilate, self.sigma_thresh = int(G), int(k), int(dilate), float(sigma_thresh)
+        self.precision = precision  # None: the engine's kernel family; else that of _lib.PRECISION (the training grids: fp32_mfma)
         if self.dilate < 0:
             raise ValueError("occupancy grid: dilate must be >= 0")
         self.lo, self.inv, self.step = grid_fields(lo, hi, G, k)
@@ -205,6 +210,11 @@ class OccupancyGrid:
             self._desc = d
         return self._desc
 
+    def _cfg(self, eng):
+        """The r2l_config of this grid's r2l_occ_build: the engine's, or the grid's own precision."""
+        from . import engine as _engine
+        return _lib.make_config(precision=self.precision) if self.precision else _engine.merged_config(eng.cfg)
+
     # -- build ------------------------------------------------------------------------------------------------
     def build(self, net, keep_sigma=False):
         """Fill the bits from `net` (a NeRF module).  GPU parameters: r2l_occ_build through teacher_engine(net) — its packed
@@ -224,7 +234,7 @@ class OccupancyGrid:
                 work = torch.empty(lib.r2l_occ_build_work_floats(self.G, self.k), dtype=torch.float32, device=dev)
                 sig = torch.empty(n_probe, dtype=torch.float32, device=dev) if keep_sigma else None
                 _lib.check(lib.r2l_occ_build(ctypes.byref(self.desc()), self.k, self.dilate, self.sigma_thresh, _ptr(eng.wstream),
-                                             _ptr(eng.flat), ctypes.byref(_engine.merged_config(eng.cfg)), _ptr(work), _ptr(sig),
+                                             _ptr(eng.flat), ctypes.byref(self._cfg(eng)), _ptr(work), _ptr(sig),
                                              _stream()), "r2l_occ_build")
                 torch.cuda.synchronize(dev)  # (work is released here; the build is timed)
             self.sigma = sig
@@ -236,6 +246,41 @@ class OccupancyGrid:
                 sig = torch.cat([net(torch.cat([e_x(p), view.expand(p.shape[0], -1)], -1))[:, 3] for p in pts.split(65536)])
             self.set_bits(build_spec(sig.numpy(), self.G, self.k, self.dilate, self.sigma_thresh))
             self.sigma = sig if keep_sigma else None
+        self.build_seconds = time.time() - t0
+        return self
+
+    def rebuild(self, net):
+        """Refill the bits IN PLACE from `net` (the refresh of a grid while its teacher trains): the grid keeps its bits tensor,
+        its descriptor and — on the GPU — the work buffer of its first rebuild, so whoever holds the descriptor (a trainer) sees the
+        new bits with nothing to re-wire.  Synchronises (the rebuild is timed; it is off the per-step path).  A grid that was
+        never built is built."""
+        if self.bits is None:
+            return self.build(net)
+        from . import engine as _engine
+        from .render import teacher_engine
+        dev = next(net.parameters()).device
+        if dev != self.bits.device:
+            raise ValueError("occupancy grid: built on %s, the net is on %s" % (self.bits.device, dev))
+        t0 = time.time()
+        if dev.type == "cuda":
+            eng = teacher_engine(net)
+            lib = _lib.load()
+            with torch.cuda.device(dev):
+                eng.ensure_packed()
+                work = self._buf.get("build_work")
+                if work is None:
+                    work = self._buf["build_work"] = torch.empty(lib.r2l_occ_build_work_floats(self.G, self.k), dtype=torch.float32,
+                                                                 device=dev)
+                _lib.check(lib.r2l_occ_build(ctypes.byref(self.desc()), self.k, self.dilate, self.sigma_thresh, _ptr(eng.wstream),
+                                             _ptr(eng.flat), ctypes.byref(self._cfg(eng)), _ptr(work), None, _stream()),
+                           "r2l_occ_build")
+                torch.cuda.synchronize(dev)
+        else:
+            bits, desc = self.bits, self._desc
+            self.build(net)  # (makes a new tensor) ...
+            bits.copy_(self.bits)  # ... whose words go into the old one
+            self.bits, self._desc = bits, desc
+        self.sigma = None
         self.build_seconds = time.time() - t0
         return self
 
@@ -419,3 +464,88 @@ def log_live(pair, logger):
     a, b = sum(g.live_points for g in seen), sum(g.total_points for g in seen)
     logger.info("occupancy grid: live points %d / %d (%.1f%%)" % (a, b, 100. * a / max(b, 1)))
     return a, b
+
+
+def popcount_words(w):
+    """Number of set bits of an int32 word tensor (plain torch ops; the arithmetic shift's sign copies fall to the & 1)."""
+    return int(sum(((w >> s) & 1).sum() for s in range(32)))
+
+
+class TrainOccupancy:
+    """The grids of a teacher-training run with --r2l_occ_train (utils/train_nerf.py): one per net, built with sigma threshold 0 and
+    one cell of dilation by the exact-fp32 kernels — the trainer's family —, handed to TeacherTrainer.set_occupancy and refreshed IN
+    PLACE every --r2l_occ_every iterations.  The grids in force in iteration i are built from the weights as they stand after
+    iteration options.occ_refresh_base(i, K); a checkpoint of iteration i carries the grids in force in iteration i + 1 (state(),
+    under KEY), so that --resume repeats the uninterrupted run.  The trainer's device counters are read at each refresh only."""
+    KEY = "r2l_occ_train"
+
+    def __init__(self, args, coarse, fine, near, far, trainer, logger, start=0, state=None):
+        from .options import occ_refresh_base
+        self.K, self.bound, self.trainer, self.logger = int(args.r2l_occ_every), box_half_side(args, near, far), trainer, logger
+        self.nets = [coarse] + ([fine] if fine is not None and len(trainer.nets) > 1 else [])
+        b = self.bound
+        self.grids = [OccupancyGrid([-b] * 3, [b] * 3, G=args.r2l_occ_res, k=2, dilate=1, sigma_thresh=0., precision="fp32_mfma")
+                      for _ in self.nets]
+        self.base = occ_refresh_base(start + 1, self.K)
+        dev = next(coarse.parameters()).device
+        why = self._mismatch(state)
+        if why is None:
+            for g, w in zip(self.grids, state["words"]):
+                g.set_bits(w.cpu().numpy().view(np.uint32), device=dev)
+            logger.info("occupancy grids of the training step: restored from the checkpoint (built from the weights after iteration "
+                        "%d; %d^3 cells over +-%.3g, refreshed every %d iterations)" % (self.base, self.grids[0].G, b, self.K))
+        else:
+            if start > 0:
+                logger.info("occupancy grids of the training step: %s — rebuilt at once from the checkpoint's weights (iteration %d), "
+                            "where the uninterrupted run's were built after iteration %d" % (why, start, self.base))
+                self.base = start
+            for name, g, net in zip(("coarse", "fine"), self.grids, self.nets):
+                g.build(net)
+                logger.info("occupancy grid of the training step (%s net): %d^3 cells over +-%.3g, %d probes per cell and axis, "
+                            "dilation %d, exact fp32: built in %.3fs, %.1f%% of the cells occupied; refreshed every %d iterations"
+                            % (name, g.G, b, g.k, g.dilate, g.build_seconds, 100. * g.occupied_share(), self.K))
+        trainer.set_occupancy(self.pair())
+        if trainer.live_acc is not None:
+            trainer.live_acc.zero_()
+
+    def pair(self):
+        return (self.grids[0], self.grids[-1])
+
+    def _mismatch(self, state):
+        """Why a checkpoint's grids cannot serve this run, or None."""
+        if state is None:
+            return "the checkpoint has no key %r" % self.KEY
+        g = self.grids[0]
+        want = {"res": g.G, "bound": self.bound, "k": g.k, "dilate": g.dilate, "every": self.K, "base": self.base, "n": len(self.grids)}
+        for k, v in want.items():
+            if state.get(k) != v:
+                return "the checkpoint's grids have %s = %r, this run %r" % (k, state.get(k), v)
+        return None
+
+    def state(self):
+        """The checkpoint entry: the fields the grids were made with, the iteration whose weights they were built from, the words."""
+        g = self.grids[0]
+        return {"res": g.G, "bound": self.bound, "k": g.k, "dilate": g.dilate, "every": self.K, "base": self.base, "n": len(self.grids),
+                "words": [x.bits.detach().cpu().clone() for x in self.grids]}
+
+    def after_step(self, i):
+        """Called when iteration i is done: refresh when the next iteration begins a window."""
+        if i % self.K == 0:
+            self.refresh(i)
+
+    def refresh(self, i):
+        a, b = (int(x) for x in self.trainer.live_acc.tolist())  # the one read of the window's counters
+        self.trainer.live_acc.zero_()
+        secs, share, new = [], [], 0
+        for g, net in zip(self.grids, self.nets):
+            old = g.bits.clone()
+            g.rebuild(net)
+            new += popcount_words(g.bits & ~old)
+            secs.append(g.build_seconds)
+            share.append(100. * g.occupied_share())
+        self.base = i
+        self.logger.info("occupancy grid refresh after iteration %d: built in %s s, %s %% of the cells occupied, live points %d / %d "
+                         "(%.1f%%) in the window, %d cells set now that were clear in the outgoing grids"
+                         % (i, " + ".join("%.3f" % s for s in secs), " / ".join("%.1f" % s for s in share), a, b,
+                            100. * a / max(b, 1), new))
+        return a, b, new

@@ -59,13 +59,22 @@ FLAGS = {
     # axis; r2l_occ_bound: half side of the cube about the origin, 0 = 0.625 (far - near), 2.5 for the Blender scenes.  Honoured by
     # utils/create_data.py --create_data rand, --test_teacher and main.py --model_name nerf --render_only; not with
     # --r2l_fused_frames / --r2l_online_kd (the frames call has no host read of the live count), --dataset_type llff (NDC space
-    # needs its own box) or raw_noise_std > 0.  utils/train_nerf.py and student training ignore the three
+    # needs its own box) or raw_noise_std > 0.  utils/train_nerf.py (but for r2l_occ_train below, which shares r2l_occ_res and
+    # r2l_occ_bound) and student training ignore the three
     "r2l_occupancy": ("flag", False), "r2l_occ_res": (int, 128), "r2l_occ_bound": (float, 0.),
     # the same grids inside the FUSED frames call (r2l_teacher_frames_occ_cfg: the live count stays on the device, nothing is
     # read on the host): utils/create_data.py --create_data rand with --r2l_fused_frames or --r2l_store_save, --test_teacher and
     # main.py --model_name nerf --render_only with --r2l_fused_frames, main.py --r2l_online_kd.  Shares r2l_occ_res / r2l_occ_bound;
     # not together with --r2l_occupancy (the per-pose path), nor with llff or raw_noise_std > 0.  utils/train_nerf.py ignores it
     "r2l_occ_fused": ("flag", False),
+    # the grids while the teacher TRAINS (utils/train_nerf.py only; r2l_teacher_mlp_train_live / r2l_teacher_backward_live /
+    # r2l_teacher_train_step_occ): forward and backward of every step run on the live samples, the live counts stay on the device.
+    # Shares r2l_occ_res / r2l_occ_bound; r2l_occ_every: a refresh of both grids from the current weights every so many iterations
+    # (sigma threshold 0, one cell of dilation, the exact-fp32 kernels; 512: the smallest power of two at which two rebuilds of 128^3
+    # cells cost at most 2 % of as many lego-size steps, profiles/teacher_occ_train.txt).  GPU only; not with llff or raw_noise_std > 0;
+    # opt-in.
+    # main.py / create_data.py ignore both
+    "r2l_occ_train": ("flag", False), "r2l_occ_every": (int, 512),
     # device-resident ray store (r2l_amd/raystore.py): training draws its shards from HBM with one launch per step.
     # r2l_device_store: the shard files of --datadir_kd are read once into the store.  r2l_online_kd: no files at all, the
     # teacher (--teacher_ckpt, described by the config file --r2l_teacher_config) renders --n_pose_kd poses into the store, all
@@ -298,6 +307,42 @@ def validate_occupancy(args, raw_noise_std=None):
         raise ValueError("--r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
     if not args.use_viewdirs:
         raise ValueError("--r2l_occupancy needs --use_viewdirs (the teacher kernels' network)")
+
+
+OCC_EVERY_MAX = 1 << 30
+
+
+def validate_occ_train(args, device_type=None):
+    """--r2l_occ_train (utils/train_nerf.py only; the sibling entry points accept and ignore it): the occupancy grids inside the
+    teacher's training step.  Names what is wrong before anything is loaded; device_type: where the run is, once known (the switch
+    has no CPU form: a CPU run with it is refused, not trained without it)."""
+    if not args.r2l_occ_train:
+        return
+    if args.raw_noise_std > 0:
+        raise ValueError("--r2l_occ_train with raw_noise_std > 0: noise can lift a skipped sample above zero, and its gradient "
+                         "with it (pass --raw_noise_std 0)")
+    if args.dataset_type == "llff":
+        raise ValueError("--r2l_occ_train puts its box about the origin of a bounded scene: not with --dataset_type llff (NDC "
+                         "space needs a box of its own)")
+    if not args.use_viewdirs:
+        raise ValueError("--r2l_occ_train needs a teacher with --use_viewdirs (the teacher kernels' network)")
+    if not 1 <= args.r2l_occ_res <= 512:
+        raise ValueError("--r2l_occ_train: --r2l_occ_res must be in 1 .. 512, got %d" % args.r2l_occ_res)
+    if args.r2l_occ_bound < 0:
+        raise ValueError("--r2l_occ_train: --r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
+    if not 1 <= args.r2l_occ_every <= OCC_EVERY_MAX:
+        raise ValueError("--r2l_occ_train: --r2l_occ_every must be in 1 .. 2^30 iterations, got %d" % args.r2l_occ_every)
+    if device_type is not None and device_type != "cuda":
+        raise ValueError("--r2l_occ_train runs the live kernels of libr2l_hip.so on a GPU; this run is on the CPU")
+
+
+def occ_refresh_base(i, K):
+    """The iteration whose weights the grids in force in iteration i >= 1 are built from: K * floor((i - 1) / K) — 0 stands for
+    the weights a run starts from (the initial ones, or the checkpoint's for a run that starts there).  Pure: a resumed run and an
+    uninterrupted one ask the same question."""
+    if i < 1 or K < 1:
+        raise ValueError("occ_refresh_base: need i >= 1 and K >= 1, got i = %d, K = %d" % (i, K))
+    return K * ((i - 1) // K)
 
 
 def validate_occ_fused(args, paths, raw_noise_std=None, use_viewdirs=None):

@@ -7,9 +7,15 @@ moments.  On ROCm tensors one step is, in libr2l_hip.so (include/r2l_hip.h, "NeR
   -> fine forward with stash -> raw2outputs backward with the img2mse seed (fine and coarse) -> both backward passes -> Adam.
 On CPU modules the same step is torch autograd over render.render_rays' CPU branch and torch.optim.Adam (plumbing only:
 it lets the host loop be tested without a GPU).
+With a pair of occupancy grids (TeacherTrainer(..., occupancy=pair) / set_occupancy; include/r2l_hip.h "occupancy while the teacher
+trains") each pass runs on its live samples only: r2l_occ_index -> r2l_teacher_mlp_train_live, and r2l_teacher_backward_live on the
+same index list; the live counts stay on the device, so the step gains no synchronisation.  fused_step then is
+r2l_teacher_train_step_occ.  With raw_noise_std = 0 a skipped sample of non-positive sigma contributes exact zeros to the loss and to
+every gradient: the grids change a step by summation order, plus whatever samples of positive sigma a stale grid skips.
 """
 import ctypes
 
+import numpy as np
 import torch
 
 from . import _lib
@@ -22,7 +28,7 @@ MAX_SAMPLES = 256  # r2l_raw2outputs_backward stages one ray's samples in LDS
 
 class TeacherTrainer:
     def __init__(self, coarse, fine=None, N_samples=64, N_importance=128, perturb=1., white_bkgd=True, raw_noise_std=0.,
-                 betas=(0.9, 0.999), eps=1e-8):
+                 betas=(0.9, 0.999), eps=1e-8, occupancy=None):
         self.nets = [coarse] + ([fine] if fine is not None and N_importance > 0 else [])
         if N_importance > 0 and fine is None:
             raise NotImplementedError("N_importance > 0 without a fine network: the reference re-uses network_fn; not supported")
@@ -32,8 +38,10 @@ class TeacherTrainer:
         self.params = [p for net in self.nets for p in net.parameters()]
         self.step_count = 0
         self.on_gpu = self.params[0].is_cuda
+        self.occupancy, self.live_acc = None, None
         if not self.on_gpu:
             self.opt = torch.optim.Adam(self.params, lr=0., betas=self.betas, eps=eps)
+            self.set_occupancy(occupancy)
             return
         S = N_samples + (N_importance if len(self.nets) > 1 else 0)
         if S > MAX_SAMPLES:  # refused here, before a step runs the forward passes the backward would then refuse
@@ -61,6 +69,27 @@ class TeacherTrainer:
         self.exp_avg_sq = torch.zeros_like(self.grads)
         self.loss_out = torch.zeros(2, dtype=torch.float32, device=dev)
         self._bufs = {}
+        self.live_acc = torch.zeros(2, dtype=torch.int64, device=dev)  # += (live samples, all samples) of every pass with grids
+        self.set_occupancy(occupancy)
+
+    def set_occupancy(self, pair):
+        """pair: None (every sample goes through the network, the step as it always was), or (grid_coarse, grid_fine), two built
+        r2l_amd.occupancy.OccupancyGrid on the trainer's device (the same grid twice is fine).  From the next step on each pass
+        runs on its grid's live samples.  The grids stay the caller's: OccupancyGrid.rebuild(net) refreshes one in place."""
+        if pair is None:
+            self.occupancy = None
+            return
+        if self.raw_noise_std > 0.:
+            raise ValueError("TeacherTrainer: occupancy with raw_noise_std > 0 — noise can lift a skipped sample above zero")
+        pair = tuple(pair)
+        if len(pair) != 2:
+            raise ValueError("TeacherTrainer: occupancy is a pair of grids (coarse, fine)")
+        dev = self.params[0].device
+        for g in pair:
+            g._need_built()
+            if g.bits.device != dev:
+                raise ValueError("TeacherTrainer: occupancy grid built on %s, the teacher is on %s" % (g.bits.device, dev))
+        self.occupancy = pair
 
     # ---- device buffers, grown on demand ------------------------------------------------------------------------------
     def _buf(self, name, n):
@@ -75,12 +104,35 @@ class TeacherTrainer:
             return None
         return torch.randn(R, S, device=self.flat.device) * self.raw_noise_std
 
+    def _index(self, i, rays_o, rays_d, z):
+        """(idx, count) of pass i's live samples in buffers of the trainer's own (the coarse list is still needed when the fine one
+        is made): r2l_occ_index, then live_acc += (count, R*S).  Nothing is read on the host."""
+        R, S = z.shape
+        n = max(R * S, 1)
+        b = self._bufs.get("occ%d" % i)
+        if b is None or b[0].numel() < n:
+            dev = self.flat.device
+            b = self._bufs["occ%d" % i] = (torch.empty(n, dtype=torch.int64, device=dev), torch.zeros(1, dtype=torch.int64, device=dev),
+                                           torch.empty(max(self.lib.r2l_occ_index_work_bytes(n), 16), dtype=torch.uint8, device=dev))
+        idx, count, work = b
+        grid = self.occupancy[i]
+        _lib.check(self.lib.r2l_occ_index(ctypes.byref(grid.desc()), _ptr(rays_o), _ptr(rays_d), _ptr(z), R, S, _ptr(idx), _ptr(count),
+                                          _ptr(work), _stream()), "r2l_occ_index")
+        _lib.check(self.lib.r2l_occ_live_add(_ptr(count), R * S, _ptr(self.live_acc), _stream()), "r2l_occ_live_add")
+        return idx, count
+
     def _forward(self, i, rays_o, rays_d, viewdirs, z):
         eng = self.engines[i]
         eng.ensure_packed()
         R, S = z.shape
         raw = torch.empty(R, S, 4, dtype=torch.float32, device=z.device)
         stash = self._buf("stash%d" % i, self.lib.r2l_teacher_stash_floats(R * S))
+        if self.occupancy is not None:
+            idx, count = self._live[i] = self._index(i, rays_o, rays_d, z)
+            _lib.check(self.lib.r2l_teacher_mlp_train_live(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(idx), _ptr(count),
+                                                           _ptr(eng.wstream), _ptr(eng.flat), _ptr(raw), _ptr(stash), R, S, _stream()),
+                       "r2l_teacher_mlp_train_live")
+            return raw, stash
         _lib.check(self.lib.r2l_teacher_mlp_train(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(eng.wstream),
                                                   _ptr(eng.flat), _ptr(raw), _ptr(stash), R, S, _stream()),
                    "r2l_teacher_mlp_train")
@@ -93,8 +145,17 @@ class TeacherTrainer:
         _lib.check(self.lib.r2l_raw2outputs_backward(_ptr(raw), _ptr(z), _ptr(rays_d), _ptr(noise), int(self.white_bkgd),
                                                      _ptr(target), _ptr(draw), _ptr(sqerr), R, S, _stream()),
                    "r2l_raw2outputs_backward")
-        work = self._buf("work", self.lib.r2l_teacher_train_work_floats(R * S))
         g = self.grads[i * self.n_net:(i + 1) * self.n_net]
+        if self.occupancy is not None:
+            idx, count = self._live[i]
+            work = self._buf("work", self.lib.r2l_teacher_train_live_work_floats(R * S))
+            _lib.check(self.lib.r2l_teacher_backward_live(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(idx), _ptr(count),
+                                                          _ptr(self.engines[i].flat), _ptr(stash), _ptr(draw), _ptr(g), _ptr(work), R, S,
+                                                          _stream()), "r2l_teacher_backward_live")
+            out = self._buf("mse%d" % i, 2)
+            _lib.check(self.lib.r2l_loss_finish(_ptr(sqerr), R, 1. / (3 * R), _ptr(out), _stream()), "r2l_loss_finish")
+            return out
+        work = self._buf("work", self.lib.r2l_teacher_train_work_floats(R * S))
         _lib.check(self.lib.r2l_teacher_backward(_ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(z), _ptr(self.engines[i].flat),
                                                  _ptr(stash), _ptr(draw), _ptr(g), _ptr(work), R, S, _stream()),
                    "r2l_teacher_backward")
@@ -114,6 +175,7 @@ class TeacherTrainer:
         far = torch.as_tensor(far, **f32).expand(R, 1).contiguous()
         z = render._coarse_z(near, far, self.N_samples, False, self.perturb, False, t_rand)
         noise_c = self._noise(R, self.N_samples)
+        self._live = {}  # with grids: pass -> (idx, count) of this step, device tensors
         raw_c, stash_c = self._forward(0, rays_o, rays_d, viewdirs, z)
         outs = []
         self.last_z = [z]  # the sample depths of this step (coarse, fine): what a test needs to restate it
@@ -165,9 +227,11 @@ class TeacherTrainer:
                                     raw_noise_std=self.raw_noise_std, near=float(near), far=float(far), lr=float(lr),
                                     beta1=self.betas[0], beta2=self.betas[1], eps=self.eps, step=int(step),
                                     seed=int(seed) & (2**64 - 1))
-        n_work = self.lib.r2l_teacher_step_work_floats(ctypes.byref(desc))
+        occ = self.occupancy
+        size_fn = "r2l_teacher_step_work_floats" if occ is None else "r2l_teacher_step_occ_work_floats"
+        n_work = getattr(self.lib, size_fn)(ctypes.byref(desc))
         if n_work < 0:
-            _lib.check(1, "r2l_teacher_step_work_floats")
+            _lib.check(1, size_fn)
         work = self._buf("step_work", n_work)
         tabs = self._bufs.get("step_tabs")
         if tabs is None:  # the tables of _coarse_z and sample_pdf_sort, by the same torch expressions
@@ -178,11 +242,15 @@ class TeacherTrainer:
             loss_out = self.loss_out
         if loss_out.dtype != torch.float32 or loss_out.numel() != 2 or not loss_out.is_contiguous() or loss_out.device != self.flat.device:
             raise ValueError("fused_step: loss_out is a contiguous fp32 tensor of 2 elements on the trainer's device")
-        _lib.check(self.lib.r2l_teacher_train_step(ctypes.byref(desc), _ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(target),
-                                                   _ptr(tabs[0]), _ptr(tabs[1]), _ptr(self.flat), _ptr(self.grads), _ptr(self.exp_avg),
-                                                   _ptr(self.exp_avg_sq), _ptr(self.engines[0].wstream),
-                                                   _ptr(self.engines[1].wstream if fine else None), _ptr(loss_out), _ptr(work),
-                                                   _stream()), "r2l_teacher_train_step")
+        head = (ctypes.byref(desc), _ptr(rays_o), _ptr(rays_d), _ptr(viewdirs), _ptr(target), _ptr(tabs[0]), _ptr(tabs[1]),
+                _ptr(self.flat), _ptr(self.grads), _ptr(self.exp_avg), _ptr(self.exp_avg_sq), _ptr(self.engines[0].wstream),
+                _ptr(self.engines[1].wstream if fine else None), _ptr(loss_out))
+        if occ is None:
+            _lib.check(self.lib.r2l_teacher_train_step(*head, _ptr(work), _stream()), "r2l_teacher_train_step")
+        else:  # the same arguments, then the pass's grids and the device counters
+            _lib.check(self.lib.r2l_teacher_train_step_occ(*head, ctypes.byref(occ[0].desc()),
+                                                           ctypes.byref(occ[1].desc()) if fine and occ[1] is not occ[0] else None,
+                                                           _ptr(self.live_acc), _ptr(work), _stream()), "r2l_teacher_train_step_occ")
         # the call re-packed both streams from the weights it wrote in place: the engines' version stamps (taken by ensure_packed
         # above; a kernel bumps no tensor version) stay valid, nothing re-packs before the next launch
         self.step_count = int(step)
@@ -192,8 +260,18 @@ class TeacherTrainer:
         R = rays_o.shape[0]
         ones = torch.ones(R, 1)
         batch = torch.cat([rays_o, rays_d, near * ones, far * ones, viewdirs], -1).float()
-        qfn = lambda inputs, vd, fn: render.run_network(inputs, vd, fn, embed_fn=render.get_embedder(10)[0],
-                                                        embeddirs_fn=render.get_embedder(4)[0])
+        qfn0 = lambda inputs, vd, fn: render.run_network(inputs, vd, fn, embed_fn=render.get_embedder(10)[0],
+                                                         embeddirs_fn=render.get_embedder(4)[0])
+        qfn = qfn0
+        if self.occupancy is not None:
+            from .occupancy import live_spec
+
+            def qfn(inputs, vd, fn):  # raw of the samples that are not live in the pass's grid is zero, as OccupancyGrid.query leaves it
+                g = self.occupancy[0 if fn is self.nets[0] else 1]
+                live = live_spec(g.words(), g.lo, g.inv, g.G, inputs.detach().numpy().reshape(-1, 3))
+                g.live_points += int(live.sum())
+                g.total_points += int(live.size)
+                return qfn0(inputs, vd, fn) * torch.from_numpy(live.astype(np.float32)).reshape(*inputs.shape[:-1], 1)
         fine = self.nets[1] if len(self.nets) > 1 else None
         ret = render.render_rays(batch, self.nets[0], qfn, self.N_samples, perturb=self.perturb,
                                  N_importance=self.N_importance, network_fine=fine, white_bkgd=self.white_bkgd,

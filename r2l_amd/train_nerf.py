@@ -22,6 +22,11 @@ one r2l_image_batch launch in place of sample_batch, device_rays and four copies
 bijection's, not numpy's; the distribution is the reference's.  An N_rand above the crop's (or the frame's) pixel count is refused
 at start-up, where the reference would fail inside numpy at the first iteration.  With --r2l_fused_step no host generator is left
 in the loop, the re-seeding is skipped, and --resume is exact with no sampler state; the staged step keeps it for torch's draws.
+With --r2l_occ_train (GPU only, raw_noise_std 0) forward and backward of every step run on the samples that are live in an occupancy grid
+per net (r2l_amd/occupancy.py TrainOccupancy; TeacherTrainer.set_occupancy): the grids in force in iteration i are built from the
+weights after iteration K * floor((i - 1) / K), K = --r2l_occ_every, and every checkpoint carries them under a key of its own
+('r2l_occ_train', which the reference's loaders never read), so that --resume repeats the uninterrupted run — bit for bit under
+--r2l_fused_step --r2l_image_sampler.
 Checkpoints are the reference's layout (checkpoint.save_ckpt, model_name='nerf'): utils/create_data.py --teacher_ckpt and
 main.py --model_name nerf --render_only read them unchanged.
 """
@@ -36,7 +41,8 @@ from .checkpoint import load_ckpt, save_ckpt
 from .driver import lpips_field, apply_arithmetic, create_nerf_teacher, init_distributed, load_lpips_vgg_weights, load_lpips_weights, render_path
 from .image_batch import ImageBatcher, crop_window, full_window
 from .logger import Logger
-from .options import parse_args, validate_accelerated
+from .occupancy import TrainOccupancy
+from .options import parse_args, validate_accelerated, validate_occ_train
 from .pixel_batch import PixelBatcher
 from .render import get_rays, ndc_rays
 from .teacher_train import MAX_SAMPLES, TeacherTrainer
@@ -112,8 +118,10 @@ def _seed(i):
 def main(argv=None):
     args = parse_args(argv)
     args.model_name = "nerf"
+    validate_occ_train(args, None)  # (the switch's own refusals first: they name it; the device is checked below)
     validate_teacher_training(args)
     rank, world, device = init_distributed()
+    validate_occ_train(args, device.type)
     if args.r2l_fused_step and device.type != "cuda":
         raise NotImplementedError("--r2l_fused_step runs on the GPU only (r2l_teacher_train_step of libr2l_hip.so); this run is on "
                                   "device '%s'" % device)
@@ -140,18 +148,24 @@ def main(argv=None):
     trainer = TeacherTrainer(coarse, fine, N_samples=args.N_samples, N_importance=args.N_importance, perturb=args.perturb,
                              white_bkgd=args.white_bkgd, raw_noise_std=args.raw_noise_std)
     start, best_psnr, best_psnr_step = 0, 0., 0
+    occ_state = None
     if args.pretrained_ckpt and args.resume:
         ckpt = load_ckpt(args.pretrained_ckpt, map_location=device)
         start = int(ckpt["global_step"])
         best_psnr, best_psnr_step = float(ckpt.get("best_psnr", 0.)), int(ckpt.get("best_psnr_step", 0))
         trainer.load_optimizer_state_dict(ckpt["optimizer_state_dict"])
+        occ_state = ckpt.get(TrainOccupancy.KEY)
         logger.info("Resume from %s at iteration %d" % (args.pretrained_ckpt, start))
     teacher = dict(hwf=(H, W, focal), chunk=args.chunk, render_kwargs=kwargs_test, render_factor=0)
     test_poses, test_images = poses[i_test], images[i_test]
 
+    occ = None
+    if args.r2l_occ_train:
+        occ = TrainOccupancy(args, coarse, fine, near, far, trainer, logger, start=start, state=occ_state)
+
     def save(path, i, lr):
         return save_ckpt(path, i, coarse, trainer.optimizer_state_dict(lr), best_psnr, best_psnr_step, model_name="nerf",
-                         model_fine=fine, r2l_config=r2l_config)
+                         model_fine=fine, r2l_config=r2l_config, extra={TrainOccupancy.KEY: occ.state()} if occ is not None else None)
 
     batcher = None
     if not args.no_batching:  # (validate_teacher_training: only with --r2l_batching)
@@ -219,6 +233,8 @@ def main(argv=None):
         else:
             loss, psnr = trainer.step(rays_o, rays_d, viewdirs, near, far, target, lr)
             history.append((loss, psnr))
+        if occ is not None:
+            occ.after_step(i)  # (before any checkpoint of iteration i: it carries the grids of iteration i + 1)
         if i % args.i_print == 0:
             logger.info("[TRAIN] Iter %d Loss %.4f PSNR %.4f LR %.8f Time %.1fs" % (i, loss, psnr, lr, time.time() - t0))
         if i % args.i_testset == 0 and len(i_test):
@@ -240,4 +256,4 @@ def main(argv=None):
     if fused:
         history = [tuple(row) for row in loss_hist.tolist()]
     return {"trainer": trainer, "logger": logger, "history": history, "coarse": coarse, "fine": fine,
-            "r2l_config": r2l_config, "batcher": batcher, "image_sampler": sampler}
+            "r2l_config": r2l_config, "batcher": batcher, "image_sampler": sampler, "occupancy": occ}

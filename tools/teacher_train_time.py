@@ -28,7 +28,18 @@ The staged step (TeacherTrainer.step: ~25 library calls and torch ops, the loss 
 Images mode's batch from the host (train_nerf._seed + sample_batch + device_rays + two copies, what the loop does without the
 switch) against ImageBatcher.next (--r2l_image_sampler), at 400 x 400 (100 views) and 800 x 800 (25 views), N_rand 1024: ms per
 batch (whole frame and centre crop; PixelBatcher.next beside it), and ms per whole iteration with the staged and the fused step,
-with and without the switch.  One process, --repeats rounds alternating the paths; [median, max - min] per path."""
+with and without the switch.  One process, --repeats rounds alternating the paths; [median, max - min] per path.
+
+  python tools/teacher_train_time.py --occ [--steps 20] [--warmup 3] [--repeats 3] [--effect_iters 3000] [--out profiles/teacher_occ_train.txt]
+
+The training step on the live samples of occupancy grids (--r2l_occ_train; TeacherTrainer.set_occupancy) against the plain step of the
+same process, on the trained-like pair of tests/teacher_util.py: 1024 rays of scene_rays' camera drawn over its frame, 64 + 128
+samples, perturb 1, lr 0 (the weights and with them the live share stay put), grids of 128^3 cells over +-1.6 and +-2.5 and an
+all-ones grid (the floor of the capacity-sized launches plus r2l_occ_index); staged and fused, --repeats alternating rounds.  Then
+the refresh: OccupancyGrid.rebuild per grid in the exact-fp32 family at 64^3 and 128^3 cells, and the smallest power of two K at
+which two rebuilds cost at most 2 % of K plain steps.  Then (--effect_iters > 0) the effect on a result: the analytic scene of
+tests/teacher_util.py trained from initial weights with and without grids, and a second seed of the plain run for the spread;
+held-out PSNR of each and the newly set cells of every refresh."""
 import argparse
 import json
 import os
@@ -261,6 +272,169 @@ def images(a):
             f.write("\n".join(lines) + "\n")
 
 
+def analytic_views(n, H, W, focal, first, n_ref=256):
+    """(o, d, viewdirs, rgb) of n views of the analytic scene of tests/teacher_util.py on the r = 4 sphere, each [n*H*W,3] on the GPU:
+    the target is the volume render of analytic_targets at n_ref even depths in [2, 6] on white (O.raw2outputs, fp32)."""
+    from r2l_amd.render import get_rays
+    from tests.teacher_util import analytic_targets
+    out = [[], [], [], []]
+    t = torch.linspace(0., 1., n_ref, device="cuda")
+    for k in range(first, first + n):
+        c2w = torch.from_numpy(O.pose_spherical(-180. + 47. * k, -20. - 25. * (k % 3), 4.)[:3, :4])
+        ro, rd = [x.reshape(-1, 3).float().cuda() for x in get_rays(H, W, focal, c2w)]
+        vd = rd / rd.norm(dim=-1, keepdim=True)
+        z = (2. * (1. - t) + 6. * t).expand(ro.shape[0], n_ref)
+        pts = ro[:, None] + rd[:, None] * z[..., None]
+        with torch.device("cuda"):
+            rgb_l, sig = analytic_targets(pts.reshape(-1, 3), vd[:, None].expand(-1, n_ref, 3).reshape(-1, 3))
+            raw = torch.cat([rgb_l, sig[:, None]], -1).view(ro.shape[0], n_ref, 4)
+            rgb = O.raw2outputs(raw, z, rd, None, True)[0]
+        for lst, v in zip(out, (ro, rd, vd, rgb)):
+            lst.append(v)
+    return [torch.cat(v) for v in out]
+
+
+class ListLog:
+    def __init__(self):
+        self.lines = []
+
+    def info(self, *a):
+        self.lines.append(" ".join(str(x) for x in a))
+
+
+def occ(a):
+    import re
+    from r2l_amd import render
+    from r2l_amd.occupancy import OccupancyGrid, TrainOccupancy, pack_bits
+    from r2l_amd.teacher_train import TeacherTrainer
+    from tests.teacher_util import scene_rays, trained_like_pair
+    lines = ["teacher training on the live samples of occupancy grids (TeacherTrainer.set_occupancy; r2l_teacher_mlp_train_live / "
+             "r2l_teacher_backward_live / r2l_teacher_train_step_occ) against the plain step of the same process; trained-like pair, "
+             "%d rays of scene_rays' camera over its frame, 64 + 128 samples, perturb 1, lr 0; %s; steps %d, warmup %d, %d alternating "
+             "rounds; wall-clock ms per step, one synchronisation after the steps of a round"
+             % (a.rays, torch.cuda.get_device_name(0), a.steps, a.warmup, a.repeats)]
+
+    def emit(r):
+        lines.append(json.dumps(r))
+        print(lines[-1], flush=True)
+
+    csd, fsd = trained_like_pair()
+    R = a.rays
+    rb = scene_rays(181 * 181, 0)[torch.randperm(181 * 181, generator=torch.Generator().manual_seed(0))[:R]].cuda()
+    o, d, vd = rb[:, 0:3].contiguous(), rb[:, 3:6].contiguous(), rb[:, 8:11].contiguous()
+    tgt = torch.rand(R, 3, generator=torch.Generator().manual_seed(1)).cuda()
+    tr = TeacherTrainer(make(csd), make(fsd), perturb=1., white_bkgd=True)
+    hist = torch.zeros(a.warmup + a.steps, 2, device="cuda")
+    it = [0]
+
+    def fused_step():
+        it[0] += 1
+        tr.fused_step(o, d, vd, 2., 6., tgt, 0., step=it[0], seed=0, loss_out=hist[it[0] % hist.shape[0]])
+
+    def staged_step():
+        tr.step(o, d, vd, 2., 6., tgt, 0.)
+
+    def grids(box, G):
+        return tuple(OccupancyGrid([-box] * 3, [box] * 3, G=G, k=2, dilate=1, precision="fp32_mfma").build(net) for net in tr.nets)
+
+    def ones():
+        return OccupancyGrid([-1.] * 3, [1.] * 3, G=4, k=1, dilate=0).set_bits(pack_bits(np.ones((4, 4, 4), dtype=bool)), device="cuda")
+
+    pairs = [("plain", None), ("box1.6", grids(1.6, 128)), ("box2.5", grids(2.5, 128)), ("all_ones", (ones(), ones()))]
+    got = {(name, kind): [] for name, _ in pairs for kind in ("staged", "fused")}
+    share = {}
+    for _ in range(a.repeats):
+        for name, pair in pairs:
+            tr.set_occupancy(pair)
+            for kind, fn in (("staged", staged_step), ("fused", fused_step)):
+                tr.live_acc.zero_()
+                it[0] = 0
+                got[(name, kind)].append(round(wall(fn, a.steps, a.warmup, sync_each=False), 3))
+                hist.tolist()
+                lv, tot = tr.live_acc.tolist()
+                share[name] = round(lv / tot, 4) if tot else 1.
+    tr.set_occupancy(None)
+    med = {k: float(np.median(v)) for k, v in got.items()}
+    for name, pair in pairs:
+        r = {"grids": name, "rays": R, "points": R * 256, "live_share": share[name]}
+        if pair is not None and name != "all_ones":
+            r["occupied_share"] = [round(g.occupied_share(), 4) for g in pair]
+        for kind in ("staged", "fused"):
+            r[kind + "_ms"] = got[(name, kind)]
+            r[kind + "_median_ms"] = med[(name, kind)]
+            r[kind + "_spread_ms"] = round(max(got[(name, kind)]) - min(got[(name, kind)]), 3)
+            r[kind + "_over_plain"] = round(med[(name, kind)] / med[("plain", kind)], 4)
+        emit(r)
+    # refresh cost
+    plain_ms = med[("plain", "fused")]
+    for G in (64, 128):
+        secs = []
+        gs = grids(1.6, G)
+        for _ in range(5):
+            secs.append([g.rebuild(net).build_seconds for g, net in zip(gs, tr.nets)])
+        per_grid = float(np.median([s for row in secs for s in row]))
+        K = 1
+        while 2. * per_grid * 1e3 > 0.02 * K * plain_ms:
+            K *= 2
+        emit({"rebuild": "exact fp32, %d^3 cells, 2 probes per cell and axis, dilation 1, box +-1.6" % G, "probes": (2 * G)**3,
+              "rebuild_ms_per_grid": round(per_grid * 1e3, 2), "all_ms": [[round(x * 1e3, 2) for x in row] for row in secs],
+              "plain_fused_step_ms": plain_ms, "smallest_power_of_two_K_with_two_rebuilds_at_most_2_percent": K,
+              "share_of_a_window_at_that_K": round(2. * per_grid * 1e3 / (K * plain_ms), 4)})
+    del tr
+    if a.effect_iters > 0:
+        H = W = 64
+        focal = 100.
+        train = analytic_views(20, H, W, focal, 0)
+        held = analytic_views(4, H, W, focal, 100)
+        n_train = train[0].shape[0]
+        N_rand, NS, NI = 1024, 32, 64
+
+        def run(seed, every):
+            sds = O.make_teacher_state_dicts(seed, 2, alpha_bias=0.5)
+            t = TeacherTrainer(make(sds[0]), make(sds[1]), N_samples=NS, N_importance=NI, perturb=1., white_bkgd=True)
+            log = ListLog()
+            oc = None
+            if every:
+                args = argparse.Namespace(r2l_occ_every=every, r2l_occ_res=128, r2l_occ_bound=1.6)
+                oc = TrainOccupancy(args, t.nets[0], t.nets[1], 2., 6., t, log, start=0)
+            g = torch.Generator(device="cuda").manual_seed(seed)
+            loss = torch.zeros(2, device="cuda")
+            t0 = time.perf_counter()
+            for i in range(1, a.effect_iters + 1):
+                sel = torch.randint(0, n_train, (N_rand,), generator=g, device="cuda")
+                t.fused_step(train[0][sel], train[1][sel], train[2][sel], 2., 6., train[3][sel], 5e-4, step=i, seed=seed, loss_out=loss)
+                if oc is not None:
+                    oc.after_step(i)
+            torch.cuda.synchronize()
+            secs = time.perf_counter() - t0
+            t.set_occupancy(None)
+            ones_ = torch.ones(held[0].shape[0], 1, device="cuda")
+            batch = torch.cat([held[0], held[1], 2. * ones_, 6. * ones_, held[2]], -1)
+            with torch.no_grad():
+                rgb = torch.cat([render.render_rays(batch[k:k + 4096], t.nets[0], None, NS, perturb=0., N_importance=NI, network_fine=t.nets[1],
+                                                    white_bkgd=True)["rgb_map"] for k in range(0, batch.shape[0], 4096)])
+            psnr = float(-10. * torch.log10(torch.mean((rgb - held[3])**2)))
+            r = {"effect_run": "grids every %d" % every if every else "plain", "seed": seed, "iterations": a.effect_iters, "N_rand": N_rand,
+                 "samples": "%d + %d" % (NS, NI), "train_loss_last": round(float(loss[0]), 5), "held_out_psnr": round(psnr, 3),
+                 "seconds": round(secs, 1)}
+            if oc is not None:
+                ref = [l for l in log.lines if "refresh after iteration" in l]
+                r["newly_set_cells_per_refresh"] = [int(re.search(r"(\d+) cells set now", l).group(1)) for l in ref]
+                r["live_share_per_window"] = [float(re.search(r"\(([0-9.]+)%\) in the window", l).group(1)) / 100 for l in ref]
+            emit(r)
+            return psnr
+
+        p0 = run(0, 0)
+        p1 = run(1, 0)
+        pk = {K: run(0, K) for K in a.effect_every}
+        emit({"effect": "held-out PSNR, grids minus plain (same seed)", "by_K": {str(K): round(v - p0, 3) for K, v in pk.items()},
+              "seed_spread_of_the_plain_run": round(abs(p0 - p1), 3)})
+    if a.out:
+        os.makedirs(os.path.dirname(os.path.abspath(a.out)), exist_ok=True)
+        with open(a.out, "w") as f:
+            f.write("\n".join(lines) + "\n")
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--rays", type=int, default=1024)
@@ -271,14 +445,20 @@ def main():
     ap.add_argument("--fused", action="store_true", help="time the staged step against the fused step (r2l_teacher_train_step)")
     ap.add_argument("--images", action="store_true", help="time images mode's host path against ImageBatcher.next (--r2l_image_sampler), "
                     "per batch and per whole iteration, staged and fused")
-    ap.add_argument("--repeats", type=int, default=3, help="--fused / --images: timed runs per path")
+    ap.add_argument("--occ", action="store_true", help="time the step on the live samples of occupancy grids (--r2l_occ_train) against "
+                    "the plain step, the grids' refresh, and the effect on a trained result")
+    ap.add_argument("--effect_iters", type=int, default=3000, help="--occ: iterations of each training run of the effect part (0: skip it)")
+    ap.add_argument("--effect_every", type=int, nargs="+", default=[64, 1024], help="--occ: the refresh intervals of the runs with grids")
+    ap.add_argument("--repeats", type=int, default=3, help="--fused / --images / --occ: timed runs per path")
     ap.add_argument("--out", default=None, help="where --batching / --fused / --images write their lines (default: "
                     "profiles/teacher_batching.txt / profiles/teacher_fused_step.txt / profiles/teacher_image_sampler.txt)")
     a = ap.parse_args()
     assert torch.cuda.is_available(), "teacher_train_time needs the GPU"
     if a.out is None:
-        a.out = os.path.join("profiles", "teacher_image_sampler.txt" if a.images else
+        a.out = os.path.join("profiles", "teacher_occ_train.txt" if a.occ else "teacher_image_sampler.txt" if a.images else
                              "teacher_fused_step.txt" if a.fused else "teacher_batching.txt")
+    if a.occ:
+        return occ(a)
     if a.images:
         return images(a)
     if a.fused:
