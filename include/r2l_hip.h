@@ -579,6 +579,80 @@ int r2l_teacher_frames_occ_cfg(const float* c2w_dev, const float* focal_dev, int
                                const r2l_occ_grid* grid_fine /*NULL: grid_coarse serves both passes*/,
                                int64_t* live_acc /*device int64[2] or NULL*/, float* work, void* stream, const r2l_config* cfg);
 
+/* ---- early ray termination: stop the teacher's rays once they are opaque ------------------------------------------------------------
+ * A grid removes the samples in empty space; what it cannot remove are the samples BEHIND the first opaque surface: their cells are
+ * occupied, the ray just never gets there.  Everything past the point where the transmittance T has fallen below eps adds less
+ * than T to the pixel.  The LAST pass of a render (the fine pass with N_importance > 0, else the only pass) is walked front to
+ * back in segments of consecutive sample numbers:
+ *   zero fill of raw;  per segment [s0, s1):  r2l_occ_index_seg (without the rays whose T < eps) -> r2l_teacher_mlp_live_into_cfg
+ *   -> r2l_ert_advance (T through the segment, from the raw just written);  then the unchanged r2l_raw2outputs.
+ * A skipped sample keeps raw = 0, which r2l_raw2outputs turns into alpha = 0 exactly — the grids' mechanism.  The coarse pass, its
+ * weights and so the fine depths are untouched bit for bit, hence for a ray terminated with transmittance T_cut (0: never):
+ *   |rgb - rgb_without| <= T_cut <= eps,  the same for acc, far * that for depth
+ * up to the fp32 slack of two S-term sums: the samples before the cut are identical, the skipped ones have weights that sum to at
+ * most T_cut and colours in [0, 1], and white_bkgd's 1 - acc moves by the same sum the other way.
+ * The calls follow the occupancy calls: stateless, arguments checked before any launch (hipErrorInvalidValue, r2l_last_error names
+ * the argument), enqueued on `stream`, never synchronising, no atomics, the same arguments give the same bits, R == 0 a successful
+ * no-op.  r2l_amd/ert.py (index_seg_spec, advance_spec) restates the first two in numpy.
+ *
+ * r2l_occ_index_seg: the index of one segment.  Sample n = r*S + s with s0 <= s < s1 is live iff
+ *   (grid == NULL, or its fp32 point is live by the rule of r2l_occ_grid above)  and  (trans == NULL, or NOT (trans[r] < eps)) —
+ * a NaN transmittance keeps its ray.  idx_out[0..M) = the live n in ascending order (capacity R*(s1-s0); entries >= M are not
+ * written), *count_out = M.  The kernels of r2l_occ_index with one more template switch: they enumerate m in [0, R*(s1-s0)) with
+ * r = m / (s1-s0), s = s0 + m % (s1-s0), which ascends in n.  work: r2l_occ_index_seg_work_bytes(R*(s1-s0)) bytes (-1 outside
+ * [0, 2^31)), 4-byte aligned.  R == 0 sets *count_out = 0.  Refused: 0 <= s0 < s1 <= S violated, R < 0, S < 1, R*S >= 2^31, eps not
+ * finite or <= 0 when trans != NULL, a NULL pointer other than grid / trans, a grid that r2l_occ_build would refuse. */
+int64_t r2l_occ_index_seg_work_bytes(int64_t n_samples);
+int r2l_occ_index_seg(const r2l_occ_grid* grid /*NULL: every point is live by the grid rule*/, const float* rays_o, const float* rays_d,
+                      const float* z /*[R,S]*/, int64_t R, int S, int s0, int s1,
+                      const float* trans /*device [R], or NULL: no ray is terminated*/, float eps,
+                      int64_t* idx_out /*capacity R*(s1-s0)*/, int64_t* count_out, void* work, void* stream);
+
+/* r2l_ert_advance: the transmittance through a segment.  T = 1.0f when s0 == 0 (trans is then not read), else trans[r]; for
+ * s = s0 .. s1-1 in ASCENDING order T = T * f_s, one fp32 rounding per product; trans[r] = T.
+ *   f_s = (1.0f - alpha_s) + 1e-10f,  alpha_s = 1.0f - __expf(-max(raw[r,s,3], 0) * dist_s),
+ *   dist_s = (s == S-1 ? 1e10f : z[r,s+1] - z[r,s]) * sqrtf(d0*d0 + d1*d1 + d2*d2)  (sums left to right)
+ * — the per-sample expressions of r2l_raw2outputs without noise.  The order is sequential on purpose: advance(0, a) followed by
+ * advance(a, b) equals advance(0, b) bit for bit.  Refused: the range errors above, a NULL pointer, S > 256. */
+int r2l_ert_advance(const float* raw /*[R,S,4]*/, const float* z /*[R,S]*/, const float* rays_d, int64_t R, int S, int s0, int s1,
+                    float* trans /*[R]: read unless s0 == 0, written*/, void* stream);
+
+/* r2l_teacher_mlp_live_cfg without its zero fill of raw, over an index list of `capacity` entries: for i < min(*count_dev, capacity)
+ * and n = idx[i] in [0, R*S), raw[n] = the point network at sample n (r2l_teacher_mlp_cfg's bits there, every kernel family, the
+ * fp16x2 family with its rescale and bf16x3 fallback); every other entry of raw is NOT TOUCHED.  The launch grid is sized for
+ * `capacity`, not for R*S: a segment pays a segment's launch floor; cfg is consulted with the capacity.  capacity == 0 launches
+ * nothing.  r2l_teacher_mlp_live_cfg is the memset plus this call with capacity = R*S.  Refused: what r2l_teacher_mlp_live_cfg
+ * refuses, capacity < 0 or > R*S. */
+int r2l_teacher_mlp_live_into_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z /*[R,S]*/,
+                                  const int64_t* idx /*device, `capacity` entries*/, const int64_t* count_dev /*device, 1*/,
+                                  int64_t capacity, const float* wstream, const float* tparams, float* raw /*[R,S,4]*/, int64_t R, int S,
+                                  void* stream, const r2l_config* cfg);
+
+/* r2l_teacher_frames_occ_cfg with early termination in the last pass.  grid_coarse / grid_fine may both be NULL: the coarse pass is
+ * then the plain r2l_teacher_mlp_cfg launch and the last pass skips by transmittance alone (grid_fine NULL with a grid_coarse: it
+ * serves both passes, as above).  The last pass zero-fills raw once and then runs, for the segments [j*seg, min((j+1)*seg, S)):
+ * r2l_occ_index_seg (trans = NULL for j = 0) -> r2l_occ_live_add (with live_acc; the total of a segment is rays*(s1-s0)) ->
+ * r2l_teacher_mlp_live_into_cfg with capacity = rays*(s1-s0) -> r2l_ert_advance (not after the last segment).  Without grids the
+ * coarse pass adds nothing to live_acc.  work: r2l_teacher_frames_ert_work_floats(d, ert) floats =
+ * r2l_teacher_frames_occ_work_floats(d) + trans (one float per ray of a chunk, rounded up to 4).  With seg >= S of the last pass
+ * there is one segment and no termination: the frame equals r2l_teacher_frames_occ_cfg's (with grids) or r2l_teacher_frames_cfg's
+ * (without) bit for bit.  Refused in addition to r2l_teacher_frames_cfg's refusals (raw_noise_std is 0 there already): a NULL ert,
+ * eps outside (0, 0.1], seg < 8, non-zero reserved, d->ndc == 1 WITH a grid (ndc == 1 without grids is accepted: the first way to
+ * skip samples on forward-facing scenes), grid_fine without grid_coarse, a grid r2l_occ_build would refuse. */
+typedef struct r2l_ert_desc {
+    float eps;                     /* a ray whose transmittance is below eps at a segment boundary is terminated */
+    int seg;                       /* samples per segment */
+    int reserved[2];               /* must be 0 */
+} r2l_ert_desc;
+int64_t r2l_teacher_frames_ert_work_floats(const r2l_teacher_frame_desc* d, const r2l_ert_desc* ert);
+int r2l_teacher_frames_ert_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                               const float* ttab, const float* u_det, const float* wstream_coarse, const float* tparams_coarse,
+                               const float* wstream_fine, const float* tparams_fine, float* rows, float* rgb, float* disp, float* acc,
+                               float* depth, float* rgb0, const r2l_occ_grid* grid_coarse /*NULL: no grids*/,
+                               const r2l_occ_grid* grid_fine /*NULL: grid_coarse serves both passes*/,
+                               int64_t* live_acc /*device int64[2] or NULL*/, const r2l_ert_desc* ert, float* work, void* stream,
+                               const r2l_config* cfg);
+
 /* ---- test-set metric ------------------------------------------------------------------------------------------------
  * out[0] = SSIM(img1, img2): utils/ssim_torch.py:28-56,86-94 as called at main.py:46,254,334 (11x11 Gaussian sigma 1.5,
  * zero padding, C1 = 0.01^2, C2 = 0.03^2, mean over every pixel and channel), fused into one kernel + a fixed-order

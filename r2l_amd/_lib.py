@@ -87,6 +87,14 @@ class OccGridDesc(ctypes.Structure):
 _occp = ctypes.POINTER(OccGridDesc)
 
 
+class ErtDesc(ctypes.Structure):
+    """r2l_ert_desc of include/r2l_hip.h (r2l_teacher_frames_ert_cfg): 16 bytes."""
+    _fields_ = [("eps", _f), ("seg", _i), ("reserved", _i * 2)]
+
+
+_ertp = ctypes.POINTER(ErtDesc)
+
+
 def make_config(precision="auto", tiling="auto", coop_tiles=0, reserve_cus=0, dw_mode="auto"):
     if tiling == "coop":
         raise ValueError("tiling 'coop' (the 32-ray fp32-MFMA cooperative kernels) was retired in round 5: every *_cfg call would "
@@ -175,6 +183,12 @@ SIGNATURES = {
     "r2l_teacher_mlp_live_cfg": (_i, [_p] * 9 + [_l, _i, _p, _cfgp]),
     "r2l_teacher_frames_occ_work_floats": (_l, [_descp]),
     "r2l_teacher_frames_occ_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 12 + [_occp, _occp, _p, _p, _p, _cfgp]),
+    "r2l_occ_index_seg_work_bytes": (_l, [_l]),
+    "r2l_occ_index_seg": (_i, [_occp] + [_p] * 3 + [_l, _i, _i, _i, _p, _f] + [_p] * 4),
+    "r2l_ert_advance": (_i, [_p, _p, _p, _l, _i, _i, _i, _p, _p]),
+    "r2l_teacher_mlp_live_into_cfg": (_i, [_p] * 6 + [_l] + [_p] * 3 + [_l, _i, _p, _cfgp]),
+    "r2l_teacher_frames_ert_work_floats": (_l, [_descp, _ertp]),
+    "r2l_teacher_frames_ert_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 12 + [_occp, _occp, _p, _ertp, _p, _p, _cfgp]),
     "r2l_ssim_partial_count": (_l, [_i, _i, _i]),
     "r2l_ssim": (_i, [_p, _p, _i, _i, _i, _p, _p, _p, _p]),
     "r2l_flip_partial_count": (_l, [_i, _i, _i]),

@@ -23,7 +23,7 @@ from .checkpoint import load_weights
 from .driver import _runs, apply_arithmetic, init_distributed, sync
 from .logger import Logger
 from .nerf_raybased import NeRF
-from .options import parse_args, validate_accelerated, validate_occ_fused, validate_occupancy
+from .options import parse_args, validate_accelerated, validate_ert, validate_occ_fused, validate_occupancy
 from .render import get_embedder, get_rays, render, render_frames, run_network
 
 
@@ -87,6 +87,7 @@ def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device
     """--r2l_store_save: render this rank's poses into a ray store in device memory and write it as one file (the name is the
     path at world size 1, <path>.rank<r>of<w> otherwise)."""
     from .online_kd import TeacherFill, rank_poses, shards_needed
+    from .occupancy import fused_skipping
     from .raystore import CompactRayStore, RayStore, store_rank_path
     n_pose = args.n_pose_kd if isinstance(args.n_pose_kd, int) else int(args.n_pose_kd[0])
     cap = shards_needed(n_pose, args.create_data_chunk, H, W, rank, world)
@@ -98,7 +99,7 @@ def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device
         store = RayStore(cap, device, seed=9973 * rank, logger=logger)
     t0 = time.time()
     filler = TeacherFill(store, args, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                         rand_pose=rand_pose, ndc=ndc, occ_args=args if args.r2l_occ_fused else None)
+                         rand_pose=rand_pose, ndc=ndc, occ_args=args if fused_skipping(args) else None)
     prov = filler.provenance()
     while not filler.done:
         filler.fill_group()
@@ -115,6 +116,7 @@ def main(argv=None):
     validate_accelerated(args)
     validate_occupancy(args)
     validate_occ_fused(args, ("r2l_fused_frames", "r2l_store_save"))
+    validate_ert(args, ("r2l_fused_frames", "r2l_store_save"))
     if args.r2l_occupancy and args.r2l_store_save:
         raise ValueError("--r2l_occupancy: not with --r2l_store_save, which renders through the fused frames call (no host read of "
                          "the live count)")
@@ -145,7 +147,7 @@ def main(argv=None):
         from .occupancy import build_pair, log_live
         occ_pair = kwargs["occupancy"] = build_pair(args, coarse, fine, near, far, logger)
     occ_fused = None  # --r2l_occ_fused: the same grids inside the fused frames calls below (not needed by a pure store fill,
-    if args.r2l_occ_fused and (args.r2l_fused_frames and (args.test_teacher or not args.r2l_store_save)):  # which builds its own)
+    if (args.r2l_occ_fused or args.r2l_ert > 0) and (args.r2l_fused_frames and (args.test_teacher or not args.r2l_store_save)):  # which builds its own)
         from .occupancy import FusedOccupancy
         occ_fused = FusedOccupancy(args, coarse, fine, near, far, logger)
     if args.test_teacher:

@@ -8,7 +8,11 @@
 //   r2l_occ_scatter  raw of the live rows back into a zero-filled [R,S,4];
 //   r2l_occ_index    r2l_occ_compact's idx and count without its row copies (the same kernels, a template switch), for the point
 //                    network's live form (r2l_teacher_mlp_live_cfg), which reads the count on the device; r2l_occ_live_add sums
-//                    counts in stream order.
+//                    counts in stream order;
+//   r2l_occ_index_seg  r2l_occ_index over one segment of consecutive sample numbers of every ray, without the rays whose transmittance
+//                    is below eps, the grid optional (one more template switch of the same kernels);
+//   r2l_ert_advance  a ray's transmittance through a segment, from the raw the point network has written (early ray termination,
+//                    include/r2l_hip.h "early ray termination").
 // No kernel of the point network is touched here.  Nothing here is compute-bound: build is the network's time, compact and scatter
 // move 40 + 8 and 32 bytes per live sample.  Every output position comes from a scan, never from the arrival order of an
 // atomic (there are no atomics in this file): the same arguments give the same bits.
@@ -146,29 +150,45 @@ struct CompactArgs {
     unsigned* blk;  // [number of workgroups]: counts, then exclusive offsets
     float *out_o, *out_d, *out_v, *out_z;
     int64_t* idx;
+    // SEG only (r2l_occ_index_seg): the samples s0 <= s < s0 + W of every ray; n is then R * W, and g.bits may be NULL (no grid)
+    int s0, W;
+    const float* trans;  // [R] or NULL: a ray with trans < eps has no live sample
+    float eps;
 };
 
 // ROWS: the (o, d, viewdirs, z) row copies of r2l_occ_compact; without them the placement writes idx alone (r2l_occ_index)
-template <bool EMIT, bool ROWS = true>
+// SEG: the enumeration runs over a segment of every ray (m -> ray m / W, sample s0 + m % W: ascending in n = ray * S + s), the grid
+//      is optional and a terminated ray drops out (r2l_occ_index_seg); the other instantiations compile from the code they had
+template <bool EMIT, bool ROWS = true, bool SEG = false>
 __global__ __launch_bounds__(OCC_THREADS) void r2l_occ_compact_kernel(const CompactArgs a) {
+    static_assert(!(SEG && ROWS), "the segment form writes idx alone");
     __shared__ unsigned wsum[OCC_THREADS / 64];
     const int t = threadIdx.x, lane = t & 63, w = t >> 6;
     const int64_t base = (int64_t)blockIdx.x * OCC_CHUNK;
     unsigned running = EMIT ? a.blk[blockIdx.x] : 0u;
 #pragma unroll 1
     for (int r = 0; r < OCC_ROUNDS; ++r) {
-        const int64_t n = base + r * OCC_THREADS + t;
+        int64_t n = base + r * OCC_THREADS + t;
         bool live = false;
         int64_t ray = 0;
         float zz = 0.f;
         if (n < a.n) {
-            ray = n / a.S;
-            zz = a.z[n];
-            // the point exactly as r2l_teacher_mlp_kernel forms it: product and sum rounded separately
-            const float px = a.o[ray * 3 + 0] + a.d[ray * 3 + 0] * zz;
-            const float py = a.o[ray * 3 + 1] + a.d[ray * 3 + 1] * zz;
-            const float pz = a.o[ray * 3 + 2] + a.d[ray * 3 + 2] * zz;
-            live = occ_live(a.g, px, py, pz);
+            if constexpr (SEG) {
+                ray = n / a.W;
+                n = ray * a.S + a.s0 + (n - ray * a.W);  // < R * S < 2^31
+                live = !(a.trans != nullptr && a.trans[ray] < a.eps);  // (a NaN transmittance keeps the ray)
+            } else {
+                ray = n / a.S;
+                live = true;
+            }
+            if (!SEG || (live && a.g.bits != nullptr)) {
+                zz = a.z[n];
+                // the point exactly as r2l_teacher_mlp_kernel forms it: product and sum rounded separately
+                const float px = a.o[ray * 3 + 0] + a.d[ray * 3 + 0] * zz;
+                const float py = a.o[ray * 3 + 1] + a.d[ray * 3 + 1] * zz;
+                const float pz = a.o[ray * 3 + 2] + a.d[ray * 3 + 2] * zz;
+                live = occ_live(a.g, px, py, pz);
+            }
         }
         const unsigned long long m = __ballot(live);
         if (!EMIT) {
@@ -249,6 +269,41 @@ __global__ void r2l_occ_live_add_kernel(const int64_t* __restrict__ count, int64
     if (blockIdx.x == 0 && threadIdx.x == 0) {
         live_acc[0] += *count;
         live_acc[1] += total;
+    }
+}
+
+// ---- early ray termination: the transmittance through a segment ----------------------------------------------------------------
+// trans[r] = (s0 == 0 ? 1 : trans[r]) * prod over s0 <= s < s1, in ascending s, of f_s = (1 - alpha_s) + 1e-10, alpha_s by the
+// per-sample expressions of r2l_raw2outputs without noise.  A workgroup owns ERT_RAYS rays.  Phase 1: all 256 threads form the
+// ERT_RAYS * W factors, consecutive threads taking consecutive samples of a ray (sigma is every fourth float of raw: a wave's loads
+// cover one contiguous span instead of one line per ray), into an LDS tile whose odd row stride keeps phase 2 off one bank.
+// Phase 2: thread r multiplies row r front to back — the pinned order, one rounding per product.
+constexpr int ERT_RAYS = 32;
+constexpr int ERT_MAX_S = 256;
+constexpr int ERT_STRIDE = ERT_MAX_S + 1;
+
+__global__ __launch_bounds__(OCC_THREADS) void r2l_ert_advance_kernel(const float* __restrict__ raw, const float* __restrict__ z,
+                                                                      const float* __restrict__ rays_d, int64_t R, int S, int s0, int W,
+                                                                      float* __restrict__ trans) {
+    __shared__ float f[ERT_RAYS * ERT_STRIDE];
+    const int t = threadIdx.x;
+    const int64_t r0 = (int64_t)blockIdx.x * ERT_RAYS;
+    const int rays = R - r0 < ERT_RAYS ? (int)(R - r0) : ERT_RAYS;
+    for (int e = t; e < rays * W; e += OCC_THREADS) {
+        const int rl = e / W, sl = e - rl * W, s = s0 + sl;
+        const int64_t ray = r0 + rl, n = ray * S + s;
+        const float d0 = rays_d[ray * 3 + 0], d1 = rays_d[ray * 3 + 1], d2 = rays_d[ray * 3 + 2];
+        const float dn = sqrtf(d0 * d0 + d1 * d1 + d2 * d2);  // the association of r2l_raw2outputs
+        float dist = (s + 1 < S) ? z[n + 1] - z[n] : 1e10f;
+        dist = dist * dn;
+        const float al = 1.0f - __expf(-fmaxf(raw[n * 4 + 3], 0.f) * dist);
+        f[rl * ERT_STRIDE + sl] = (1.0f - al) + 1e-10f;
+    }
+    __syncthreads();
+    if (t < rays) {
+        float T = s0 == 0 ? 1.0f : trans[r0 + t];
+        for (int sl = 0; sl < W; ++sl) T = T * f[t * ERT_STRIDE + sl];
+        trans[r0 + t] = T;
     }
 }
 
@@ -484,6 +539,81 @@ extern "C" int r2l_occ_live_add(const int64_t* count, int64_t total, int64_t* li
     R2L_REQUIRE(total >= 0, "r2l_occ_live_add: total is negative");
     R2L_REQUIRE(live_acc != nullptr, "r2l_occ_live_add: live_acc is NULL");
     hipLaunchKernelGGL(r2l_occ_live_add_kernel, dim3(1), dim3(64), 0, (hipStream_t)stream, count, total, live_acc);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t r2l_occ_index_seg_work_bytes(int64_t n) {
+    if (n < 0 || n >= ((int64_t)1 << 31)) {
+        r2l_set_error_msg("r2l_occ_index_seg_work_bytes: need 0 <= R*(s1-s0) < 2^31");
+        return -1;
+    }
+    return r2l_occ_compact_work_bytes(n);  // (the same per-workgroup counts)
+}
+
+// The index of one segment of every ray, with the terminated rays left out: the count / scan / placement launches of r2l_occ_index
+// over the R * (s1 - s0) samples of the segment
+extern "C" int r2l_occ_index_seg(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, const float* z, int64_t R, int S,
+                                 int s0, int s1, const float* trans, float eps, int64_t* idx_out, int64_t* count_out, void* work,
+                                 void* stream) {
+    if (grid != nullptr)
+        if (const char* why = occ_grid_check(grid, "r2l_occ_index_seg: grid is NULL")) {
+            r2l_set_error_msg(why);
+            return (int)hipErrorInvalidValue;
+        }
+    R2L_REQUIRE(R >= 0, "r2l_occ_index_seg: R is negative");
+    R2L_REQUIRE(S >= 1, "r2l_occ_index_seg: S: need S >= 1");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_occ_index_seg: R*S: need R*S < 2^31");
+    R2L_REQUIRE(s0 >= 0 && s0 < s1 && s1 <= S, "r2l_occ_index_seg: s0 / s1: need 0 <= s0 < s1 <= S");
+    R2L_REQUIRE(trans == nullptr || (eps > 0.f && eps - eps == 0.f), "r2l_occ_index_seg: eps: need a positive finite value with trans");
+    R2L_REQUIRE(count_out != nullptr, "r2l_occ_index_seg: count_out is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    if (R == 0) {
+        R2L_CHECK(hipMemsetAsync(count_out, 0, sizeof(int64_t), s));
+        return 0;
+    }
+    R2L_REQUIRE(rays_o != nullptr, "r2l_occ_index_seg: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_occ_index_seg: rays_d is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_occ_index_seg: z is NULL");
+    R2L_REQUIRE(idx_out != nullptr, "r2l_occ_index_seg: idx_out is NULL");
+    R2L_REQUIRE(work != nullptr, "r2l_occ_index_seg: work is NULL");
+    R2L_REQUIRE(((uintptr_t)work & 3) == 0, "r2l_occ_index_seg: work is not 4-byte aligned");
+    CompactArgs a{};
+    if (grid != nullptr) a.g = occ_dev(grid);  // (else bits == NULL: every point is live by the grid rule)
+    a.o = rays_o; a.d = rays_d; a.z = z;
+    a.S = S;
+    a.s0 = s0;
+    a.W = s1 - s0;
+    a.n = R * (int64_t)a.W;
+    a.trans = trans;
+    a.eps = eps;
+    a.blk = (unsigned*)work;
+    a.idx = idx_out;
+    const int64_t nb = (a.n + OCC_CHUNK - 1) / OCC_CHUNK;  // <= 2^20
+    hipLaunchKernelGGL((r2l_occ_compact_kernel<false, false, true>), dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, a);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(r2l_occ_scan_kernel, dim3(1), dim3(OCC_SCAN_THREADS), 0, s, a.blk, nb, (nb + OCC_SCAN_THREADS - 1) / OCC_SCAN_THREADS,
+                       count_out);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL((r2l_occ_compact_kernel<true, false, true>), dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_ert_advance(const float* raw, const float* z, const float* rays_d, int64_t R, int S, int s0, int s1, float* trans,
+                               void* stream) {
+    R2L_REQUIRE(R >= 0, "r2l_ert_advance: R is negative");
+    R2L_REQUIRE(S >= 1 && S <= ERT_MAX_S, "r2l_ert_advance: S: need 1 <= S <= 256");
+    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_ert_advance: R*S: need R*S < 2^31");
+    R2L_REQUIRE(s0 >= 0 && s0 < s1 && s1 <= S, "r2l_ert_advance: s0 / s1: need 0 <= s0 < s1 <= S");
+    if (R == 0) return 0;
+    R2L_REQUIRE(raw != nullptr, "r2l_ert_advance: raw is NULL");
+    R2L_REQUIRE(z != nullptr, "r2l_ert_advance: z is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_ert_advance: rays_d is NULL");
+    R2L_REQUIRE(trans != nullptr, "r2l_ert_advance: trans is NULL");
+    const int64_t nb = (R + ERT_RAYS - 1) / ERT_RAYS;  // < 2^26
+    hipLaunchKernelGGL(r2l_ert_advance_kernel, dim3((unsigned)nb), dim3(OCC_THREADS), 0, (hipStream_t)stream, raw, z, rays_d, R, S, s0,
+                       s1 - s0, trans);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

@@ -255,7 +255,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher2_kernel(const T16Args a) {
     bool valid = pt < n_pts;
     int64_t pc = valid ? pt : n_pts - 1;
     int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
-    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_out, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -418,9 +418,9 @@ int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream)
 
 int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const int64_t* idx, const int64_t* count_dev) {
+                     const int64_t* idx, const int64_t* count_dev, int64_t n_out) {
     T16Args a{};
-    a.idx = idx; a.count_dev = count_dev;
+    a.idx = idx; a.count_dev = count_dev; a.n_out = n_out > 0 ? n_out : n_pts;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream2); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
     // the status word lives in the caller's stream buffer (library-private contents): written through, hence the cast

@@ -117,7 +117,7 @@ __global__ __launch_bounds__(256, 1) void r2l_teacher3_kernel(const T16Args a) {
     bool valid = pt < n_pts;
     int64_t pc = valid ? pt : n_pts - 1;
     int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
-    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_out, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -254,10 +254,10 @@ int r2l_teacher3_pack(const float* tparams, float* wstream3, hipStream_t stream)
 
 int r2l_teacher3_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream3, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const unsigned* run_if, const int64_t* idx, const int64_t* count_dev) {
+                     const unsigned* run_if, const int64_t* idx, const int64_t* count_dev, int64_t n_out) {
     T16Args a{};
     a.run_if = run_if;
-    a.idx = idx; a.count_dev = count_dev;
+    a.idx = idx; a.count_dev = count_dev; a.n_out = n_out > 0 ? n_out : n_pts;
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z;
     a.stream = reinterpret_cast<const unsigned char*>(wstream3); a.params = tparams; a.raw = raw; a.n_pts = n_pts; a.S = S;
     if (idx != nullptr) hipLaunchKernelGGL(r2l_teacher3_kernel<true>, dim3(t_workgroups(n_pts)), dim3(256), 0, stream, a);

@@ -11,6 +11,9 @@
 //                           buffer the caller sized once: no allocation, no host synchronisation
 //   r2l_teacher_frames_occ_cfg: the same body with each point-network launch replaced by r2l_occ_index -> r2l_teacher_mlp_live_cfg
 //                           (occupancy grids, the live count read on the device): still no host synchronisation
+//   r2l_teacher_frames_ert_cfg: the same body again; its LAST pass walks the samples front to back in segments and leaves out the
+//                           rays whose transmittance has fallen below eps (r2l_occ_index_seg -> r2l_teacher_mlp_live_into_cfg ->
+//                           r2l_ert_advance per segment), with or without grids
 //   r2l_pixel_batch       : the batching mode of teacher training (main.py:1137-1162, 1199-1210) without its bank of rays:
 //                           draw t takes pixel pi(epoch_key(seed, t / M), M)(t % M) of the M = n_img*H*W training pixels
 //                           (csrc/r2l_perm.h, the ray store's sampler), and its ray is computed on the spot
@@ -22,6 +25,7 @@
 #include "r2l_dispatch.h"
 #include "r2l_perm.h"
 #include "r2l_pixel_ray.h"
+#include <initializer_list>
 #include <math.h>
 #include <stdio.h>
 
@@ -330,11 +334,22 @@ OccWork occ_work(const r2l_teacher_frame_desc* d, const FrameWork& w) {
     return o;
 }
 
-// The grids of the occupancy form, or none: the ONE body below serves both entry points
+// The grids of the occupancy form (both NULL: the early-termination form without grids) and the early termination of the last pass,
+// or none: the ONE body below serves the three entry points
 struct FrameOcc {
     const r2l_occ_grid *coarse, *fine;
     int64_t* live_acc;
+    const r2l_ert_desc* ert;
 };
+
+// What is wrong with an early-termination descriptor, or nullptr
+const char* ert_check(const r2l_ert_desc* e) {
+    if (e == nullptr) return "r2l_ert_desc: ert is NULL";
+    if (!(e->eps > 0.f && e->eps <= 0.1f)) return "r2l_ert_desc.eps: need 0 < eps <= 0.1";
+    if (e->seg < 8) return "r2l_ert_desc.seg: need seg >= 8";
+    if (e->reserved[0] || e->reserved[1]) return "r2l_ert_desc.reserved: must be 0";
+    return nullptr;
+}
 
 int frames_body(const char* who, const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d, const float* ttab,
                 const float* u_det, const float* wstream_coarse, const float* tparams_coarse, const float* wstream_fine,
@@ -478,6 +493,45 @@ extern "C" int64_t r2l_teacher_frames_occ_work_floats(const r2l_teacher_frame_de
     return occ_work(d, frame_work(d)).total;
 }
 
+extern "C" int64_t r2l_teacher_frames_ert_work_floats(const r2l_teacher_frame_desc* d, const r2l_ert_desc* ert) {
+    const char* why = desc_check(d);
+    if (why == nullptr) why = ert_check(ert);
+    if (why != nullptr) {
+        r2l_set_error_msg(why);
+        return -1;
+    }
+    const int64_t hw = (int64_t)d->H * d->W;
+    const int64_t cr = d->chunk_rays > 0 && d->chunk_rays < hw ? d->chunk_rays : hw;
+    return occ_work(d, frame_work(d)).total + r4(cr);  // (trans of a chunk's rays behind the occupancy form's buffer)
+}
+
+extern "C" int r2l_teacher_frames_ert_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
+                                          const float* ttab, const float* u_det, const float* wstream_coarse,
+                                          const float* tparams_coarse, const float* wstream_fine, const float* tparams_fine, float* rows,
+                                          float* rgb, float* disp, float* acc, float* depth, float* rgb0,
+                                          const r2l_occ_grid* grid_coarse, const r2l_occ_grid* grid_fine, int64_t* live_acc,
+                                          const r2l_ert_desc* ert, float* work, void* stream, const r2l_config* cfg) {
+    const char* why = desc_check(d);
+    if (why == nullptr) why = ert_check(ert);
+    if (why != nullptr) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    R2L_REQUIRE(grid_coarse != nullptr || grid_fine == nullptr,
+                "r2l_teacher_frames_ert_cfg: grid_fine without grid_coarse (both NULL: no grids; grid_fine NULL: grid_coarse serves both passes)");
+    R2L_REQUIRE(d->ndc == 0 || grid_coarse == nullptr,
+                "r2l_teacher_frames_ert_cfg: r2l_teacher_frame_desc.ndc must be 0 with a grid (the box of an occupancy grid is in world space)");
+    for (const r2l_occ_grid* g : {grid_coarse, grid_fine})
+        if (g != nullptr)
+            if (const char* bad = r2l_occ_grid_why(g, "r2l_teacher_frames_ert_cfg: grid is NULL")) {
+                r2l_set_error_msg(bad);
+                return (int)hipErrorInvalidValue;
+            }
+    const FrameOcc occ{grid_coarse, grid_fine ? grid_fine : grid_coarse, live_acc, ert};
+    return frames_body("r2l_teacher_frames_ert_cfg", c2w_dev, focal_dev, K, d, ttab, u_det, wstream_coarse, tparams_coarse, wstream_fine,
+                       tparams_fine, rows, rgb, disp, acc, depth, rgb0, work, stream, cfg, &occ);
+}
+
 extern "C" int r2l_teacher_frames_occ_cfg(const float* c2w_dev, const float* focal_dev, int K, const r2l_teacher_frame_desc* d,
                                           const float* ttab, const float* u_det, const float* wstream_coarse,
                                           const float* tparams_coarse, const float* wstream_fine, const float* tparams_fine, float* rows,
@@ -498,7 +552,7 @@ extern "C" int r2l_teacher_frames_occ_cfg(const float* c2w_dev, const float* foc
             r2l_set_error_msg(why);
             return (int)hipErrorInvalidValue;
         }
-    const FrameOcc occ{grid_coarse, grid_fine ? grid_fine : grid_coarse, live_acc};
+    const FrameOcc occ{grid_coarse, grid_fine ? grid_fine : grid_coarse, live_acc, nullptr};
     return frames_body("r2l_teacher_frames_occ_cfg", c2w_dev, focal_dev, K, d, ttab, u_det, wstream_coarse, tparams_coarse, wstream_fine,
                        tparams_fine, rows, rgb, disp, acc, depth, rgb0, work, stream, cfg, &occ);
 }
@@ -516,14 +570,33 @@ namespace {
         }                                                            \
     } while (0)
 
-// The point network of one pass: the plain launch, or (occupancy form) index -> [live_acc] -> the live launch
+// The point network of one pass: the plain launch, or (occupancy form) index -> [live_acc] -> the live launch, or (the last pass
+// of the early-termination form) a zero fill of raw, then per segment of consecutive sample numbers: the index of the segment
+// without the rays terminated so far -> [live_acc] -> the live launch into raw -> the transmittance through the segment
 int frames_mlp(const float* o, const float* dd, const float* v, const float* z, const float* wstream, const float* tparams, float* raw,
                int64_t cr, int S, void* stream, const r2l_config* cfg, const r2l_occ_grid* grid, const FrameOcc* occ, float* work,
-               const OccWork& ow) {
+               const OccWork& ow, bool last) {
     if (occ == nullptr) return r2l_teacher_mlp_cfg(o, dd, v, z, wstream, tparams, raw, cr, S, stream, cfg);
     int64_t* const idx = reinterpret_cast<int64_t*>(work + ow.idx);
     int64_t* const count = reinterpret_cast<int64_t*>(work + ow.count);
     int rc;
+    if (occ->ert != nullptr && last) {
+        float* const trans = work + ow.total;  // [chunk rays], behind the occupancy form's parts
+        R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)cr * S * 4 * sizeof(float), (hipStream_t)stream));
+        const int seg = occ->ert->seg;
+        for (int s0 = 0; s0 < S; s0 += seg) {
+            const int s1 = S - s0 < seg ? S : s0 + seg;
+            const int64_t cap = cr * (int64_t)(s1 - s0);
+            if ((rc = r2l_occ_index_seg(grid, o, dd, z, cr, S, s0, s1, s0 == 0 ? nullptr : trans, occ->ert->eps, idx, count,
+                                        work + ow.iwork, stream)))
+                return rc;
+            if (occ->live_acc != nullptr && (rc = r2l_occ_live_add(count, cap, occ->live_acc, stream))) return rc;
+            if ((rc = r2l_teacher_mlp_live_into_cfg(o, dd, v, z, idx, count, cap, wstream, tparams, raw, cr, S, stream, cfg))) return rc;
+            if (s1 < S && (rc = r2l_ert_advance(raw, z, dd, cr, S, s0, s1, trans, stream))) return rc;
+        }
+        return 0;
+    }
+    if (grid == nullptr) return r2l_teacher_mlp_cfg(o, dd, v, z, wstream, tparams, raw, cr, S, stream, cfg);
     if ((rc = r2l_occ_index(grid, o, dd, z, cr, S, idx, count, work + ow.iwork, stream))) return rc;
     if (occ->live_acc != nullptr && (rc = r2l_occ_live_add(count, cr * (int64_t)S, occ->live_acc, stream))) return rc;
     return r2l_teacher_mlp_live_cfg(o, dd, v, z, idx, count, wstream, tparams, raw, cr, S, stream, cfg);
@@ -579,7 +652,7 @@ int frames_body(const char* who, const float* c2w_dev, const float* focal_dev, i
             }
             if ((rc = r2l_stratified_z(nf, nf + 1, 0, ttab, t_rand, z, cr, S, stream))) return rc;
             if ((rc = frames_mlp(o, dd, v, z, wstream_coarse, tparams_coarse, raw, cr, S, stream, cfg, occ ? occ->coarse : nullptr, occ, work,
-                                 ow)))
+                                 ow, NI == 0)))
                 return rc;
             if (NI == 0) {
                 if ((rc = r2l_raw2outputs(raw, z, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, S, stream)))
@@ -599,7 +672,7 @@ int frames_body(const char* who, const float* c2w_dev, const float* focal_dev, i
                                               stream)))
                     return rc;
                 if ((rc = frames_mlp(o, dd, v, work + w.zall, wfine, pfine, raw, cr, T, stream, cfg, occ ? occ->fine : nullptr, occ, work,
-                                     ow)))
+                                     ow, true)))
                     return rc;
                 if ((rc = r2l_raw2outputs(raw, work + w.zall, dd, nullptr, d->white_bkgd, f_rgb, f_disp, f_acc, nullptr, f_depth, cr, T,
                                           stream)))

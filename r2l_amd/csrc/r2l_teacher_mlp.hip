@@ -7,6 +7,7 @@
 // MFMA, weights pre-packed into ONE stream in consumption order (r2l_pack_teacher below).
 #include "r2l_dispatch.h"
 #include "r2l_teacher_net.h"
+#include <stdio.h>
 
 #define T_PE_STEPS 36   // xyz embedding k-steps per half-wave (30 trig + 3 identity + 3 pad)  -> 9 groups
 #define T_PE_GROUPS 9
@@ -117,6 +118,7 @@ struct TeacherArgs {
     float* stash;           // training only (r2l_teacher_mlp_train): the layer outputs of every point (r2l_teacher_net.h)
     const int64_t* idx;        // live form only (r2l_teacher_net.h): the sample of every tile lane, capacity n_pts
     const int64_t* count_dev;  // live form only: how many entries of idx count (device, 1)
+    int64_t n_out;             // live form only: the entries of idx name samples in [0, n_out) (R*S; n_pts unless the list is shorter)
 };
 
 // one wave's NT 32-feature tiles of a layer output (accumulator layout: point = lane & 31, feature 32T + 8q + 4h + j)
@@ -197,7 +199,7 @@ __device__ __forceinline__ void t_mlp_chain(const TeacherArgs& a) {
     bool valid = pt < n_pts;
     int64_t pc = valid ? pt : n_pts - 1;
     int live_n = 0;  // LIVE: the sample this lane stores (< 2^31: one register across the chain, not the 64-bit pair)
-    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_pts, pt, valid));
+    if constexpr (LIVE) live_n = (int)(pc = t_live_sample(a.idx, n_pts, a.n_out, pt, valid));
     const int64_t ray = pc / a.S;
 
     float p[3], vd[3];
@@ -395,43 +397,74 @@ extern "C" int r2l_teacher_mlp_cfg(const float* rays_o, const float* rays_d, con
 }
 
 // The point network on an index list with a device count (include/r2l_hip.h): the dispatch of r2l_teacher_mlp_cfg with every
-// kernel in its live form, behind a zero fill of raw.  Nothing here reads the count on the host.
-extern "C" int r2l_teacher_mlp_live_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
-                                        const int64_t* idx, const int64_t* count_dev, const float* wstream, const float* params,
-                                        float* raw, int64_t R, int S, void* stream, const r2l_config* cfg) {
+// kernel in its live form.  Nothing here reads the count on the host.  `who` names the entry point in a refusal; zero_fill: the
+// memset of raw that r2l_teacher_mlp_live_cfg puts in front (sigma = +0 -> alpha = 0, as r2l_occ_scatter).
+static int t_mlp_live(const char* who, bool zero_fill, const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                      const int64_t* idx, const int64_t* count_dev, int64_t capacity, const float* wstream, const float* params, float* raw,
+                      int64_t R, int S, void* stream, const r2l_config* cfg) {
+#define T_LIVE_REQUIRE(cond, msg)                                \
+    do {                                                         \
+        if (!(cond)) {                                           \
+            static thread_local char buf_[160];                  \
+            snprintf(buf_, sizeof buf_, "%s: %s", who, msg);     \
+            r2l_set_error_msg(buf_);                             \
+            return (int)hipErrorInvalidValue;                    \
+        }                                                        \
+    } while (0)
     R2L_CFG_ENTER(cfg);
-    R2L_REQUIRE(R >= 0, "r2l_teacher_mlp_live_cfg: R is negative");
-    R2L_REQUIRE(S >= 1, "r2l_teacher_mlp_live_cfg: S: need S >= 1");
-    R2L_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "r2l_teacher_mlp_live_cfg: R*S: need R*S < 2^31");
+    T_LIVE_REQUIRE(R >= 0, "R is negative");
+    T_LIVE_REQUIRE(S >= 1, "S: need S >= 1");
+    T_LIVE_REQUIRE(R < ((int64_t)1 << 31) && R * (int64_t)S < ((int64_t)1 << 31), "R*S: need R*S < 2^31");
+    const int64_t n_out = R * (int64_t)S;
+    T_LIVE_REQUIRE(capacity >= 0 && capacity <= n_out, "capacity: need 0 <= capacity <= R*S");
     if (R == 0) return 0;
-    R2L_REQUIRE(rays_o != nullptr, "r2l_teacher_mlp_live_cfg: rays_o is NULL");
-    R2L_REQUIRE(rays_d != nullptr, "r2l_teacher_mlp_live_cfg: rays_d is NULL");
-    R2L_REQUIRE(viewdirs != nullptr, "r2l_teacher_mlp_live_cfg: viewdirs is NULL");
-    R2L_REQUIRE(z != nullptr, "r2l_teacher_mlp_live_cfg: z is NULL");
-    R2L_REQUIRE(idx != nullptr, "r2l_teacher_mlp_live_cfg: idx is NULL");
-    R2L_REQUIRE(count_dev != nullptr, "r2l_teacher_mlp_live_cfg: count_dev is NULL");
-    R2L_REQUIRE(wstream != nullptr, "r2l_teacher_mlp_live_cfg: wstream is NULL");
-    R2L_REQUIRE(params != nullptr, "r2l_teacher_mlp_live_cfg: tparams is NULL");
-    R2L_REQUIRE(raw != nullptr, "r2l_teacher_mlp_live_cfg: raw is NULL");
-    R2L_REQUIRE(((uintptr_t)raw & 15) == 0, "r2l_teacher_mlp_live_cfg: raw is not 16-byte aligned");
+    T_LIVE_REQUIRE(rays_o != nullptr, "rays_o is NULL");
+    T_LIVE_REQUIRE(rays_d != nullptr, "rays_d is NULL");
+    T_LIVE_REQUIRE(viewdirs != nullptr, "viewdirs is NULL");
+    T_LIVE_REQUIRE(z != nullptr, "z is NULL");
+    T_LIVE_REQUIRE(idx != nullptr, "idx is NULL");
+    T_LIVE_REQUIRE(count_dev != nullptr, "count_dev is NULL");
+    T_LIVE_REQUIRE(wstream != nullptr, "wstream is NULL");
+    T_LIVE_REQUIRE(params != nullptr, "tparams is NULL");
+    T_LIVE_REQUIRE(raw != nullptr, "raw is NULL");
+    T_LIVE_REQUIRE(((uintptr_t)raw & 15) == 0, "raw is not 16-byte aligned");
+#undef T_LIVE_REQUIRE
     const hipStream_t st = (hipStream_t)stream;
-    const int64_t cap = R * (int64_t)S;
-    R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)cap * 4 * sizeof(float), st));  // (sigma = +0 -> alpha = 0, as r2l_occ_scatter)
+    if (zero_fill) R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)n_out * 4 * sizeof(float), st));
+    if (capacity == 0) return 0;
+    const int64_t cap = capacity;
     const int arith = r2l_plan(cfg, cap, 0, false, false).arith_fwd;  // the capacity, as r2l_teacher_mlp_cfg asks for n_pts
     if (arith == R2L_ARITH_FP16X2) {
-        const int rc = r2l_teacher2_mlp(rays_o, rays_d, viewdirs, z, t_w2(wstream), params, raw, cap, S, st, idx, count_dev);
+        const int rc = r2l_teacher2_mlp(rays_o, rays_d, viewdirs, z, t_w2(wstream), params, raw, cap, S, st, idx, count_dev, n_out);
         if (rc) return rc;
         return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, cap, S, st,
-                                r2l_teacher2_status(t_w2(wstream)) + F2S_GO, idx, count_dev);
+                                r2l_teacher2_status(t_w2(wstream)) + F2S_GO, idx, count_dev, n_out);
     }
     if (arith == R2L_ARITH_BF16X3)
-        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, cap, S, st, nullptr, idx, count_dev);
+        return r2l_teacher3_mlp(rays_o, rays_d, viewdirs, z, t_w3(wstream), params, raw, cap, S, st, nullptr, idx, count_dev, n_out);
     TeacherArgs a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
-    a.raw = raw; a.n_pts = cap; a.S = S; a.idx = idx; a.count_dev = count_dev;
+    a.raw = raw; a.n_pts = cap; a.S = S; a.idx = idx; a.count_dev = count_dev; a.n_out = n_out;
     hipLaunchKernelGGL((r2l_teacher_mlp_kernel<false, true>), dim3(t_workgroups(cap)), dim3(256), 0, st, a);
     R2L_CHECK(hipGetLastError());
     return 0;
+}
+
+// the zero fill of raw, then the live launch over the capacity R*S
+extern "C" int r2l_teacher_mlp_live_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                        const int64_t* idx, const int64_t* count_dev, const float* wstream, const float* params,
+                                        float* raw, int64_t R, int S, void* stream, const r2l_config* cfg) {
+    const int64_t cap = R >= 0 && S >= 1 && R < ((int64_t)1 << 31) ? R * (int64_t)S : 0;  // (a bad R / S is refused inside)
+    return t_mlp_live("r2l_teacher_mlp_live_cfg", true, rays_o, rays_d, viewdirs, z, idx, count_dev, cap, wstream, params, raw, R, S, stream,
+                      cfg);
+}
+
+// the live launch alone, over `capacity` entries of idx: raw is written at the listed samples and nowhere else
+extern "C" int r2l_teacher_mlp_live_into_cfg(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
+                                             const int64_t* idx, const int64_t* count_dev, int64_t capacity, const float* wstream,
+                                             const float* params, float* raw, int64_t R, int S, void* stream, const r2l_config* cfg) {
+    return t_mlp_live("r2l_teacher_mlp_live_into_cfg", false, rays_o, rays_d, viewdirs, z, idx, count_dev, capacity, wstream, params, raw, R,
+                      S, stream, cfg);
 }
 
 // ---- teacher training: the fp32 chain with stash (the backward pass is in r2l_teacher_train.hip) ----------------------
@@ -478,7 +511,7 @@ extern "C" int r2l_teacher_mlp_train_live(const float* rays_o, const float* rays
     R2L_CHECK(hipMemsetAsync(raw, 0, (size_t)cap * 4 * sizeof(float), st));  // (sigma = +0 -> alpha = 0, as r2l_teacher_mlp_live_cfg)
     TeacherArgs a{};
     a.rays_o = rays_o; a.rays_d = rays_d; a.viewdirs = viewdirs; a.z = z; a.wstream = wstream; a.params = params;
-    a.raw = raw; a.n_pts = cap; a.S = S; a.stash = stash; a.idx = idx; a.count_dev = count_dev;
+    a.raw = raw; a.n_pts = cap; a.S = S; a.stash = stash; a.idx = idx; a.count_dev = count_dev; a.n_out = cap;
     hipLaunchKernelGGL(r2l_teacher_mlp_train_live_kernel, dim3(t_workgroups(cap)), dim3(256), 0, st, a);
     R2L_CHECK(hipGetLastError());
     return 0;

@@ -141,10 +141,12 @@ struct T16Args {
     int S;
     const int64_t* idx;        // live form only (below): the sample of every tile lane, capacity n_pts
     const int64_t* count_dev;  // live form only: how many entries of idx count (device, 1)
+    int64_t n_out;             // live form only: the entries of idx name samples in [0, n_out) (R*S; n_pts unless the list is shorter)
 };
 
 // ---- live form of the three forward kernels (r2l_teacher_mlp_live_cfg, include/r2l_hip.h) ------------------------------------
-// The launch is sized for the capacity n_pts = R*S; tile lane i < count = min(*count_dev, n_pts) takes sample n = idx[i] where the
+// The launch is sized for the capacity n_pts of the index list (R*S behind r2l_teacher_mlp_live_cfg; r2l_teacher_mlp_live_into_cfg
+// names a shorter one, and then n_out = R*S bounds the sample numbers); tile lane i < count = min(*count_dev, n_pts) takes sample n = idx[i] where the
 // plain form takes sample i, and stores at raw + 4 n.  LIVE is a template parameter of each kernel: the plain instantiations
 // compile from the code they always had.  A point is a column of its tile, so raw[n] has the bits the plain form writes at n.
 // The fp32 chain's training form (STASH) has a live instantiation too, in a kernel of its own (r2l_teacher_mlp_train_live_kernel): its
@@ -160,7 +162,7 @@ __device__ __forceinline__ bool t_live_workgroup_idle(int64_t count) {
     return (int64_t)blockIdx.x * (4 * R2L_TILE_RAYS) >= count;
 }
 // Sample of tile lane i (count >= 1).  A lane at or past the count reads row count - 1 and stores nothing, as the plain form
-// clamps to its last point; an entry outside [0, cap) reads sample 0 in its place and stores nothing.
+// clamps to its last point; an entry outside [0, cap) — cap = n_out, the samples of raw — reads sample 0 in its place and stores nothing.
 __device__ __forceinline__ int64_t t_live_sample(const int64_t* __restrict__ idx, int64_t count, int64_t cap, int64_t i, bool& valid) {
     const bool below = i < count;
     const int64_t n = idx[below ? i : count - 1];
@@ -180,12 +182,12 @@ int64_t r2l_teacher3_stream_floats(void);
 int r2l_teacher3_pack(const float* tparams, float* wstream3, hipStream_t stream);
 int r2l_teacher3_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream3, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const unsigned* run_if, const int64_t* idx = nullptr, const int64_t* count_dev = nullptr);
+                     const unsigned* run_if, const int64_t* idx = nullptr, const int64_t* count_dev = nullptr, int64_t n_out = 0);
 // r2l_teacher2.hip: three fp16 products per fp32 product (default), range-guarded; its stream follows the bf16x3 one
 int64_t r2l_teacher2_stream_floats(void);
 const unsigned* r2l_teacher2_status(const float* wstream2);
 int r2l_teacher2_pack(const float* tparams, float* wstream2, hipStream_t stream);
 int r2l_teacher2_mlp(const float* rays_o, const float* rays_d, const float* viewdirs, const float* z,
                      const float* wstream2, const float* tparams, float* raw, int64_t n_pts, int S, hipStream_t stream,
-                     const int64_t* idx = nullptr, const int64_t* count_dev = nullptr);
-// (idx / count_dev: NULL pair = the plain form; else the live form over the capacity n_pts)
+                     const int64_t* idx = nullptr, const int64_t* count_dev = nullptr, int64_t n_out = 0);
+// (idx / count_dev: NULL pair = the plain form; else the live form over the capacity n_pts, sample numbers below n_out — 0: n_pts)

@@ -19,7 +19,7 @@ from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import (parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_image_store,
-                      validate_occ_fused, validate_occupancy, validate_store_file)
+                      validate_ert, validate_occ_fused, validate_occupancy, validate_store_file)
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -751,7 +751,7 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         else:
             loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
         filler = TeacherFill(loader, targs, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                             rand_pose=scene.rand_pose, ndc=scene.ndc, occ_args=args if args.r2l_occ_fused else None)
+                             rand_pose=scene.rand_pose, ndc=scene.ndc, occ_args=args if (args.r2l_occ_fused or args.r2l_ert > 0) else None)
         # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
         # number, so these are the same rows bit for bit
         n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
@@ -854,12 +854,14 @@ def main(argv=None):
     if is_teacher:
         validate_occupancy(args, raw_noise_std=0.)  # (the teacher's test render runs without noise; student runs ignore the switch)
         validate_occ_fused(args, ("r2l_fused_frames",), raw_noise_std=0.)
-    elif args.r2l_occ_fused:  # the teacher of the online fill: its config says whether it has view directions (its raw_noise_std
+        validate_ert(args, ("r2l_fused_frames",), raw_noise_std=0.)
+    elif args.r2l_occ_fused or args.r2l_ert != 0:  # the teacher of the online fill: its config says whether it has view directions (its raw_noise_std
         targs_ = None         # is 0, or parse_teacher_config refuses it)
         if args.r2l_online_kd and args.r2l_teacher_config:
             from .options import parse_teacher_config
             targs_ = parse_teacher_config(args.r2l_teacher_config)
         validate_occ_fused(args, ("r2l_online_kd",), raw_noise_std=0., use_viewdirs=targs_.use_viewdirs if targs_ is not None else True)
+        validate_ert(args, ("r2l_online_kd",), raw_noise_std=0., use_viewdirs=targs_.use_viewdirs if targs_ is not None else True)
     rank, world, device = init_distributed()
     if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
         raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
@@ -899,7 +901,7 @@ def main(argv=None):
         if args.r2l_occupancy:  # both grids once, behind --r2l_precision
             from .occupancy import build_pair
             kwargs_test["occupancy"] = build_pair(args, model, kwargs_test["network_fine"], near, far, logger)
-        if args.r2l_occ_fused:  # the same grids inside the fused frames calls of render_path
+        if args.r2l_occ_fused or args.r2l_ert > 0:  # the same grids / early termination inside the fused frames calls of render_path
             from .occupancy import FusedOccupancy
             teacher["occ_fused"] = FusedOccupancy(args, model, kwargs_test["network_fine"], near, far, logger)
     else:

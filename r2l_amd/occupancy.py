@@ -435,26 +435,43 @@ def build_pair(args, coarse, fine, near, far, logger):
     return tuple(grids)
 
 
+def fused_skipping(args):
+    """Whether a run skips samples inside the fused frames call: --r2l_occ_fused (grids), --r2l_ert (early termination), or both."""
+    return bool(args.r2l_occ_fused) or args.r2l_ert > 0
+
+
 class FusedOccupancy:
-    """The grids of a run with --r2l_occ_fused: the pair build_pair makes, and the device counters the fused frames calls add
-    their live and total samples to (render_frames(occupancy=, live_acc=)).  Nothing is read per frame: log() reads the two
-    counters once, when the run's frames are done."""
+    """What a run skips inside the fused frames call: the grids of --r2l_occ_fused (the pair build_pair makes), the early
+    termination of --r2l_ert EPS / --r2l_ert_seg W (r2l_amd/ert.py), or both, and the device counters the frames calls add their live
+    and total samples to (render_frames(occupancy=, ert=, live_acc=)).  Nothing is read per frame: log() reads the two counters
+    once, when the run's frames are done."""
 
     def __init__(self, args, coarse, fine, near, far, logger):
-        self.pair = build_pair(args, coarse, fine, near, far, logger)
+        self.pair = build_pair(args, coarse, fine, near, far, logger) if args.r2l_occ_fused else None
         self.bound = box_half_side(args, near, far)
-        self.live_acc = torch.zeros(2, dtype=torch.int64, device=self.pair[0].bits.device)
+        self.ert = (float(args.r2l_ert), int(args.r2l_ert_seg)) if args.r2l_ert > 0 else None
+        self.live_acc = torch.zeros(2, dtype=torch.int64, device=next(coarse.parameters()).device)
 
     def kwargs(self):
-        return {"occupancy": self.pair, "live_acc": self.live_acc}
+        return {"live_acc": self.live_acc, **({"occupancy": self.pair} if self.pair is not None else {}),
+                **({"ert": self.ert} if self.ert is not None else {})}
 
     def provenance(self):
-        g = self.pair[0]
-        return {"res": g.G, "bound": self.bound, "k": g.k, "dilate": g.dilate}
+        """The entries a store file's provenance gains: 'occupancy' with the grids, 'ert' with early termination."""
+        out = {}
+        if self.pair is not None:
+            g = self.pair[0]
+            out["occupancy"] = {"res": g.G, "bound": self.bound, "k": g.k, "dilate": g.dilate}
+        if self.ert is not None:
+            out["ert"] = {"eps": self.ert[0], "seg": self.ert[1]}
+        return out
 
     def log(self, logger):
         a, b = (int(x) for x in self.live_acc.tolist())  # the one read of the run
-        logger.info("occupancy grid: live points %d / %d (%.1f%%)" % (a, b, 100. * a / max(b, 1)))
+        if self.ert is not None:  # (the one line of such a run; without grids b counts the last pass alone)
+            logger.info("early termination: eps %g, seg %d, live points %d / %d (%.1f%%)" % (self.ert[0], self.ert[1], a, b, 100. * a / max(b, 1)))
+        else:
+            logger.info("occupancy grid: live points %d / %d (%.1f%%)" % (a, b, 100. * a / max(b, 1)))
         return a, b
 
 

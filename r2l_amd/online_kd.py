@@ -64,12 +64,12 @@ class TeacherFill:
         self.r2l_config = None  # the record apply_arithmetic returns (precision of the teacher kernels): provenance()
         if logger is not None:
             self.r2l_config = apply_arithmetic(targs, self.device, logger, teachers=(self.coarse, self.fine))
-        # --r2l_occ_fused (occ_args: the namespace that carries r2l_occ_res / r2l_occ_bound): both grids once, behind the
-        # arithmetic switch; the build is deterministic, so a re-run renders the same store
+        # --r2l_occ_fused / --r2l_ert (occ_args: the namespace that carries r2l_occ_res / r2l_occ_bound / r2l_ert / r2l_ert_seg):
+        # both grids once, behind the arithmetic switch; the build and the render are deterministic, so a re-run renders the same store
         self.occ = self.occ_prov = None
         if occ_args is not None:
             from .occupancy import FusedOccupancy
-            if self.ndc:
+            if self.ndc and occ_args.r2l_occ_fused:
                 raise ValueError("--r2l_occ_fused puts its box about the origin of a bounded scene: not with an NDC (llff) scene")
             self.occ = FusedOccupancy(occ_args, self.coarse, self.fine, self.near, self.far, _Quiet() if logger is None else logger)
             self.occ_prov = self.occ.provenance()  # (kept: the grids go with the teacher in release())
@@ -95,7 +95,7 @@ class TeacherFill:
                 "white_bkgd": bool(a.white_bkgd), "use_rand_focal": bool(a.use_rand_focal), "n_pose": self.n_pose,
                 "create_data_chunk": self.chunk, "near": self.near, "far": self.far, "ndc": self.ndc, "focal": self.focal,
                 "precision": (self.r2l_config or {}).get("precision", a.r2l_precision), "R2L_SEED": os.environ.get("R2L_SEED", "0"),
-                **({"occupancy": self.occ_prov} if self.occ_prov is not None else {})}
+                **(self.occ_prov or {})}
 
     def fill_group(self):
         """Render the next flush group into the store; returns the number of shards it added."""

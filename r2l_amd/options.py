@@ -67,6 +67,12 @@ FLAGS = {
     # main.py --model_name nerf --render_only with --r2l_fused_frames, main.py --r2l_online_kd.  Shares r2l_occ_res / r2l_occ_bound;
     # not together with --r2l_occupancy (the per-pose path), nor with llff or raw_noise_std > 0.  utils/train_nerf.py ignores it
     "r2l_occ_fused": ("flag", False),
+    # early ray termination in the last pass of the FUSED frames call (r2l_teacher_frames_ert_cfg; r2l_amd/ert.py): the pass is walked
+    # front to back in segments of r2l_ert_seg samples and a ray whose transmittance is below r2l_ert (0 = off, at most 0.1) at a
+    # segment boundary leaves the segments behind it; a pixel moves by less than r2l_ert.  The paths of r2l_occ_fused, with it or
+    # without; with --dataset_type llff only without it (no box is needed: the first way to skip samples in NDC space).  Not with
+    # --r2l_occupancy, raw_noise_std > 0 or a teacher without view directions.  utils/train_nerf.py ignores both
+    "r2l_ert": (float, 0.), "r2l_ert_seg": (int, 32),
     # the grids while the teacher TRAINS (utils/train_nerf.py only; r2l_teacher_mlp_train_live / r2l_teacher_backward_live /
     # r2l_teacher_train_step_occ): forward and backward of every step run on the live samples, the live counts stay on the device.
     # Shares r2l_occ_res / r2l_occ_bound; r2l_occ_every: a refresh of both grids from the current weights every so many iterations
@@ -370,6 +376,28 @@ def validate_occ_fused(args, paths, raw_noise_std=None, use_viewdirs=None):
         raise ValueError("--r2l_occ_fused: --r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
     if not (args.use_viewdirs if use_viewdirs is None else use_viewdirs):
         raise ValueError("--r2l_occ_fused needs a teacher with --use_viewdirs (the teacher kernels' network)")
+
+
+def validate_ert(args, paths, raw_noise_std=None, use_viewdirs=None):
+    """--r2l_ert EPS / --r2l_ert_seg W: early ray termination in the last pass of the fused frames call.  Arguments as
+    validate_occ_fused's; returns (eps, seg), or None with the switch off.  Names the flag, before anything is loaded."""
+    if args.r2l_ert == 0:
+        return None
+    if not 0. < args.r2l_ert <= 0.1:
+        raise ValueError("--r2l_ert must be in (0, 0.1] (0: off), got %g" % args.r2l_ert)
+    if args.r2l_ert_seg < 8:
+        raise ValueError("--r2l_ert_seg must be >= 8, got %d" % args.r2l_ert_seg)
+    if args.r2l_occupancy:
+        raise ValueError("--r2l_ert acts inside the fused frames call, --r2l_occupancy in the per-pose render: not --r2l_ert with "
+                         "--r2l_occupancy (--r2l_occ_fused is the grids' switch of that call)")
+    if not any(getattr(args, p) for p in paths):
+        raise ValueError("--r2l_ert acts inside the fused frames call: it needs %s" % " or ".join("--" + p for p in paths))
+    if (args.raw_noise_std if raw_noise_std is None else raw_noise_std) > 0:
+        raise ValueError("--r2l_ert with raw_noise_std > 0: the transmittance of the walk is that of the noiseless sigma (pass "
+                         "--raw_noise_std 0)")
+    if not (args.use_viewdirs if use_viewdirs is None else use_viewdirs):
+        raise ValueError("--r2l_ert needs a teacher with --use_viewdirs (the teacher kernels' network)")
+    return float(args.r2l_ert), int(args.r2l_ert_seg)
 
 
 def validate_compact_store(args):

@@ -339,14 +339,22 @@ def _coarse_z(near, far, N_samples, lindisp, perturb, pytest, t_rand=None):
 
 def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False, lindisp=False, perturb=0.,
                 N_importance=0, network_fine=None, white_bkgd=False, raw_noise_std=0., verbose=False, pytest=False,
-                t_rand=None, u=None, occupancy=None):
+                t_rand=None, u=None, occupancy=None, ert=None, live_acc=None):
     """Volumetric rendering of ray_batch[R, 8|11] = [o, d, near, far, (viewdirs)]  (create_data.py:405-544).
     Returns the reference's dict: rgb_map, disp_map, acc_map, depth_map, (raw), and with N_importance > 0 also
     rgb0, disp0, acc0, z_std.  t_rand / u override the random draws (tests).
     occupancy = (grid_for_network_fn, grid_for_network_fine), two built r2l_amd.occupancy.OccupancyGrid: only the samples that are
     live in the pass's grid go through the point network, the others keep raw = 0 (OccupancyGrid.query: compact, one 8-byte read
     of the live count — the one synchronisation this adds per launch —, the network on the live rows, scatter); the grids count
-    live and total points.  Not with raw_noise_std > 0: noise can lift an empty sample above zero."""
+    live and total points.  Not with raw_noise_std > 0: noise can lift an empty sample above zero.
+    ert = (eps, seg): early ray termination in the LAST pass (r2l_amd.ert.ert_query: the pass is walked front to back in segments of
+    `seg` samples and a ray whose transmittance is below eps at a segment boundary is left out of the segments behind it; with
+    occupancy= the pass's grid applies too).  The coarse pass and the fine depths are untouched, a pixel moves by at most the
+    transmittance at the cut.  On the GPU nothing is read on the host in this form — the passes with a grid go through
+    OccupancyGrid.index and TeacherEngine.mlp_live —, and live_acc (int64[2] on the rays' device) receives += (live, all) samples
+    of every pass that has an index list (without grids: the last pass only); the grids' own counters stay as they are.  On CPU
+    tensors the full raw is evaluated and the mask applied.  The returned dict gains 'ert_trans', the transmittances the walk held at
+    its segment boundaries.  Not with raw_noise_std > 0, not without view directions."""
     rays_o, rays_d = ray_batch[:, 0:3].contiguous(), ray_batch[:, 3:6].contiguous()
     viewdirs = ray_batch[:, -3:].contiguous() if ray_batch.shape[-1] > 8 else None
     near, far = ray_batch[:, 6:7].contiguous(), ray_batch[:, 7:8].contiguous()
@@ -356,10 +364,28 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         if viewdirs is None:
             raise NotImplementedError("render_rays: occupancy needs use_viewdirs=True (the compacted rows carry viewdirs)")
         grid_coarse, grid_fine = occupancy
+    if ert is not None:
+        from . import ert as _ert
+        ert = _ert.check_staged(*ert)
+        if raw_noise_std > 0.:
+            raise ValueError("render_rays: ert with raw_noise_std > 0 — the transmittance of the walk is that of the noiseless sigma")
+        if viewdirs is None:
+            raise ValueError("render_rays: ert needs use_viewdirs=True (the point network's index form carries viewdirs)")
+    elif live_acc is not None:
+        raise ValueError("render_rays: live_acc without ert")
+    ert_trans = None
     z_vals = _coarse_z(near, far, N_samples, lindisp, perturb, pytest, t_rand)
     on_gpu = ray_batch.is_cuda
 
-    def query(z, net, grid=None):
+    def query(z, net, grid=None, last=False):
+        nonlocal ert_trans
+        if ert is not None and last:
+            raw, ert_trans = _ert.ert_query(net, rays_o, rays_d, viewdirs, z, ert[0], ert[1], grid=grid, live_acc=live_acc,
+                                            network_query_fn=network_query_fn)
+            return raw
+        if ert is not None and grid is not None and on_gpu:  # (no read on the host in the ert form)
+            idx, count = grid.index(rays_o, rays_d, z, live_acc=live_acc)
+            return teacher_engine(net).mlp_live(rays_o, rays_d, viewdirs, z, idx, count)
         if grid is not None:
             return grid.query(net, rays_o, rays_d, viewdirs, z, network_query_fn)
         if on_gpu:
@@ -369,14 +395,14 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         pts = rays_o[..., None, :] + rays_d[..., None, :] * z[..., :, None]
         return network_query_fn(pts, viewdirs, net)
 
-    raw = query(z_vals, network_fn, None if occupancy is None else grid_coarse)
+    raw = query(z_vals, network_fn, None if occupancy is None else grid_coarse, last=N_importance <= 0)
     rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd,
                                                                  pytest=pytest)
     if N_importance > 0:
         rgb0, disp0, acc0 = rgb_map, disp_map, acc_map
         z_samples, z_vals, z_std = sample_pdf_sort(z_vals, weights, N_importance, det=(perturb == 0.), pytest=pytest,
                                                    u=u)
-        raw = query(z_vals, network_fn if network_fine is None else network_fine, None if occupancy is None else grid_fine)
+        raw = query(z_vals, network_fn if network_fine is None else network_fine, None if occupancy is None else grid_fine, last=True)
         rgb_map, disp_map, acc_map, weights, depth_map = raw2outputs(raw, z_vals, rays_d, raw_noise_std, white_bkgd,
                                                                      pytest=pytest, need_weights=False)
     ret = {"rgb_map": rgb_map, "disp_map": disp_map, "acc_map": acc_map, "depth_map": depth_map}
@@ -384,6 +410,8 @@ def render_rays(ray_batch, network_fn, network_query_fn, N_samples, retraw=False
         ret["raw"] = raw
     if N_importance > 0:
         ret.update(rgb0=rgb0, disp0=disp0, acc0=acc0, z_std=z_std)
+    if ert is not None:
+        ret["ert_trans"] = ert_trans
     return ret
 
 
@@ -492,7 +520,7 @@ def draw_normal(n, seed, stream_id, device, scale=1.):
 
 
 def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samples, N_importance, perturb, white_bkgd, seed,
-                  frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None, occupancy=None, live_acc=None):
+                  frame_id0=0, chunk=0, rows=False, ndc=False, ndc_focal=None, occupancy=None, live_acc=None, ert=None):
     """K teacher frames from K poses in ONE library call (r2l_teacher_frames_cfg): what render(H, W, focal_k, c2w=c2ws[k],
     ndc=False, near=, far=, use_viewdirs=True, ...) computes per pose, with the random draws of perturb > 0 made on the device
     by draw_uniform (frame k: t_rand = stream 2*(frame_id0+k), u = stream 2*(frame_id0+k)+1 of `seed`).  GPU only.
@@ -505,7 +533,9 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
     occupancy = (grid_coarse, grid_fine), two built r2l_amd.occupancy.OccupancyGrid (the same one twice when the coarse net serves
     both passes): r2l_teacher_frames_occ_cfg — each pass sends only its live samples through the point network, the live count
     never leaves the device.  live_acc: None or an int64[2] device tensor that receives += (live, all) samples of every pass; the
-    caller reads it when it wants the share (one read per run, not per frame).  Not with ndc=True: the box is in world space."""
+    caller reads it when it wants the share (one read per run, not per frame).  Not with ndc=True: the box is in world space.
+    ert = (eps, seg): early ray termination in the last pass of every chunk (r2l_teacher_frames_ert_cfg; render_rays(ert=) per pose,
+    bit for bit), with occupancy= or without — without, ndc=True is allowed and live_acc counts the last pass alone."""
     c2ws = _pose_table(c2ws, next(network_fn.parameters()).device)
     _need_gpu(c2ws, "render_frames")
     dev = c2ws.device
@@ -532,10 +562,18 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
                 raise ValueError("render_frames: occupancy needs two grids built on %s" % dev)
         if live_acc is not None and (live_acc.dtype != torch.int64 or live_acc.numel() != 2 or live_acc.device != dev):
             raise ValueError("render_frames: live_acc must be an int64[2] tensor on %s" % dev)
-    elif live_acc is not None:
+    elif live_acc is not None and ert is None:
         raise ValueError("render_frames: live_acc without occupancy")
-    size_fn = lib.r2l_teacher_frames_work_floats if occupancy is None else lib.r2l_teacher_frames_occ_work_floats
-    n_work = size_fn(ctypes.byref(desc))
+    elif live_acc is not None and (live_acc.dtype != torch.int64 or live_acc.numel() != 2 or live_acc.device != dev):
+        raise ValueError("render_frames: live_acc must be an int64[2] tensor on %s" % dev)
+    if ert is not None:
+        from . import ert as _ert
+        eps, seg = _ert.check(*ert)
+        edesc = _lib.ErtDesc(eps=eps, seg=seg)
+        n_work = lib.r2l_teacher_frames_ert_work_floats(ctypes.byref(desc), ctypes.byref(edesc))
+    else:
+        size_fn = lib.r2l_teacher_frames_work_floats if occupancy is None else lib.r2l_teacher_frames_occ_work_floats
+        n_work = size_fn(ctypes.byref(desc))
     if n_work < 0:
         _lib.check(1, "r2l_teacher_frames_work_floats")
     work = getattr(coarse, "_frames_work", None)  # kept on the engine: frames of one size re-use it
@@ -553,7 +591,12 @@ def render_frames(c2ws, H, W, focal, near, far, network_fn, network_fine, N_samp
             _ptr(out["rgb"]), _ptr(out["disp"]), _ptr(out["acc"]), _ptr(out["depth"]), _ptr(out["rgb0"]))
     tail = (_ptr(work), _stream(), ctypes.byref(_engine.merged_config(coarse.cfg)))
     with torch.cuda.device(dev):
-        if occupancy is None:
+        if ert is not None:
+            gc, gf = occupancy if occupancy is not None else (None, None)
+            _lib.check(lib.r2l_teacher_frames_ert_cfg(*head, None if gc is None else ctypes.byref(gc.desc()),
+                                                      None if gf is gc else ctypes.byref(gf.desc()), _ptr(live_acc), ctypes.byref(edesc),
+                                                      *tail), "r2l_teacher_frames_ert_cfg")
+        elif occupancy is None:
             _lib.check(lib.r2l_teacher_frames_cfg(*head, *tail), "r2l_teacher_frames_cfg")
         else:
             gc, gf = occupancy

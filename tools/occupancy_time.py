@@ -14,6 +14,15 @@ floor: the capacity-sized grid of workgroups that leave at once, the index launc
 rounds alternated a -> b -> c -> d; the live share of (b) from its device counters and the spread between rounds.
 
     python tools/occupancy_time.py --fused --out profiles/occupancy_fused.txt
+
+--ert: early ray termination in the last pass of the fused frames call (render_frames(ert=(eps, seg)), r2l_teacher_frames_ert_cfg).
+Same frame, pair and boxes, chunk 32 768; ms per frame of (a) the grids alone (r2l_teacher_frames_occ_cfg: the baseline), (b) grids +
+termination at eps 1e-3 with seg 16, 32, 64, (c) termination without grids, seg 32, next to the frame without either, (d) grids +
+termination with seg 256: one segment, nothing terminated — the cost of the mechanism; three rounds alternated over all paths.  The
+live shares from the device counters, PSNR and max |d RGB| of (b) against (a), and r2l_ert_advance / r2l_occ_index_seg alone on one
+chunk's fine pass (32 768 rays x 192 samples, one segment of 32).
+
+    python tools/occupancy_time.py --ert --out profiles/ert.txt
 """
 import argparse
 import math
@@ -87,6 +96,74 @@ def fused_report(a, nets, H, W, focal, c2w, dev):
     return lines
 
 
+def ert_report(a, nets, H, W, focal, c2w, dev):
+    """The lines of --ert (see the module docstring)."""
+    from r2l_amd import _lib, ert as E
+    med = lambda v: sorted(v)[len(v) // 2]
+    EPS = 1e-3
+
+    def frames(occ, ert, acc):
+        return render.render_frames(c2w[None], H, W, focal, 2., 6., nets[0], nets[1], 64, 128, 0., True, seed=0, chunk=32768,
+                                    occupancy=occ, live_acc=acc, ert=ert)["rgb"]
+
+    lines = ["teacher frames, %d x %d, 64+128 samples, chunk 32768, perturb 0, precision %s (%s), trained-like pair of tests/teacher_util.py, %s"
+             % (H, W, a.precision, engine.arithmetic(render.teacher_engine(nets[0]).cfg)["precision"], torch.cuda.get_device_name(0)),
+             "grid %d^3 cells x 2 probes per cell and axis x dilation 1; eps %g; ms/frame by device events, one process, rounds alternated "
+             "over all paths" % (a.res, EPS),
+             "(a) grids only (the baseline)   (b16/b32/b64) grids + early termination, seg 16 / 32 / 64   (c) early termination without "
+             "grids, seg 32   (n) neither   (d) grids + early termination, seg 256: one segment, nothing terminated",
+             "The scene is analytic: an opaque shell at r = 1 stops every ray that meets it, so the gain below is NOT that of a published scene."]
+    with torch.no_grad():
+        for box in (1.6, 2.5):
+            pair = tuple(OC.OccupancyGrid([-box] * 3, [box] * 3, G=a.res).build(n) for n in nets)
+            accs = {k: torch.zeros(2, dtype=torch.int64, device=dev) for k in ("a", "b16", "b32", "b64", "c", "d")}
+            paths = {"a": lambda: frames(pair, None, accs["a"]), "b16": lambda: frames(pair, (EPS, 16), accs["b16"]),
+                     "b32": lambda: frames(pair, (EPS, 32), accs["b32"]), "b64": lambda: frames(pair, (EPS, 64), accs["b64"]),
+                     "c": lambda: frames(None, (EPS, 32), accs["c"]), "n": lambda: frames(None, None, None),
+                     "d": lambda: frames(pair, (EPS, 256), accs["d"])}
+            for fn in paths.values():
+                fn()  # warm-up
+            for t in accs.values():
+                t.zero_()
+            ms, out = {k: [] for k in paths}, {}
+            for _ in range(a.rounds):
+                for k, fn in paths.items():
+                    t, out[k] = timed(fn)
+                    ms[k].append(t)
+            lines.append("box +-%.1f: occupied cells %.1f %% (coarse net) / %.1f %% (fine net)" %
+                         (box, 100 * pair[0].occupied_share(), 100 * pair[1].occupied_share()))
+            for k, v in ms.items():
+                share = ""
+                if k in accs:
+                    live, total = (int(x) for x in accs[k].tolist())
+                    share = "; live points %.1f %% (%d / %d)" % (100. * live / max(total, 1), live, total)
+                lines.append("  (%-3s) %s   median %.2f, spread %.2f%s" % (k, "  ".join("%.2f" % x for x in v), med(v), max(v) - min(v), share))
+            for k in ("b16", "b32", "b64"):
+                diff = (out[k] - out["a"]).abs()
+                mse = float((diff.double()**2).mean())
+                lines.append("  (%s) / (a) %.3f; max |d RGB| against (a) %.3e, PSNR %s dB" %
+                             (k, med(ms[k]) / med(ms["a"]), float(diff.max()), "inf" if mse == 0 else "%.2f" % (-10. * math.log10(mse))))
+            lines.append("  (c) / (n) %.3f; (d) - (a) %+.2f ms (the extra launches with nothing terminated); (d) equals (a) bit for bit: %s" %
+                         (med(ms["c"]) / med(ms["n"]), med(ms["d"]) - med(ms["a"]), bool(torch.equal(out["d"], out["a"]))))
+        # the two new kernels alone, on the fine pass of one chunk
+        rays = scene_rays(H * W, 0, H=H, W=W, focal=focal)[::max(H * W // 32768, 1)][:32768].to(dev)
+        o, d, vd = rays[:, 0:3].contiguous(), rays[:, 3:6].contiguous(), rays[:, 8:11].contiguous()
+        n = rays.shape[0]
+        z = torch.linspace(2., 6., 192, device=dev).expand(n, 192).contiguous()
+        raw = render.teacher_engine(nets[1]).mlp(o, d, vd, z)
+        trans = torch.empty(n, device=dev)
+        idx = torch.empty(n * 32, dtype=torch.int64, device=dev)
+        cnt = torch.empty(1, dtype=torch.int64, device=dev)
+        work = torch.empty(max(_lib.load().r2l_occ_index_seg_work_bytes(n * 32), 16), dtype=torch.uint8, device=dev)
+        E.advance(raw, z, d, 0, 64, trans)
+        ta = [timed(lambda: E.advance(raw, z, d, 64, 96, trans))[0] for _ in range(5)]
+        ti = [timed(lambda: E.index_seg(pair[1], o, d, z, 96, 128, trans, EPS, idx, cnt, work))[0] for _ in range(5)]
+        tn = [timed(lambda: E.index_seg(None, o, d, z, 96, 128, trans, EPS, idx, cnt, work))[0] for _ in range(5)]
+        lines.append("one chunk's fine pass (%d rays x 192 samples), one segment of 32: r2l_ert_advance %.3f ms, r2l_occ_index_seg %.3f ms with "
+                     "the grid, %.3f ms without (3 launches; %d of %d live; medians of 5)" % (n, med(ta), med(ti), med(tn), int(cnt[0]), n * 32))
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--size", type=int, default=400)
@@ -95,6 +172,7 @@ def main():
     ap.add_argument("--precision", default="auto", choices=["auto", "fp16x2", "bf16x3", "fp32_mfma"])
     ap.add_argument("--out", default="")
     ap.add_argument("--fused", action="store_true", help="time the grids inside the fused frames call (profiles/occupancy_fused.txt)")
+    ap.add_argument("--ert", action="store_true", help="time early ray termination in the fused frames call (profiles/ert.txt)")
     a = ap.parse_args()
     dev = "cuda:0"
     nets = []
@@ -109,8 +187,8 @@ def main():
     H = W = a.size
     focal = 555.5555155968841 * a.size / 400.
     c2w = torch.from_numpy(O.pose_spherical(35., -25., 4.)[:3, :4]).to(dev)
-    if a.fused:
-        text = "\n".join(fused_report(a, nets, H, W, focal, c2w, dev))
+    if a.fused or a.ert:
+        text = "\n".join((ert_report if a.ert else fused_report)(a, nets, H, W, focal, c2w, dev))
         print(text)
         if a.out:
             with open(os.path.abspath(a.out), "w") as f:
