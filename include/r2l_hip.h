@@ -537,6 +537,45 @@ int r2l_occ_index(const r2l_occ_grid* grid, const float* rays_o, const float* ra
  * the call that wrote *count.  No atomics: calls on one stream add up exactly.  Refused: a NULL pointer, total < 0. */
 int r2l_occ_live_add(const int64_t* count /*device, 1*/, int64_t total, int64_t* live_acc, void* stream);
 
+/* ---- whole rays: does a ray meet an occupied cell? ---------------------------------------------------------------------------------
+ * A light-field network cannot skip samples; whole rays are the only work it can leave out.  r2l_occ_rays asks the grid per RAY:
+ * ray r is live iff any of the T points p_j = rays_o[r] + rays_d[r] * t_j, j < T, is live by the point rule pinned under
+ * r2l_occ_grid above (outside the box or not finite: live; inside: the cell's bit), with
+ *   dt = (far - near) / (float)T  (host fp32);   t_j = near + ((float)j + 0.5f) * dt
+ * every operation rounded separately, product and sum of the point formed exactly as r2l_occ_index forms its point.  The call is
+ * therefore SPECIFIED BY r2l_occ_index: with z[r, j] = t_j for all rays, ray r is live iff r2l_occ_index lists any sample n in
+ * [r*T, (r+1)*T).  z[R,T] is never built: a sub-wave of 16 lanes steps a ray's depths and leaves at the first hit.
+ * idx_out[0..M) = the live ray numbers in ASCENDING order (capacity R; entries >= M are not written), *count_out (device int64) = M,
+ * live_out (optional, [R] bytes) = 0 or 1 per ray.  Three launches on `stream` — flag + count per 2048 rays, the scan of
+ * r2l_occ_index, placement —, no atomics, no synchronisation, stateless: two calls give the same bits.  work:
+ * r2l_occ_rays_work_bytes(R) bytes (-1 for R < 0 or R >= 2^31), 4-byte aligned.  R == 0 is a successful no-op that sets
+ * *count_out = 0.  Refused before any launch: a NULL grid / pointer (live_out may be NULL), R < 0, R >= 2^31, T < 1, near or far not
+ * finite, far < near, far - near out of fp32 range, a grid that r2l_occ_build would refuse, a misaligned work.
+ *
+ * WHY A DEAD RAY IS BACKGROUND (host side; r2l_amd/occupancy.py cull_steps, rays_spec).  Let the grid be dilated by at least one
+ * cell and T be the smallest count with (far - near) / T * d_max <= the smallest cell side, d_max >= |rays_d[r]|.  Consecutive
+ * sample points are then at most one cell side apart, so every point x of the segment [near, far] of a dead ray lies within half a
+ * cell of a sample s.  s is inside the box and in a clear cell; x's cell differs from s's by at most one along each axis, so it was
+ * clear BEFORE the dilation, or x is at most half a cell outside the box.  A dead ray meets no cell in which a build probe had
+ * sigma > sigma_thresh: raw2outputs gives it acc = 0 and the background colour (0, or 1 - acc = 1 with white_bkgd) up to what the
+ * probes missed.  For the rays of a frame d_max = sqrt(1 + (W/(2 f))^2 + (H/(2 f))^2), f the smallest focal in use. */
+int64_t r2l_occ_rays_work_bytes(int64_t R);
+int r2l_occ_rays(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, int64_t R, float near, float far, int T,
+                 int64_t* idx_out /*[R]*/, int64_t* count_out /*device, 1*/, uint8_t* live_out /*[R] or NULL*/, void* work,
+                 void* stream);
+/* The two small kernels of a culled render (r2l_frame_rays -> r2l_occ_rays -> read M -> r2l_rays_gather -> r2l_forward_rays_cfg on
+ * M rays -> r2l_rgb_scatter_bg), one launch each:
+ *   r2l_rays_gather: out_o[i], out_d[i] = rays_o[idx[i]], rays_d[idx[i]] for i < M; an index outside [0, R) gives a NaN row and
+ *     reads nothing.  M == 0 is a successful no-op.
+ *   r2l_rgb_scatter_bg: rgb_out[r] = (bg, bg, bg) for every ray with live[r] == 0, and rgb_out[idx[i]] = rgb_live[i] for i < M (an
+ *     index outside [0, R) writes nothing).  idx and live must come from ONE r2l_occ_rays call, so that no row is written twice;
+ *     rows of live rays that idx does not list are left alone.  M == 0 needs neither rgb_live nor idx.
+ * Refused: R or M negative or >= 2^31, M > R (scatter), a NaN bg, a NULL pointer that is needed. */
+int r2l_rays_gather(const float* rays_o, const float* rays_d, int64_t R, const int64_t* idx, int64_t M, float* out_o /*[M,3]*/,
+                    float* out_d /*[M,3]*/, void* stream);
+int r2l_rgb_scatter_bg(const float* rgb_live /*[M,3]*/, const int64_t* idx /*[M]*/, int64_t M, const uint8_t* live /*[R]*/, float bg,
+                       float* rgb_out /*[R,3]*/, int64_t R, void* stream);
+
 /* The point network on an index list with a device count.  raw[R,S,4] is zero-filled first (a memset, as r2l_occ_scatter); then for
  * i < min(*count_dev, R*S) and n = idx[i]:  raw[n] = net(rays_o[n/S] + rays_d[n/S] * z[n], viewdirs[n/S]), the point formed with
  * product and sum rounded separately.  An idx[i] outside [0, R*S) reads and writes nothing at that number; nothing outside
@@ -810,6 +849,15 @@ int r2l_store_append_images(const float* images /*dev [K,H,W,3]*/, const float* 
                             const float* focal_dev /*[K] or NULL*/, float focal, int K, int H, int W,
                             float* store, int64_t capacity_shards, int64_t first_shard, int64_t rays_per_shard,
                             uint64_t key, int shuffle, int64_t* n_written_out, void* stream);
+/*   r2l_store_append_live: r2l_store_append of the M rows rows_in[idx[0..M)] (idx: device, e.g. the live rays of r2l_occ_rays),
+ *     without the gathered intermediate: output row i < m * rays_per_shard is input row idx[pi(key, M)(i)], m = floor(M /
+ *     rays_per_shard), the tail of the permuted sequence dropped, *n_written_out = m.  BIT FOR BIT what a gather of the M rows
+ *     followed by r2l_store_append(n_rows = M, key) gives, in one launch.  An index outside [0, n_rows) writes a NaN row and reads
+ *     nothing.  Refused: what r2l_store_append refuses (with M in the place of its n_rows), M < 0, a NULL idx with M > 0.
+ *     r2l_amd/raystore.py (append_live_spec) restates it in numpy. */
+int r2l_store_append_live(const float* rows_in /*[n_rows,9]*/, int64_t n_rows, const int64_t* idx /*[M]*/, int64_t M, float* store,
+                          int64_t capacity_shards, int64_t first_shard, int64_t rays_per_shard, uint64_t key, int shuffle,
+                          int64_t* n_written_out, void* stream);
 
 /* ---- compact ray store (16 bytes a ray; o and d recomputed per draw) ------------------------------------------------------------
  * A store that the TEACHER fills is redundant at 36 bytes a ray: every row of a flush group comes from r2l_teacher_frames_cfg,

@@ -180,6 +180,11 @@ SIGNATURES = {
     "r2l_occ_index_work_bytes": (_l, [_l]),
     "r2l_occ_index": (_i, [_occp] + [_p] * 3 + [_l, _i] + [_p] * 4),
     "r2l_occ_live_add": (_i, [_p, _l, _p, _p]),
+    "r2l_occ_rays_work_bytes": (_l, [_l]),
+    "r2l_occ_rays": (_i, [_occp, _p, _p, _l, _f, _f, _i, _p, _p, _p, _p, _p]),
+    "r2l_rays_gather": (_i, [_p, _p, _l, _p, _l, _p, _p, _p]),
+    "r2l_rgb_scatter_bg": (_i, [_p, _p, _l, _p, _f, _p, _l, _p]),
+    "r2l_store_append_live": (_i, [_p, _l, _p, _l, _p, _l, _l, _l, ctypes.c_uint64, _i, _p, _p]),
     "r2l_teacher_mlp_live_cfg": (_i, [_p] * 9 + [_l, _i, _p, _cfgp]),
     "r2l_teacher_frames_occ_work_floats": (_l, [_descp]),
     "r2l_teacher_frames_occ_cfg": (_i, [_p, _p, _i, _descp] + [_p] * 12 + [_occp, _occp, _p, _p, _p, _cfgp]),

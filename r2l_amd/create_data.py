@@ -23,7 +23,7 @@ from .checkpoint import load_weights
 from .driver import _runs, apply_arithmetic, init_distributed, sync
 from .logger import Logger
 from .nerf_raybased import NeRF
-from .options import parse_args, validate_accelerated, validate_ert, validate_occ_fused, validate_occupancy
+from .options import parse_args, validate_accelerated, validate_ert, validate_occ_fused, validate_occupancy, validate_ray_cull
 from .render import get_embedder, get_rays, render, render_frames, run_network
 
 
@@ -99,7 +99,8 @@ def store_main(args, H, W, focal, near, far, rand_pose, ndc, rank, world, device
         store = RayStore(cap, device, seed=9973 * rank, logger=logger)
     t0 = time.time()
     filler = TeacherFill(store, args, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                         rand_pose=rand_pose, ndc=ndc, occ_args=args if fused_skipping(args) else None)
+                         rand_pose=rand_pose, ndc=ndc, occ_args=args if fused_skipping(args) else None,
+                         ray_cull=bool(args.r2l_ray_cull))
     prov = filler.provenance()
     while not filler.done:
         filler.fill_group()
@@ -117,12 +118,14 @@ def main(argv=None):
     validate_occupancy(args)
     validate_occ_fused(args, ("r2l_fused_frames", "r2l_store_save"))
     validate_ert(args, ("r2l_fused_frames", "r2l_store_save"))
+    validate_ray_cull(args, entry="create_data")
     if args.r2l_occupancy and args.r2l_store_save:
         raise ValueError("--r2l_occupancy: not with --r2l_store_save, which renders through the fused frames call (no host read of "
                          "the live count)")
     if args.create_data != "rand":
         raise NotImplementedError("only --create_data rand (the README pipeline) is on the accelerated path")
     rank, world, device = init_distributed()
+    validate_ray_cull(args, device.type, entry="create_data")
     if args.r2l_store_save:  # the store is filled through the fused frames path: its refusals, before anything is loaded
         from .online_kd import check_teacher_args
         check_teacher_args(args, device)

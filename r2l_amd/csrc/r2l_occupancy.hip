@@ -11,6 +11,9 @@
 //                    counts in stream order;
 //   r2l_occ_index_seg  r2l_occ_index over one segment of consecutive sample numbers of every ray, without the rays whose transmittance
 //                    is below eps, the grid optional (one more template switch of the same kernels);
+//   r2l_occ_rays     the rays that meet an occupied cell at any of T depths (a light-field student can leave out whole rays only):
+//                    flag + count per 2048 rays, the scan of r2l_occ_index, placement; r2l_rays_gather and r2l_rgb_scatter_bg are the
+//                    two small kernels of a culled frame (include/r2l_hip.h "whole rays");
 //   r2l_ert_advance  a ray's transmittance through a segment, from the raw the point network has written (early ray termination,
 //                    include/r2l_hip.h "early ray termination").
 // No kernel of the point network is touched here.  Nothing here is compute-bound: build is the network's time, compact and scatter
@@ -272,6 +275,123 @@ __global__ void r2l_occ_live_add_kernel(const int64_t* __restrict__ count, int64
     }
 }
 
+// ---- whole rays: does a ray meet an occupied cell? (r2l_occ_rays) -------------------------------------------------------------------
+// A ray is live iff any of its T points o + d * t_j, t_j = near + ((float)j + 0.5f) * dt, is live by occ_live.  A sub-wave of
+// RAY_LANES lanes owns a ray: lane l tests the depths l, l + RAY_LANES, ... and the sub-wave stops at the first round with a hit
+// (the loop itself is wave-uniform: it ends when every sub-wave of the wave is done).  The lanes of a sub-wave read the same o and
+// d (one address: a broadcast); the grid's bits are read where the points fall — 256 KB at 128^3, resident in L2, no LDS copy.
+// Workgroup b owns the rays [b * 2048, (b + 1) * 2048), as the sample kernels above own samples: launch 1 writes a flag byte per ray
+// and the workgroup's count, launch 2 is r2l_occ_scan_kernel, launch 3 places the flagged rays behind the offset (ascending r).
+constexpr int RAY_LANES = 16;
+constexpr int RAY_THREADS = 1024;
+constexpr int RAY_PER_PASS = RAY_THREADS / RAY_LANES;  // 64 rays a pass, 32 passes a workgroup
+
+__global__ __launch_bounds__(RAY_THREADS) void r2l_occ_rays_flag_kernel(const OccGrid g, const float* __restrict__ o,
+                                                                        const float* __restrict__ d, int64_t R, float near, float dt, int T,
+                                                                        uint8_t* __restrict__ flags, unsigned* __restrict__ blk) {
+    __shared__ unsigned wsum[RAY_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6, sub = t & (RAY_LANES - 1);
+    const int shift = lane & ~(RAY_LANES - 1);  // where the sub-wave's bits sit in a ballot
+    const int64_t base = (int64_t)blockIdx.x * OCC_CHUNK;
+    unsigned running = 0;
+#pragma unroll 1
+    for (int pass = 0; pass < OCC_CHUNK / RAY_PER_PASS; ++pass) {
+        const int64_t r = base + pass * RAY_PER_PASS + (t >> 4);
+        const bool have = r < R;
+        float ox = 0.f, oy = 0.f, oz = 0.f, dx = 0.f, dy = 0.f, dz = 0.f;
+        if (have) {
+            ox = o[r * 3 + 0]; oy = o[r * 3 + 1]; oz = o[r * 3 + 2];
+            dx = d[r * 3 + 0]; dy = d[r * 3 + 1]; dz = d[r * 3 + 2];
+        }
+        bool done = !have, hit = false;
+#pragma unroll 1
+        for (int j0 = 0; j0 < T; j0 += RAY_LANES) {
+            const int j = j0 + sub;
+            bool live = false;
+            if (!done && j < T) {
+                const float tj = near + ((float)j + 0.5f) * dt;  // (no contraction: product and sum rounded separately)
+                live = occ_live(g, ox + dx * tj, oy + dy * tj, oz + dz * tj);  // the point as r2l_occ_index forms it
+            }
+            const unsigned long long m = __ballot(live);
+            if ((m >> shift) & ((1ull << RAY_LANES) - 1ull)) hit = done = true;
+            if (__ballot(!done) == 0ull) break;  // (uniform over the wave)
+        }
+        const bool mine = have && sub == 0;
+        if (mine) flags[r] = hit ? 1 : 0;
+        running += (unsigned)__popcll(__ballot(mine && hit));  // (every lane carries the wave's count)
+    }
+    if (lane == 0) wsum[w] = running;
+    __syncthreads();
+    if (t == 0) {
+        unsigned s = 0;
+        for (int j = 0; j < RAY_THREADS / 64; ++j) s += wsum[j];
+        blk[blockIdx.x] = s;
+    }
+}
+
+// the placement of r2l_occ_compact_kernel<true> with the predicate read from the flags
+__global__ __launch_bounds__(OCC_THREADS) void r2l_occ_rays_place_kernel(const uint8_t* __restrict__ flags, int64_t R,
+                                                                         const unsigned* __restrict__ blk, int64_t* __restrict__ idx) {
+    __shared__ unsigned wsum[OCC_THREADS / 64];
+    const int t = threadIdx.x, lane = t & 63, w = t >> 6;
+    const int64_t base = (int64_t)blockIdx.x * OCC_CHUNK;
+    unsigned running = blk[blockIdx.x];
+#pragma unroll 1
+    for (int r = 0; r < OCC_ROUNDS; ++r) {
+        const int64_t n = base + r * OCC_THREADS + t;
+        const bool live = n < R && flags[n] != 0;
+        const unsigned long long m = __ballot(live);
+        if (lane == 0) wsum[w] = (unsigned)__popcll(m);
+        __syncthreads();
+        unsigned before = 0, total = 0;
+#pragma unroll
+        for (int j = 0; j < OCC_THREADS / 64; ++j) {
+            const unsigned c = wsum[j];
+            if (j < w) before += c;
+            total += c;
+        }
+        if (live) idx[(int64_t)running + before + (unsigned)__popcll(m & ((1ull << lane) - 1ull))] = n;
+        running += total;
+        __syncthreads();
+    }
+}
+
+// out row i = row idx[i] of rays_o / rays_d; an index outside [0, R) gives a NaN row and reads nothing
+__global__ __launch_bounds__(OCC_THREADS) void r2l_rays_gather_kernel(const float* __restrict__ o, const float* __restrict__ d, int64_t R,
+                                                                      const int64_t* __restrict__ idx, int64_t M, float* __restrict__ out_o,
+                                                                      float* __restrict__ out_d) {
+    const float nan = __int_as_float(0x7fc00000);
+    for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < M * 3; e += (int64_t)gridDim.x * blockDim.x) {
+        const int64_t i = e / 3, n = idx[i];
+        const int c = (int)(e - i * 3);
+        const bool ok = n >= 0 && n < R;
+        out_o[e] = ok ? o[n * 3 + c] : nan;
+        out_d[e] = ok ? d[n * 3 + c] : nan;
+    }
+}
+
+// thread r: a dead ray's row = bg; and, as thread i = r < M, row idx[i] = rgb_live[i].  idx lists exactly the rays with live != 0
+// (one r2l_occ_rays call made both), so no row is written twice
+__global__ __launch_bounds__(OCC_THREADS) void r2l_rgb_scatter_bg_kernel(const float* __restrict__ rgb_live, const int64_t* __restrict__ idx,
+                                                                         int64_t M, const uint8_t* __restrict__ live, float bg,
+                                                                         float* __restrict__ out, int64_t R) {
+    for (int64_t r = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; r < R; r += (int64_t)gridDim.x * blockDim.x) {
+        if (live[r] == 0) {
+            out[r * 3 + 0] = bg;
+            out[r * 3 + 1] = bg;
+            out[r * 3 + 2] = bg;
+        }
+        if (r < M) {
+            const int64_t n = idx[r];
+            if (n >= 0 && n < R) {
+                out[n * 3 + 0] = rgb_live[r * 3 + 0];
+                out[n * 3 + 1] = rgb_live[r * 3 + 1];
+                out[n * 3 + 2] = rgb_live[r * 3 + 2];
+            }
+        }
+    }
+}
+
 // ---- early ray termination: the transmittance through a segment ----------------------------------------------------------------
 // trans[r] = (s0 == 0 ? 1 : trans[r]) * prod over s0 <= s < s1, in ascending s, of f_s = (1 - alpha_s) + 1e-10, alpha_s by the
 // per-sample expressions of r2l_raw2outputs without noise.  A workgroup owns ERT_RAYS rays.  Phase 1: all 256 threads form the
@@ -530,6 +650,86 @@ extern "C" int r2l_occ_index(const r2l_occ_grid* grid, const float* rays_o, cons
                        count_out);
     R2L_CHECK(hipGetLastError());
     hipLaunchKernelGGL((r2l_occ_compact_kernel<true, false>), dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, a);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int64_t r2l_occ_rays_work_bytes(int64_t R) {
+    if (R < 0 || R >= ((int64_t)1 << 31)) {
+        r2l_set_error_msg("r2l_occ_rays_work_bytes: need 0 <= R < 2^31");
+        return -1;
+    }
+    return r2l_occ_compact_work_bytes(R) + (R + 15) / 16 * 16;  // the per-workgroup counts, then a flag byte per ray
+}
+
+// The live rays of [R]: flag + count per 2048 rays, the scan of r2l_occ_index, placement.  The flags go to live_out when it is
+// given, else into work.
+extern "C" int r2l_occ_rays(const r2l_occ_grid* grid, const float* rays_o, const float* rays_d, int64_t R, float near, float far, int T,
+                            int64_t* idx_out, int64_t* count_out, uint8_t* live_out, void* work, void* stream) {
+    if (const char* why = occ_grid_check(grid, "r2l_occ_rays: grid is NULL")) {
+        r2l_set_error_msg(why);
+        return (int)hipErrorInvalidValue;
+    }
+    R2L_REQUIRE(R >= 0, "r2l_occ_rays: R is negative");
+    R2L_REQUIRE(R < ((int64_t)1 << 31), "r2l_occ_rays: R: need R < 2^31");
+    R2L_REQUIRE(T >= 1, "r2l_occ_rays: T: need T >= 1");
+    R2L_REQUIRE(near - near == 0.f && far - far == 0.f, "r2l_occ_rays: near / far: not finite");
+    R2L_REQUIRE(near <= far, "r2l_occ_rays: near / far: need near <= far");
+    const float dt = (far - near) / (float)T;
+    R2L_REQUIRE(dt - dt == 0.f, "r2l_occ_rays: near / far: far - near is out of fp32 range");
+    R2L_REQUIRE(count_out != nullptr, "r2l_occ_rays: count_out is NULL");
+    hipStream_t s = (hipStream_t)stream;
+    if (R == 0) {
+        R2L_CHECK(hipMemsetAsync(count_out, 0, sizeof(int64_t), s));
+        return 0;
+    }
+    R2L_REQUIRE(rays_o != nullptr, "r2l_occ_rays: rays_o is NULL");
+    R2L_REQUIRE(rays_d != nullptr, "r2l_occ_rays: rays_d is NULL");
+    R2L_REQUIRE(idx_out != nullptr, "r2l_occ_rays: idx_out is NULL");
+    R2L_REQUIRE(work != nullptr, "r2l_occ_rays: work is NULL");
+    R2L_REQUIRE(((uintptr_t)work & 3) == 0, "r2l_occ_rays: work is not 4-byte aligned");
+    unsigned* blk = (unsigned*)work;
+    uint8_t* flags = live_out != nullptr ? live_out : (uint8_t*)work + r2l_occ_compact_work_bytes(R);
+    const int64_t nb = (R + OCC_CHUNK - 1) / OCC_CHUNK;  // <= 2^20
+    hipLaunchKernelGGL(r2l_occ_rays_flag_kernel, dim3((unsigned)nb), dim3(RAY_THREADS), 0, s, occ_dev(grid), rays_o, rays_d, R, near, dt, T,
+                       flags, blk);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(r2l_occ_scan_kernel, dim3(1), dim3(OCC_SCAN_THREADS), 0, s, blk, nb, (nb + OCC_SCAN_THREADS - 1) / OCC_SCAN_THREADS,
+                       count_out);
+    R2L_CHECK(hipGetLastError());
+    hipLaunchKernelGGL(r2l_occ_rays_place_kernel, dim3((unsigned)nb), dim3(OCC_THREADS), 0, s, flags, R, blk, idx_out);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_rays_gather(const float* rays_o, const float* rays_d, int64_t R, const int64_t* idx, int64_t M, float* out_o,
+                               float* out_d, void* stream) {
+    R2L_REQUIRE(R >= 0 && R < ((int64_t)1 << 31), "r2l_rays_gather: R: need 0 <= R < 2^31");
+    R2L_REQUIRE(M >= 0 && M < ((int64_t)1 << 31), "r2l_rays_gather: M: need 0 <= M < 2^31");
+    if (M == 0) return 0;
+    R2L_REQUIRE(idx != nullptr, "r2l_rays_gather: idx is NULL");
+    R2L_REQUIRE(out_o != nullptr, "r2l_rays_gather: out_o is NULL");
+    R2L_REQUIRE(out_d != nullptr, "r2l_rays_gather: out_d is NULL");
+    R2L_REQUIRE(R == 0 || rays_o != nullptr, "r2l_rays_gather: rays_o is NULL");
+    R2L_REQUIRE(R == 0 || rays_d != nullptr, "r2l_rays_gather: rays_d is NULL");
+    hipLaunchKernelGGL(r2l_rays_gather_kernel, dim3(occ_blocks(M * 3, OCC_THREADS)), dim3(OCC_THREADS), 0, (hipStream_t)stream, rays_o,
+                       rays_d, R, idx, M, out_o, out_d);
+    R2L_CHECK(hipGetLastError());
+    return 0;
+}
+
+extern "C" int r2l_rgb_scatter_bg(const float* rgb_live, const int64_t* idx, int64_t M, const uint8_t* live, float bg, float* rgb_out,
+                                  int64_t R, void* stream) {
+    R2L_REQUIRE(R >= 0 && R < ((int64_t)1 << 31), "r2l_rgb_scatter_bg: R: need 0 <= R < 2^31");
+    R2L_REQUIRE(M >= 0 && M <= R, "r2l_rgb_scatter_bg: M: need 0 <= M <= R");
+    R2L_REQUIRE(bg == bg, "r2l_rgb_scatter_bg: bg is NaN");
+    if (R == 0) return 0;
+    R2L_REQUIRE(live != nullptr, "r2l_rgb_scatter_bg: live is NULL");
+    R2L_REQUIRE(rgb_out != nullptr, "r2l_rgb_scatter_bg: rgb_out is NULL");
+    R2L_REQUIRE(M == 0 || rgb_live != nullptr, "r2l_rgb_scatter_bg: rgb_live is NULL");
+    R2L_REQUIRE(M == 0 || idx != nullptr, "r2l_rgb_scatter_bg: idx is NULL");
+    hipLaunchKernelGGL(r2l_rgb_scatter_bg_kernel, dim3(occ_blocks(R, OCC_THREADS)), dim3(OCC_THREADS), 0, (hipStream_t)stream, rgb_live, idx,
+                       M, live, bg, rgb_out, R);
     R2L_CHECK(hipGetLastError());
     return 0;
 }

@@ -19,7 +19,7 @@ from .logger import Logger
 from .metrics import flip, img2mse, lpips, lpips_vgg, mse2psnr, ssim, to8b
 from .nerf_raybased import NeRF_v3_2, PointSampler, PositionalEmbedder
 from .options import (parse_args, validate_accelerated, validate_compact_store, validate_fused_iter, validate_image_store,
-                      validate_ert, validate_occ_fused, validate_occupancy, validate_store_file)
+                      validate_ert, validate_occ_fused, validate_occupancy, validate_ray_cull, validate_store_file)
 from .dist_utils import split_shards
 from .train_step import N_SAMPLE, R2LTrainer, lr_schedule
 
@@ -528,7 +528,7 @@ def _runs(idx):
 
 
 def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, savedir=None, rank=0, world=1, teacher=None,
-                lpips_params=None, lpips_vgg_params=None):
+                lpips_params=None, lpips_vgg_params=None, ray_cull=None):
     """Render poses[rank::world]; returns (rgbs [n,H,W,3], misc with test_loss/test_psnr/test_psnr_v2 over ALL frames)
     and test_ssim / test_flip — main.py:189-398.  No host
     sync inside the loop: metrics stay on the device, frames are written by _FrameWriter, per-frame times come from device
@@ -543,8 +543,12 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
     teacher = dict(hwf=(H, W, focal), chunk=, render_kwargs=): the `model_name in ['nerf']` branch (main.py:275-282): every
     frame is render(H, W, focal, chunk, c2w=pose[:3,:4], **render_kwargs) of r2l_amd/render.py (coarse + fine NeRF on the
     teacher kernels); `model` = render_kwargs['network_fn'], `point_sampler` unused.  With fused=True in that dict
-    (--r2l_fused_frames; GPU only) the frames come from render_frames in groups of POSES_PER_LAUNCH instead."""
+    (--r2l_fused_frames; GPU only) the frames come from render_frames in groups of POSES_PER_LAUNCH instead.
+    ray_cull = a ray_cull.RayCull (--r2l_ray_cull; student branch, GPU): the rays of a launch group that meet no occupied cell are
+    left out of the forward and get the background colour exactly; None: nothing changes."""
     model.eval()
+    if ray_cull is not None and (teacher is not None or device.type != "cuda"):
+        raise ValueError("--r2l_ray_cull culls the student's renders on a GPU (not the teacher branch, not a CPU run)")
     mine = list(range(rank, len(poses), world))
     rgbs, gts, sq_err, psnrs, ssims, events, errors = [], [], [], [], [], [], []
     if savedir is not None:
@@ -628,7 +632,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
             e0.record()
             c2ws = torch.stack([torch.as_tensor(poses[i], dtype=torch.float32)[:3, :4] for i in idx], 0)
             with torch.no_grad():
-                frames = model.render_poses(c2ws, point_sampler).view(len(idx), point_sampler.H, point_sampler.W, 3)
+                frames = (model.render_poses(c2ws, point_sampler) if ray_cull is None else
+                          ray_cull.render_poses(model, c2ws, point_sampler)).view(len(idx), point_sampler.H, point_sampler.W, 3)
             e1.record()
             events.append((idx, e0, e1))
             for k, i in enumerate(idx):
@@ -652,6 +657,8 @@ def render_path(poses, model, point_sampler, device, logger, gt_imgs=None, saved
         writer.flush()  # (shared writer: threads and pinned slots stay for the next evaluation)
     if on_gpu:
         sync(device)
+        if ray_cull is not None:
+            ray_cull.log(logger, "ray cull (student renders so far)")
         for idx, e0, e1 in events:
             for i in idx:  # (one launch per group of frames: its time divided evenly)
                 logger.info("[#%d] frame, rendering done, time for this frame: %.4fs" % (i, e0.elapsed_time(e1) * 1e-3 / len(idx)))
@@ -716,7 +723,7 @@ def lpips_field(misc):
 
 
 # ---------------------------------------------------------------------------------------------------------------
-def open_training_source(args, scene, H, W, focal, near, far, shards, start, rank, world, device, logger):
+def open_training_source(args, scene, H, W, focal, near, far, shards, start, rank, world, device, logger, ray_cull=None):
     """The source of this rank's training batches, as the options say: a store the teacher fills (--r2l_online_kd, plain or
     --r2l_compact_store), a store of the scene's real training rays (--r2l_image_store, alone or behind the teacher's), a store
     file (--r2l_store_load), a store the shard files are read into once (--r2l_device_store), or the reader of the shard files.  shards: shard files per step of every rank; start: the iteration a resumed run starts
@@ -751,7 +758,8 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
         else:
             loader = RayStore(cap, device, seed=9973 * rank, logger=logger)
         filler = TeacherFill(loader, targs, H, W, focal, near, far, n_pose, args.create_data_chunk, rank, world, device, logger,
-                             rand_pose=scene.rand_pose, ndc=scene.ndc, occ_args=args if (args.r2l_occ_fused or args.r2l_ert > 0) else None)
+                             rand_pose=scene.rand_pose, ndc=scene.ndc, occ_args=args if (args.r2l_occ_fused or args.r2l_ert > 0) else None,
+                             ray_cull=ray_cull)
         # a resumed run rebuilds what the store held at its start iteration: the frames are a pure function of seed and pose
         # number, so these are the same rows bit for bit
         n_groups = None if args.r2l_kd_every <= 0 else 1 + start // args.r2l_kd_every
@@ -809,6 +817,14 @@ def open_training_source(args, scene, H, W, focal, near, far, shards, start, ran
             raise ValueError("--r2l_store_load %s: a compact store hands out batches through its own kernel: not with "
                              "--r2l_fused_iter, which reads the 36-byte rows of the plain store" % path)
         logger.info("ray store file %s: provenance %s" % (path, json.dumps(hdr["provenance"], sort_keys=True)))
+        if ray_cull is not None:  # the file is used as it is; the log says whether its rows were culled with this run's grid
+            theirs = hdr["provenance"].get("ray_cull") if isinstance(hdr["provenance"], dict) else None
+            diff = ["the file's provenance has no ray_cull entry (its rows were not culled)"] if not theirs else ray_cull.mismatch(theirs)
+            logger.info("ray cull: the store file %s" % ("was culled with this run's grid" if not diff else
+                                                         "and this run's grid DIFFER — " + "; ".join(diff)))
+        if isinstance(hdr["provenance"], dict) and hdr["provenance"].get("ray_cull") and not args.r2l_ray_cull:
+            raise ValueError("--r2l_store_load %s: its provenance says ray_cull (the store holds no ray that sees only empty space): "
+                             "train on it with --r2l_ray_cull, so that every render of the run is culled too" % path)
         loader = load_store(path, device, seed=9973 * rank, logger=logger)
         files = loader.files
     elif args.r2l_device_store:
@@ -845,6 +861,7 @@ def main(argv=None):
     validate_fused_iter(args)
     validate_compact_store(args)
     validate_store_file(args)
+    validate_ray_cull(args)
     is_teacher = args.model_name == "nerf"
     if is_teacher and (not args.render_only or args.benchmark):
         # (--benchmark times render_func = the R2L student's forward, main.py:401-404,1124-1133)
@@ -863,6 +880,7 @@ def main(argv=None):
         validate_occ_fused(args, ("r2l_online_kd",), raw_noise_std=0., use_viewdirs=targs_.use_viewdirs if targs_ is not None else True)
         validate_ert(args, ("r2l_online_kd",), raw_noise_std=0., use_viewdirs=targs_.use_viewdirs if targs_ is not None else True)
     rank, world, device = init_distributed()
+    validate_ray_cull(args, device.type)
     if args.r2l_device_pool and not (args.render_only or args.benchmark) and device.type != "cuda":
         raise NotImplementedError("--r2l_device_pool ranks the hard rays and draws the jitter on the GPU (r2l_pool_select, "
                                   "r2l_draw_uniform of libr2l_hip.so); this run is on the CPU")
@@ -890,7 +908,7 @@ def main(argv=None):
     if args.focal_scale > 0:
         focal *= args.focal_scale
 
-    teacher = None
+    teacher = ray_cull = None
     if is_teacher:
         kwargs_test = create_nerf_teacher(args, device, logger, near, far, ndc=scene.ndc)
         model, point_sampler = kwargs_test["network_fn"], None
@@ -911,13 +929,21 @@ def main(argv=None):
         if ckpt is not None and ckpt.get("r2l_config"):
             was = ckpt["r2l_config"]
             logger.info("checkpoint was trained with r2l_config: precision %s, dw_mode %s" % (was.get("precision"), was.get("dw_mode")))
+        if args.r2l_ray_cull:  # the grid of every student render of this run, of the store fill, and of the checkpoints it writes
+            from . import ray_cull as _rc
+            # (a training run renders its first student frame after the store fill: the fill's grid serves, nothing is built twice)
+            ray_cull = _rc.for_run(args, ckpt, near, far, device, logger,
+                                   fill_builds=bool(args.r2l_online_kd) and not (args.test_pretrained or args.render_only or args.benchmark))
+        elif ckpt is not None and ckpt.get("r2l_ray_cull") is not None:
+            logger.info("WARNING: the checkpoint carries a grid (key r2l_ray_cull): it was trained on a culled ray store and has never "
+                        "seen a background ray; this run is without --r2l_ray_cull and renders every ray through it")
     test_poses, test_images = poses[i_test], images[i_test]
     video_poses = scene.video_poses
     start, best_psnr, best_psnr_step = history["start"], history["best_psnr"], history["best_psnr_step"]
 
     if args.test_pretrained:
         _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images, rank=rank,
-                              world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
+                              world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w, ray_cull=ray_cull)
         logger.info("Pretrained test: TestLoss %.4f TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
                     (misc["test_loss"].item(), misc["test_psnr"].item(), misc["test_psnr_v2"].item(),
                      misc["test_ssim"].item(), lpips_field(misc), misc["test_flip"].item()))
@@ -929,13 +955,13 @@ def main(argv=None):
         if args.render_test:
             rgbs, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
                                      savedir=logger.gen_img_path if rank == 0 or world > 1 else None, rank=rank,
-                                     world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
+                                     world=world, teacher=teacher, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w, ray_cull=ray_cull)
             logger.info("[TEST] TestPSNR %.4f TestPSNRv2 %.4f TestSSIM %.4f%s TestFLIP %.4f" %
                         (misc["test_psnr"].item(), misc["test_psnr_v2"].item(), misc["test_ssim"].item(), lpips_field(misc),
                          misc["test_flip"].item()))
         else:
             rgbs, misc = render_path(video_poses, model, point_sampler, device, logger, savedir=logger.gen_img_path,
-                                     rank=rank, world=world, teacher=teacher)
+                                     rank=rank, world=world, teacher=teacher, ray_cull=ray_cull)
         n_rays = rgbs.numel() // 3 if rgbs.numel() else 0  # (frames x rendered pixels: --render_factor shrinks the teacher's frames)
         dt = time.time() - t_
         logger.info("Rendered %d frames (%d rays) in %.2fs on rank %d = %.0f rays/s incl. I/O; frames in %s" %
@@ -989,7 +1015,8 @@ def main(argv=None):
         shards = split_shards(args.N_rand, world)
     except ValueError as e:
         raise SystemExit(str(e))
-    loader, files, filler = open_training_source(args, scene, H, W, float(hwf[2]), near, far, shards, start, rank, world, device, logger)
+    loader, files, filler = open_training_source(args, scene, H, W, float(hwf[2]), near, far, shards, start, rank, world, device, logger,
+                                                 ray_cull=ray_cull)
     uneven = len(set(shards)) > 1
     if uneven:
         logger.info("--N_rand %d over %d ranks: %s shard files per rank and step; gradients weighted by ray share" %
@@ -1021,7 +1048,8 @@ def main(argv=None):
                             (0 if pool.pool is None else pool.pool.shape[0], pool.full, pool._draws))
             else:
                 logger.info("hard-ray pool: the checkpoint carries none (written without --r2l_device_pool?): it starts empty")
-    pool_extra = lambda: {"r2l_hard_pool": pool.state_dict()} if save_pool else None
+    pool_extra = lambda: ({**({"r2l_hard_pool": pool.state_dict()} if save_pool else {}),
+                           **({"r2l_ray_cull": ray_cull.state()} if ray_cull is not None else {})} or None)
     if args.r2l_fused_iter:
         # the whole iteration below — batch, pool rows, jitter, step, pool update — is one call of r2l_student_train_step
         logger.info("[Config] Fused iteration (--r2l_fused_iter): one library call per iteration, jitter from Philox stream "
@@ -1080,7 +1108,8 @@ def main(argv=None):
             os.makedirs(savedir, exist_ok=True)
             t_ = time.time()
             _, misc = render_path(test_poses, model, point_sampler, device, logger, gt_imgs=test_images,
-                                  savedir=savedir, rank=rank, world=world, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w)
+                                  savedir=savedir, rank=rank, world=world, lpips_params=lpips_w, lpips_vgg_params=lpips_vgg_w,
+                                  ray_cull=ray_cull)
             if misc["test_psnr_v2"] > best_psnr:
                 best_psnr, best_psnr_step = misc["test_psnr_v2"].item(), i
                 if rank == 0:
@@ -1095,7 +1124,7 @@ def main(argv=None):
             # test: using novel poses (main.py:1473-1484)
             logger.info("Iter %d Rendering video... (n_pose: %d)" % (i, len(video_poses)))
             t_ = time.time()
-            rgbs, _ = render_path(video_poses, model, point_sampler, device, logger, rank=rank, world=world)
+            rgbs, _ = render_path(video_poses, model, point_sampler, device, logger, rank=rank, world=world, ray_cull=ray_cull)
             path = save_video(rgbs, logger, logger.ExpID, i, args.video_tag, rank, world, device)
             if rank == 0:
                 logger.info('Iter %d Save video: "%s" (time: %.2fs)' % (i, path, time.time() - t_))

@@ -139,6 +139,65 @@ def compact_spec(bits, lo, inv, G, rays_o, rays_d, viewdirs, z):
     return int(idx.size), idx, o[r], d[r], v[r], z.reshape(-1)[idx]
 
 
+def ray_depths(near, far, T):
+    """float32[T]: t_j = near + ((float)j + 0.5f) * dt, dt = (far - near) / (float)T, every operation rounded separately — the
+    depths r2l_occ_rays steps along a ray."""
+    near, far, T = F32(near), F32(far), int(T)
+    if T < 1 or not (np.isfinite(near) and np.isfinite(far)) or far < near:
+        raise ValueError("ray_depths: need T >= 1 and finite near <= far, got T = %d, near %r, far %r" % (T, near, far))
+    dt = F32(F32(far - near) / F32(T))
+    return (near + ((np.arange(T).astype(F32) + F32(.5)).astype(F32) * dt).astype(F32)).astype(F32)
+
+
+def rays_spec(bits, lo, inv, G, rays_o, rays_d, near, far, T):
+    """What r2l_occ_rays writes: (M, idx int64[M] ascending, live uint8[R]).  Stated on compact_spec, as include/r2l_hip.h states
+    the call on r2l_occ_index: with z[r, j] = ray_depths(near, far, T)[j] for all rays, ray r is live iff compact_spec lists any
+    sample n in [r*T, (r+1)*T)."""
+    o, d = (np.asarray(t, dtype=F32).reshape(-1, 3) for t in (rays_o, rays_d))
+    R, T = o.shape[0], int(T)
+    z = np.broadcast_to(ray_depths(near, far, T)[None, :], (R, T))
+    live = np.zeros(R, dtype=np.uint8)
+    for a in range(0, R, 65536):  # (slabs of rays: z[R,T] points are the spec's memory, not the kernel's)
+        b = min(a + 65536, R)
+        _, n, *_ = compact_spec(bits, lo, inv, G, o[a:b], d[a:b], o[a:b], z[a:b])
+        live[a + np.unique(n // T)] = 1
+    idx = np.flatnonzero(live).astype(np.int64)
+    return int(idx.size), idx, live
+
+
+def frame_d_max(H, W, focal):
+    """The largest |rays_d| of an H x W pinhole frame (r2l_frame_rays: d = R (x, y, -1), R a rotation), a little above it:
+    sqrt(1 + (W/(2 f))^2 + (H/(2 f))^2).  focal: the SMALLEST focal in use (under use_rand_focal the scene's: the draws scale it
+    up)."""
+    f = float(focal)
+    if not f > 0:
+        raise ValueError("frame_d_max: need focal > 0, got %r" % (focal,))
+    return float(np.sqrt(1. + (W / (2. * f))**2 + (H / (2. * f))**2))
+
+
+def cull_steps(grid, near, far, d_max):
+    """The smallest T with (far - near) / T * d_max <= the smallest cell side of `grid` (an OccupancyGrid), at least 1: with it
+    and a grid dilated by at least one cell, every point of a dead ray's segment [near, far] lies within half a cell of a sample
+    that is inside the box and in a clear cell — so the point's own cell was clear BEFORE the dilation, or the point is at most half
+    a cell outside the box (include/r2l_hip.h r2l_occ_rays).  Refuses a grid built with dilate < 1: the argument needs the ring."""
+    if grid.dilate < 1:
+        raise ValueError("cull_steps: the ray rule needs a grid dilated by at least one cell (dilate >= 1), this one has dilate = %d"
+                         % grid.dilate)
+    near, far, d_max = float(near), float(far), float(d_max)
+    if not (np.isfinite(near) and np.isfinite(far) and far >= near and np.isfinite(d_max) and d_max > 0):
+        raise ValueError("cull_steps: need finite near <= far and d_max > 0, got near %r, far %r, d_max %r" % (near, far, d_max))
+    side = float(((grid.hi.astype(np.float64) - grid.lo.astype(np.float64)) / grid.G).min())
+    span = (far - near) * d_max
+    T = max(int(np.ceil(span / side)), 1)
+    while T > 1 and span / (T - 1) <= side:  # (the quotient's rounding: settle on the definition)
+        T -= 1
+    while span / T > side:
+        T += 1
+    if T >= 2**31:
+        raise ValueError("cull_steps: %d steps (cells far smaller than the segment)" % T)
+    return T
+
+
 def scatter_spec(raw_live, idx, R, S):
     """What r2l_occ_scatter writes: float32[R,S,4], zero but for raw_out[idx[i]] = raw_live[i]."""
     out = np.zeros((int(R) * int(S), 4), dtype=F32)
@@ -325,6 +384,31 @@ class OccupancyGrid:
             if live_acc is not None:
                 _lib.check(lib.r2l_occ_live_add(_ptr(b["count"]), R * S, _ptr(live_acc), _stream()), "r2l_occ_live_add")
         return b["idx"][:max(R * S, 1)], b["count"]
+
+    def rays(self, rays_o, rays_d, near, far, T):
+        """(idx, count, live): the numbers of the rays that meet an occupied cell at any of their T depths (r2l_occ_rays), ascending,
+        in an int64 tensor of capacity R (entries at and past the count are not written), their count as an int64[1] device tensor —
+        nothing is read on the host — and a uint8[R] flag per ray.  The returned tensors are views of buffers the grid re-uses on
+        the next call."""
+        self._need_built()
+        R, dev = int(rays_o.shape[0]), rays_o.device
+        if self.bits.device != dev:
+            raise ValueError("occupancy grid: built on %s, the rays are on %s" % (self.bits.device, dev))
+        key = ("rays", dev.type, dev.index)
+        b = self._buf.get(key)
+        lib = _lib.load()
+        if b is None or b["n"] < R:
+            n = max(R, 1)
+            b = self._buf[key] = dict(n=n, idx=torch.empty(n, dtype=torch.int64, device=dev),
+                                      count=torch.empty(1, dtype=torch.int64, device=dev),
+                                      live=torch.empty(n, dtype=torch.uint8, device=dev),
+                                      work=torch.empty(max(lib.r2l_occ_rays_work_bytes(n), 16), dtype=torch.uint8, device=dev))
+        rays_o, rays_d = rays_o.contiguous(), rays_d.contiguous()  # (named: a copy must live until the launch is enqueued)
+        with torch.cuda.device(dev):
+            _lib.check(lib.r2l_occ_rays(ctypes.byref(self.desc()), _ptr(rays_o), _ptr(rays_d), R, float(near),
+                                        float(far), int(T), _ptr(b["idx"]), _ptr(b["count"]), _ptr(b["live"]), _ptr(b["work"]),
+                                        _stream()), "r2l_occ_rays")
+        return b["idx"][:max(R, 1)], b["count"], b["live"][:R]
 
     @staticmethod
     def scatter(raw_live, idx, R, S):

@@ -44,7 +44,7 @@ class TeacherFill:
     """State of an incremental fill: the rank's pose list, its RandomState, the teacher pair and what is still pending."""
 
     def __init__(self, store, targs, H, W, focal, near, far, n_pose, chunk_poses, rank, world, device, logger=None,
-                 rand_pose=None, ndc=False, occ_args=None):
+                 rand_pose=None, ndc=False, occ_args=None, ray_cull=None):
         from .create_data import create_teacher
         from .driver import apply_arithmetic
         check_teacher_args(targs, device)
@@ -73,6 +73,23 @@ class TeacherFill:
                 raise ValueError("--r2l_occ_fused puts its box about the origin of a bounded scene: not with an NDC (llff) scene")
             self.occ = FusedOccupancy(occ_args, self.coarse, self.fine, self.near, self.far, _Quiet() if logger is None else logger)
             self.occ_prov = self.occ.provenance()  # (kept: the grids go with the teacher in release())
+        # --r2l_ray_cull (ray_cull: a ray_cull.RayCull, or True for one on this fill's own grid — the grid of the net that makes the
+        # final colour): the rays of a group that meet no occupied cell are not appended.  T from the SCENE's focal: the smallest in
+        # use (use_rand_focal scales it up)
+        self.cull = self.cull_T = None
+        if ray_cull:
+            from .ray_cull import RayCull
+            if self.occ is None or self.occ.pair is None:
+                raise ValueError("--r2l_ray_cull culls the fill with the grids of --r2l_occ_fused: give that switch too")
+            if hasattr(store, "append_frames"):
+                raise ValueError("--r2l_ray_cull: not with --r2l_compact_store, whose rows keep a ray's number in its flush group")
+            if isinstance(ray_cull, RayCull):  # the run's own (a checkpoint's grid), or deferred: it adopts this fill's grid
+                self.cull = ray_cull if ray_cull.grid is not None else ray_cull.adopt(self.occ.pair[1], targs.white_bkgd)
+            else:
+                self.cull = RayCull(self.occ.pair[1], self.near, self.far, targs.white_bkgd)
+            self.cull_T = self.cull.steps(self.H, self.W, self.focal)
+            self.cull_live, self.cull_total = 0, 0
+            self.occ_prov = {**self.occ_prov, "ray_cull": self.cull.provenance(self.cull_T)}
 
     @property
     def pending(self):
@@ -125,7 +142,15 @@ class TeacherFill:
         rows = parts[0] if len(parts) == 1 else torch.cat(parts, 0)
         key = int(self.rng.randint(0, 2**31 - 1))  # the flush seed: drawn where create_data.main's flush() draws it
         e[1].record()
-        m = self.store.append_frames(rows, c2ws, focals, key, shuffle=True) if compact else self.store.append(rows, key, shuffle=True)
+        if self.cull is not None:
+            # r2l_occ_rays on the group's WORLD o, d; ONE 8-byte read of the count per flush group; r2l_store_append_live
+            M, idx, _ = self.cull.live_index(rows[:, 0:3], rows[:, 3:6], self.cull_T)
+            self.cull_live += M
+            self.cull_total += int(rows.shape[0])
+            self._info("ray cull: live rays %d / %d (%.1f%%) of the flush group" % (M, rows.shape[0], 100. * M / max(rows.shape[0], 1)))
+            m = self.store.append_live(rows, idx, M, key, shuffle=True)
+        else:
+            m = self.store.append_frames(rows, c2ws, focals, key, shuffle=True) if compact else self.store.append(rows, key, shuffle=True)
         e[2].record()
         self.append_ms.append(e)
         self.at += len(group)
@@ -144,6 +169,9 @@ class TeacherFill:
             if self.logger is not None:
                 self.occ.log(self.logger)
             self.occ = None
+        if self.cull is not None:
+            self._info("ray cull: live rays %d / %d (%.1f%%) of the whole fill" %
+                       (self.cull_live, self.cull_total, 100. * self.cull_live / max(self.cull_total, 1)))
         freed = 0
         for net in (self.coarse, self.fine):
             eng = net.__dict__.pop("_r2l_teacher_engine", None)

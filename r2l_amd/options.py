@@ -67,6 +67,13 @@ FLAGS = {
     # main.py --model_name nerf --render_only with --r2l_fused_frames, main.py --r2l_online_kd.  Shares r2l_occ_res / r2l_occ_bound;
     # not together with --r2l_occupancy (the per-pose path), nor with llff or raw_noise_std > 0.  utils/train_nerf.py ignores it
     "r2l_occ_fused": ("flag", False),
+    # whole rays that see only empty space are left out (r2l_occ_rays; r2l_amd/ray_cull.py): main.py culls EVERY student render of
+    # the run (dead pixels get the background colour exactly) and, with r2l_online_kd and r2l_occ_fused, the rays of the store fill;
+    # utils/create_data.py --r2l_store_save with r2l_occ_fused writes a culled store file.  The grid travels in every checkpoint
+    # (key r2l_ray_cull); a later run takes it from --pretrained_ckpt, else builds it from --teacher_ckpt + --r2l_teacher_config.
+    # GPU only; not with llff or r2l_compact_store.  A run with the switch is another run than one without.  utils/train_nerf.py
+    # ignores it
+    "r2l_ray_cull": ("flag", False),
     # early ray termination in the last pass of the FUSED frames call (r2l_teacher_frames_ert_cfg; r2l_amd/ert.py): the pass is walked
     # front to back in segments of r2l_ert_seg samples and a ray whose transmittance is below r2l_ert (0 = off, at most 0.1) at a
     # segment boundary leaves the segments behind it; a pixel moves by less than r2l_ert.  The paths of r2l_occ_fused, with it or
@@ -376,6 +383,40 @@ def validate_occ_fused(args, paths, raw_noise_std=None, use_viewdirs=None):
         raise ValueError("--r2l_occ_fused: --r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
     if not (args.use_viewdirs if use_viewdirs is None else use_viewdirs):
         raise ValueError("--r2l_occ_fused needs a teacher with --use_viewdirs (the teacher kernels' network)")
+
+
+def validate_ray_cull(args, device_type=None, entry="main", ckpt_has_grid=None):
+    """--r2l_ray_cull as main.py (entry 'main') and utils/create_data.py (entry 'create_data') take it; utils/train_nerf.py accepts
+    and ignores it.  Names the flag, before anything is loaded.  device_type: where the run is, once known (a CPU run is refused, not
+    rendered without culling).  ckpt_has_grid: once --pretrained_ckpt is read (main.py), whether it carries the key r2l_ray_cull —
+    without it the grid is built from the teacher, which then must be named."""
+    if not args.r2l_ray_cull:
+        return
+    if args.dataset_type == "llff":
+        raise ValueError("--r2l_ray_cull asks a grid whose box sits about the origin of a bounded scene: not with --dataset_type llff "
+                         "(NDC space needs a box of its own)")
+    if args.r2l_compact_store:
+        raise ValueError("--r2l_ray_cull: not with --r2l_compact_store, whose rows keep a ray's number in its flush group (a culled "
+                         "compact store would need an id variant of its own)")
+    if device_type is not None and device_type != "cuda":
+        raise ValueError("--r2l_ray_cull runs r2l_occ_rays of libr2l_hip.so on a GPU; this run is on the CPU")
+    if not 1 <= args.r2l_occ_res <= 512:
+        raise ValueError("--r2l_ray_cull: --r2l_occ_res must be in 1 .. 512, got %d" % args.r2l_occ_res)
+    if args.r2l_occ_bound < 0:
+        raise ValueError("--r2l_ray_cull: --r2l_occ_bound must be >= 0 (0: 0.625 (far - near)), got %g" % args.r2l_occ_bound)
+    if entry == "create_data":
+        if not (args.r2l_store_save and args.r2l_occ_fused):
+            raise ValueError("--r2l_ray_cull in utils/create_data.py culls the store fill: it needs --r2l_store_save and "
+                             "--r2l_occ_fused (the grids are built there)")
+        return
+    if args.model_name == "nerf":
+        raise ValueError("--r2l_ray_cull culls the STUDENT's renders and its store: not with --model_name nerf (with grids the "
+                         "teacher's dead rays already cost only the floor)")
+    if args.r2l_online_kd and not args.r2l_occ_fused:
+        raise ValueError("--r2l_ray_cull culls the fill of --r2l_online_kd with the grids of --r2l_occ_fused: give that switch too")
+    if ckpt_has_grid is False and not (args.teacher_ckpt and args.r2l_teacher_config):
+        raise ValueError("--r2l_ray_cull needs a grid: either --pretrained_ckpt names a checkpoint of a run with the switch (it "
+                         "carries the key r2l_ray_cull), or --teacher_ckpt and --r2l_teacher_config name the teacher to build it from")
 
 
 def validate_ert(args, paths, raw_noise_std=None, use_viewdirs=None):

@@ -94,6 +94,22 @@ def append_images_spec(images, c2ws, focals, rays_per_shard, key, shuffle=True):
     return np.concatenate([o, d, images.reshape(-1, 3)[src]], 1)
 
 
+def append_live_spec(rows, idx, rays_per_shard, key, shuffle=True):
+    """What r2l_store_append_live writes into its new shards, in numpy: rows [n_rows, 9], idx int64[M] -> float32[m *
+    rays_per_shard, 9] with m = M // rays_per_shard: row i is rows[idx[perm(key, M)[i]]] — a gather of the M rows followed by
+    r2l_store_append's shuffle over M; an index outside [0, n_rows) gives a NaN row; the tail of the permuted sequence is dropped.
+    shuffle=False: the identity."""
+    rows = np.asarray(rows, dtype=np.float32).reshape(-1, 9)
+    idx = np.asarray(idx, dtype=np.int64).reshape(-1)
+    M = idx.size
+    n_out = M // int(rays_per_shard) * int(rays_per_shard)
+    src = idx[perm_at(key, M, np.arange(n_out, dtype=np.uint64)) if shuffle else np.arange(n_out, dtype=np.int64)]
+    ok = (src >= 0) & (src < rows.shape[0])
+    out = np.full((n_out, 9), np.nan, dtype=np.float32)
+    out[ok] = rows[src[ok]]
+    return out
+
+
 def cstore_batch_spec(rgb_rows, ids, pose_c2w, pose_focal, shard_pose0, H, W, n_shards, rays_per_shard, draw0, n_draw, seed):
     """What r2l_cstore_batch writes, in numpy: (batch float32[n_draw * rays_per_shard, 9], shard ids int32[n_draw]).  rgb_rows
     [>= n_shards * rays_per_shard, 3] and ids (uint32, same length) are the store's rows, pose_c2w [n_pose, 3, 4] / pose_focal
@@ -219,6 +235,22 @@ class RayStore(_Store):
         _lib.check(self._L.r2l_store_append(_p(rows), rows.shape[0], _p(self.data), self.capacity, self.n_shards,
                                             self.rows_per_file, int(key) & M64, int(bool(shuffle)), ctypes.byref(m),
                                             _stream(self.device)), "r2l_store_append")
+        return self._appended(m.value)
+
+    def append_live(self, rows, idx, M, key, shuffle=True):
+        """Append the M rows rows[idx[:M]] (idx: a device int64 tensor, e.g. the live rays of OccupancyGrid.rays; M: its count, read
+        by the caller) as floor(M / rays_per_shard) shards, shuffled by perm(key, M): what append(rows[idx[:M]], key) writes, bit for
+        bit, in one launch and without the gathered rows (r2l_store_append_live).  Returns the number of shards written."""
+        if rows.device != self.device or rows.dtype != torch.float32 or rows.dim() != 2 or rows.shape[1] != 9:
+            raise ValueError("RayStore.append_live: need a [n, 9] fp32 tensor on %s" % self.device)
+        M = int(M)
+        if idx.device != self.device or idx.dtype != torch.int64 or idx.dim() != 1 or not 0 <= M <= idx.shape[0]:
+            raise ValueError("RayStore.append_live: need an int64 index tensor on %s with at least M = %d entries" % (self.device, M))
+        rows, idx = rows.contiguous(), idx.contiguous()
+        m = ctypes.c_int64()
+        _lib.check(self._L.r2l_store_append_live(_p(rows), rows.shape[0], _p(idx), M, _p(self.data), self.capacity, self.n_shards,
+                                                 self.rows_per_file, int(key) & M64, int(bool(shuffle)), ctypes.byref(m),
+                                                 _stream(self.device)), "r2l_store_append_live")
         return self._appended(m.value)
 
     def append_images(self, images, c2ws, focals, key, shuffle=True):
